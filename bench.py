@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — TPC-H Q1 rows/s at SF10 on MI355X through the engine's C ABI.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing else: it sets up, warms up, times the K steps, writes the timed plan's
+answer when --dump-outputs is given, and prints the line.  `--full` adds everything else the line can carry, each measured or
+checked after the timed region: the comparison of the answer with the reference's (`parity_checked`), the CPU baseline, the read
+roofline measured in the same run, `config.phases` of a multi-rank step, `extras`, and for `--path capi` the per-shard kernel
+times.  `--no-cpu-baseline` and `--no-extras` leave parts of that out again.
+
+`--dump-outputs DIR` writes the result relation of the last timed step, what a caller of the path receives: one DIR/<column>.npy
+per column, float64 (DECIMAL columns as their decimal value, CHAR(1) as the character's code, DATE as yyyymmdd).  The tables are
+generated from fixed seeds, so the same arguments give the same inputs in every run, and two builds can be compared file for file.
 
 N > 1 needs one process per GPU.  Two ways in, same code path afterwards:
   * under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`): RANK / LOCAL_RANK /
@@ -15,8 +25,8 @@ One *step* = one execution of the compiled Q1 plan over the whole lineitem table
 (device-generated, deterministic; H2D is not part of any timed region): scan 7 columns -> filter -> 6-group aggregation
 kernel -> group-by merge (one RCCL all-gather of the 42-word partial tables + one fused merge kernel when N > 1) -> host
 finalisation (AVG, projection, ORDER BY) to ReSQL's result relation.  `value` = lineitem rows of the whole job / wall
-time of the K steps (max over ranks).  After the timed region the answer is compared with the UNMODIFIED reference's answer
-on the same rows (tests/golden/ref_full_q1_sf{1,10}.tbl): "parity_checked", and a non-zero exit code on a mismatch.
+time of the K steps (max over ranks).  With --full, after the timed region the answer is compared with the UNMODIFIED reference's
+answer on the same rows (tests/golden/ref_full_q1_sf{1,10}.tbl): "parity_checked", and a non-zero exit code on a mismatch.
 
 N > 1 shards the SF10 table by row range across the ranks ("morsel-sharded", BASELINE.json config 4): total work is
 fixed, so scaling is "strong".
@@ -24,12 +34,12 @@ fixed, so scaling is "strong".
 `--path capi` runs the same step through rsq_multi_* (include/resql_hip.h): ONE host process over the N GPUs, RCCL reduce
 issued by the library — the way a C++ ReSQL host would call it.  Under a launcher only rank 0 works in that mode.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`roofline` in every run, the others with --full):
   roofline     — the scan+aggregate kernel: ALGORITHMIC bytes (38 B/row x rows per launch) / its average
-                 duration measured with HIP events on the engine's stream, against the 8 TB/s HBM3E peak of
-                 /opt/skills/guides/MI355X_MICROARCH.md.  `traffic` is NOT measured by this run: it is the FETCH_SIZE
+                 duration measured with HIP events on the engine's stream during the timed steps, against the MI355X's
+                 8 TB/s HBM3E peak.  `traffic` is NOT measured by this run: it is the FETCH_SIZE
                  figure of the committed rocprofv3 --pmc pass named in `traffic_source`, quoted only when this run has the
-                 same bytes per launch.
+                 same bytes per launch.  `measured_read_roofline` (--full): this box's streaming read rate, measured after the line.
   cpu_baseline — the UNMODIFIED reference (oracle/_ref/ref_harness: ReSQL's asmjit path, threads=1; ReSQL's aggregation
                  pipelines are single-threaded by construction) timed on this box's host cores on the SAME
                  rows the value is quoted on (SF10 lineitem read back from the device table), rank 0, N = 1 only.
@@ -114,7 +124,26 @@ def parse_args(argv=None):
     ap.add_argument("--workload", choices=["q1", "q3"], default="q1",
                     help="q3 (with --share-gpu or under a launcher): TPC-H Q3 with replicated build sides, lineitem sharded on an l_orderkey "
                          "boundary, every rank's own top 10 merged by the sort keys (resql_amd/dist.py merge_ordered_results)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (parity with the reference's answer, CPU "
+                         "baseline, measured read roofline, phases, extras); see the module docstring")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result relation of the last timed step as DIR/<column>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(res, directory: str) -> None:
+    """the result relation a caller of the timed path receives, one float64 array per column (DECIMAL as its decimal value)"""
+    import numpy as np
+    from resql_amd import plan as P
+    os.makedirs(directory, exist_ok=True)
+    for c, (name, t) in enumerate(zip(res.names, res.types)):
+        div = 10 ** t.scale if t.tag == P.DECIMAL else 1       # (Python's int / int is correctly rounded, also past 2**53)
+        col = np.array([res.value(r, c) / div for r in range(res.n_rows)], dtype=np.float64)
+        np.save(os.path.join(directory, f"{name}.npy"), col)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -395,23 +424,10 @@ def run_capi(args) -> int:
         for _ in range(args.steps):
             q.execute()
         elapsed = time.perf_counter() - t0
-        # per-shard kernel times: a second, untimed loop (a report per step inside the timed loop would time its own bookkeeping)
-        probe = max(1, min(args.steps, 20))
-        per = [0.0] * n_dev
-        fin = 0.0
-        coll = 0.0
-        for _ in range(probe):
-            q.execute()
-            rep, k = q.report()
-            per = [a + b for a, b in zip(per, k)]
-            fin += rep.finalize_time_ms
-            coll += q.collective_ms
-        per = [v / probe for v in per]
         result = q.result()
+        if args.dump_outputs:
+            dump_outputs(result, args.dump_outputs)
         rows_per = [t.n_rows for t in shards]
-        bytes_per_launch = tpch.Q1_BYTES_PER_ROW * max(rows_per)
-        slowest = max(per)
-        achieved = bytes_per_launch / (slowest * 1e-3) / 1e9
         out = {
             "metric": "TPC-H Q1 rows/s at SF10", "value": n_total * args.steps / elapsed, "unit": "rows/s",
             "n_gpus": len(set(devices)), "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -419,15 +435,32 @@ def run_capi(args) -> int:
             "config": {"workload": f"TPC-H Q1 over lineitem SF{args.sf:g} ({n_total} rows, 7 columns, 38 B/row) resident in HBM, "
                                    f"row-range sharded over {n_dev} shard(s) on devices {devices}",
                        "rows": n_total, "rows_per_shard": rows_per, "result_groups": result.n_rows, "path": "capi",
-                       "parallelism": f"one host process, rsq_multi_* over {n_dev} shard(s): {m.merge_name}; {q.merge_name}",
-                       "phases": {"kernel_ms_per_rank": per, "collective_ms": coll / probe, "finalize_ms": fin / probe,
-                                  "step_minus_slowest_kernel_ms": elapsed / args.steps * 1e3 - slowest}},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": None, "traffic_source": None,
-                         "kernel": "scan+filter+dense aggregation pipeline (the slowest shard's launches)", "kernel_ms": slowest,
-                         "bytes_per_launch": bytes_per_launch},
+                       "parallelism": f"one host process, rsq_multi_* over {n_dev} shard(s): {m.merge_name}; {q.merge_name}"},
         }
-        rc = check_parity(result.text, args.sf, out)
+        rc = 0
+        if args.full:
+            # per-shard kernel times: a second, untimed loop (a report per step inside the timed loop would time its own bookkeeping)
+            probe = max(1, min(args.steps, 20))
+            per = [0.0] * n_dev
+            fin = 0.0
+            coll = 0.0
+            for _ in range(probe):
+                q.execute()
+                rep, k = q.report()
+                per = [a + b for a, b in zip(per, k)]
+                fin += rep.finalize_time_ms
+                coll += q.collective_ms
+            per = [v / probe for v in per]
+            bytes_per_launch = tpch.Q1_BYTES_PER_ROW * max(rows_per)
+            slowest = max(per)
+            achieved = bytes_per_launch / (slowest * 1e-3) / 1e9
+            out["config"]["phases"] = {"kernel_ms_per_rank": per, "collective_ms": coll / probe, "finalize_ms": fin / probe,
+                                       "step_minus_slowest_kernel_ms": elapsed / args.steps * 1e3 - slowest}
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                               "traffic": None, "traffic_source": None,
+                               "kernel": "scan+filter+dense aggregation pipeline (the slowest shard's launches)", "kernel_ms": slowest,
+                               "bytes_per_launch": bytes_per_launch}
+            rc = check_parity(result.text, args.sf, out)
         print(json.dumps(out), flush=True)
         q.close()
         for t in shards:
@@ -685,7 +718,9 @@ def run_q3_sharded(args, dist, world: int, rank: int, local_rank: int, device) -
     rows_per = gather_per_rank(dist, world, float(n_rows), None if share else device)
     rc = 0
     if rank == 0:
-        want = _golden_text(f"q3_sf{sf:g}")
+        if args.dump_outputs:
+            dump_outputs(merged, args.dump_outputs)
+        want = _golden_text(f"q3_sf{sf:g}") if args.full else None
         out = {"metric": "TPC-H Q3 rows/s", "value": (nL + nO + nC) * args.steps / elapsed, "unit": "rows/s (lineitem + orders + customer rows of the whole job)",
                "n_gpus": 1 if share else world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
@@ -845,14 +880,17 @@ def main(argv=None) -> int:
         elapsed = float(t.item())
 
     _mark(f"timed region done: {elapsed / args.steps * 1e3:.4f} ms per step")
+    result = q.result() if rank == 0 else None        # the answer of the last timed step
+    if result is not None and args.dump_outputs:
+        dump_outputs(result, args.dump_outputs)
     # ---- where a multi-rank step's time goes: a second, UNTIMED loop of the same steps with an event pair around the merge ----
     phases = None
-    if multi and share:
+    if multi and share and args.full:
         phases = {"kernel_ms_per_rank": gather_per_rank(dist, world, avg_kernel_ms, None),
                   "note": "two rank processes share ONE GPU: their kernels run side by side or one after the other as the hardware queues "
                           "decide, and the exchange is a D2H copy, a gloo all-gather in host memory and an H2D copy - a rehearsal of the code "
                           "path, not a measurement of xGMI"}
-    if multi and not share:
+    if multi and not share and args.full:
         probe = max(1, min(args.steps, 20))
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(probe)]
         fin_ms = 0.0
@@ -883,7 +921,7 @@ def main(argv=None) -> int:
     # ---- the weak-scaling extra runs on every rank (its collectives need all of them), after the headline measurement ----
     weak = None
     weak_error = None
-    if not args.no_extras and not share:
+    if args.full and not args.no_extras and not share:
         try:
             # (--dist-path takes the multi-rank step here too, with a process group of one: partial execution, merge collective, finalize)
             weak = weak_scaling_extra(args, ctx, dist if (dist is not None and (world > 1 or args.dist_path)) else None, world, rank, device)
@@ -892,7 +930,7 @@ def main(argv=None) -> int:
 
     configs = None
     configs_error = None
-    if not args.no_extras and world == 1 and rank == 0:
+    if args.full and not args.no_extras and world == 1 and rank == 0:
         try:
             configs = config_extras(ctx, table, args.sf)
         except Exception as e:
@@ -900,16 +938,9 @@ def main(argv=None) -> int:
     _mark(f"extras done ({weak_error}, {configs_error})")
     rc = 0
     if rank == 0:
-        result = q.result()
         bytes_per_launch = tpch.Q1_BYTES_PER_ROW * n_rows
         traffic, traffic_source = committed_traffic(bytes_per_launch) if world == 1 else (None, None)
         achieved = bytes_per_launch / (avg_kernel_ms * 1e-3) / 1e9
-        # the read-only streaming roofline of THIS box, measured after the timed region with the access form the scan
-        # uses (16 B per lane, non-temporal, 2 workgroups per CU): SURVEY.md §8d asks for the fraction against it too
-        try:
-            measured = ctx.read_bandwidth(4 << 30, 5)
-        except Exception:
-            measured = None
         config = {"workload": f"TPC-H Q1 over lineitem SF{args.sf:g} ({n_total} rows, 7 columns, 38 B/row) "
                               f"resident in HBM, row-range sharded over {world} GPU(s)",
                   "rows": n_total, "rows_per_gpu": n_rows, "result_groups": result.n_rows, "path": "dist",
@@ -945,11 +976,18 @@ def main(argv=None) -> int:
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": "scan+filter+dense aggregation pipeline (rank 0's launches)", "kernel_ms": avg_kernel_ms,
-                         "bytes_per_launch": bytes_per_launch,
-                         "measured_read_roofline": measured,
-                         "frac_of_measured_read_roofline": (achieved / measured) if measured else None},
+                         "bytes_per_launch": bytes_per_launch},
         }
-        rc = check_parity(result.text, args.sf, out)
+        if args.full:
+            # the read-only streaming roofline of THIS box, measured after the timed region with the access form the scan
+            # uses (16 B per lane, non-temporal, 2 workgroups per CU): SURVEY.md §8d asks for the fraction against it too
+            try:
+                measured = ctx.read_bandwidth(4 << 30, 5)
+            except Exception:
+                measured = None
+            out["roofline"].update({"measured_read_roofline": measured,
+                                    "frac_of_measured_read_roofline": (achieved / measured) if measured else None})
+            rc = check_parity(result.text, args.sf, out)
         if configs is not None or configs_error is not None:
             out.setdefault("extras", {}).update(configs if configs is not None else {"configs_error": configs_error})
             bad = [k for k, v in (configs or {}).items() if v.get("parity_checked") is False]
@@ -960,7 +998,7 @@ def main(argv=None) -> int:
             out.setdefault("extras", {}).update({"weak_scaling": weak if weak is not None else {"error": weak_error},
                              "weak_scaling_note": "BASELINE config 5: one synthetic 4 x int64 shard per GPU (rows_per_gpu), a < tau at 10 %, "
                                                   "group by b, 2 sums + count; whole step incl. merge and rank 0's host tail; untimed for `value`"})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             want_sf = args.cpu_baseline_sf if args.cpu_baseline_sf is not None else args.sf
             try:
                 out["cpu_baseline"] = cpu_baseline(want_sf, table if want_sf == args.sf else None)

@@ -15,6 +15,15 @@ def golden_text(name: str) -> str:
         return f.read()
 
 
+def golden_columns(text: str) -> dict:
+    """a serialised numeric result relation as {column: [float, ...]} (CHAR(1) as the character's code): what
+    `bench.py --dump-outputs` writes for the same answer"""
+    lines = text.splitlines()
+    schema = [c.split(":") for c in lines[0][len("#schema "):].split("|")[:-1]]
+    rows = [l.split("|")[:-1] for l in lines[1:] if l]
+    return {name: [float(ord(r[i])) if typ == "CHAR(1)" else float(r[i]) for r in rows] for i, (name, typ) in enumerate(schema)}
+
+
 def golden_plan(name: str):
     p = INDEX[name]
     if p["plan"] == "synthetic":

@@ -105,3 +105,27 @@ def test_world_size_mismatch_is_refused():
     env.update({"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     pr = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--backend", "gloo", "--no-gpu"], env=env, capture_output=True, text=True, timeout=120)
     assert pr.returncode != 0 and "WORLD_SIZE=2" in pr.stderr
+
+
+def test_options_of_a_plain_run():
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True
+    pr = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert pr.returncode == 2 and "--steps must be at least 1" in pr.stderr
+
+
+def test_dump_outputs_writes_the_result_relation_column_by_column(tmp_path):
+    """what --dump-outputs writes for an answer: one float64 array per column, equal to the reference's recorded answer"""
+    import numpy as np
+    import bench
+    import goldens
+    from oracle import orc
+    res = orc.execute(goldens.golden_plan("q1_sf0.01"))
+    bench.dump_outputs(res, str(tmp_path / "out"))
+    want = goldens.golden_columns(goldens.golden_text("q1_sf0.01"))
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(f"{c}.npy" for c in want)
+    for name, values in want.items():
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and got.tolist() == values, name

@@ -25,7 +25,7 @@ def _bench(*args):
 
 
 def test_two_rank_processes_share_the_gpu_q1():
-    line = _bench("--gpus", "2", "--share-gpu", "--sf", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras")
+    line = _bench("--full", "--gpus", "2", "--share-gpu", "--sf", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras")
     c = line["config"]
     assert line["parity_checked"] is True and "ref_full_q1_sf1.tbl" in line["parity_source"]
     assert c["ranks"] == 2 and c["world_size"] == 2 and c["share_gpu"] is True and c["rccl_ranks_seen"] == 2 and c["self_launched"] is True
@@ -35,7 +35,7 @@ def test_two_rank_processes_share_the_gpu_q1():
 
 
 def test_two_rank_processes_share_the_gpu_q3_key_aligned():
-    line = _bench("--gpus", "2", "--share-gpu", "--workload", "q3", "--sf", "1", "--steps", "3", "--warmup", "1")
+    line = _bench("--full", "--gpus", "2", "--share-gpu", "--workload", "q3", "--sf", "1", "--steps", "3", "--warmup", "1")
     c = line["config"]
     assert line["parity_checked"] is True and "ref_full_q3_sf1.tbl" in line["parity_source"]
     assert c["ranks"] == 2 and c["share_gpu"] is True and len(c["lineitem_rows_per_rank"]) == 2

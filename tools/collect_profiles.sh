@@ -124,10 +124,10 @@ if hipcc -O3 --offload-arch=gfx950 -o /tmp/store_rate "$ROOT/tools/exp/store_rat
 step "does a shard's tail overlap the next shard's scan?  two 1.25 B-row shards on two contexts of this GPU (DESIGN round-5 item 6)"
 ( timeout -k 10 200 python3 "$ROOT/tools/exp/pair_overlap.py" 0.1 2>&1 | grep '^sel'; timeout -k 10 200 python3 "$ROOT/tools/exp/pair_overlap.py" 0.5 2>&1 | grep '^sel' ) > "$OUT/${R}_pair_overlap.txt"
 step "two rank PROCESSES on this one GPU (bench.py --gpus 2 --share-gpu): Q1 at SF10, and TPC-H Q3 with key-aligned shards"
-timeout -k 10 300 python3 "$ROOT/bench.py" --gpus 2 --share-gpu --no-cpu-baseline --no-extras --steps 20 2>/dev/null | grep '^{' > "$OUT/${R}_bench_share_gpu_2ranks.json"
-timeout -k 10 300 python3 "$ROOT/bench.py" --gpus 2 --share-gpu --workload q3 --sf 10 --steps 10 --warmup 2 2>/dev/null | grep '^{' > "$OUT/${R}_bench_share_gpu_q3_2ranks.json"
+timeout -k 10 300 python3 "$ROOT/bench.py" --full --gpus 2 --share-gpu --no-cpu-baseline --no-extras --steps 20 2>/dev/null | grep '^{' > "$OUT/${R}_bench_share_gpu_2ranks.json"
+timeout -k 10 300 python3 "$ROOT/bench.py" --full --gpus 2 --share-gpu --workload q3 --sf 10 --steps 10 --warmup 2 2>/dev/null | grep '^{' > "$OUT/${R}_bench_share_gpu_q3_2ranks.json"
 step "the same Q1 step through the C ABI's one-process path: 8 shards on this one GPU"
-timeout -k 10 200 python3 "$ROOT/bench.py" --path capi --capi-devices 0,0,0,0,0,0,0,0 --steps 20 2>/dev/null | grep '^{' > "$OUT/${R}_bench_capi_8shards_1gpu.json"
+timeout -k 10 200 python3 "$ROOT/bench.py" --full --path capi --capi-devices 0,0,0,0,0,0,0,0 --steps 20 2>/dev/null | grep '^{' > "$OUT/${R}_bench_capi_8shards_1gpu.json"
 ls -la "$OUT" | tail -n 20
 stamp_all
 exit 0
@@ -147,11 +147,11 @@ step "rocprofv3 durations against the engine's HIP events, same command, back to
 timeout -k 10 400 python3 "$ROOT/tools/q1_profile_gap.py" "$OUT/${R}_q1_rocprof_vs_events.txt" > /tmp/gap.log 2>&1 || echo "   q1_profile_gap failed: $(tail -n 2 /tmp/gap.log)"
 
 step "bench line (N = 1)"
-if timeout -k 10 400 python3 "$ROOT/bench.py" > "$OUT/${R}_bench_n1.log" 2>&1; then
+if timeout -k 10 400 python3 "$ROOT/bench.py" --full > "$OUT/${R}_bench_n1.log" 2>&1; then
     grep '^{' "$OUT/${R}_bench_n1.log" | tail -n 1 > "$OUT/${R}_bench_n1.json"
 else echo "   bench.py failed"; fi
 step "bench line, multi-rank step forced on one rank (RCCL world of one)"
-if timeout -k 10 300 python3 "$ROOT/bench.py" --dist-path --no-cpu-baseline > "$OUT/${R}_bench_distpath.log" 2>&1; then
+if timeout -k 10 300 python3 "$ROOT/bench.py" --full --dist-path --no-cpu-baseline > "$OUT/${R}_bench_distpath.log" 2>&1; then
     grep '^{' "$OUT/${R}_bench_distpath.log" | tail -n 1 > "$OUT/${R}_bench_distpath.json"
 fi
 
