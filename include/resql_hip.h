@@ -72,6 +72,8 @@ typedef struct rsq_config {
                                   * queries (0: 2 GiB, and 40 MiB of pinned host memory; < 0: nothing up front - slabs are taken when first needed) */
     int64_t  arena_keep_bytes;   /* free arena memory the context keeps between queries before slabs go back to the driver (0: 1/8 of the
                                   * device's memory) */
+    int64_t  nested_loops_max_pairs;/* RSQ_ENGINE_NESTED_LOOPS: most (outer rows x inner rows) one nested-loops join may pair; an execution
+                                  * beyond it is RSQ_ERR_UNSUPPORTED before any pair is formed (0: 2^36; < 0: RSQ_ERR_INVALID) */
 } rsq_config;
 
 /* A ReSQL host compiles a statement, executes it ONCE and deletes the plan (reference src/execute.h:213-247).  Two things make that one
@@ -82,8 +84,12 @@ typedef struct rsq_config {
  *   - the plan memo: what an execution learns about a plan over a table version - build cardinalities, whether build keys are unique
  *     (rank dictionary or hash form), group counts, region layouts of a staged aggregation, result sizes, which kernel form ran - is
  *     kept by (kernel texts, table ids + versions) and a later query of the same shape starts with it; everything in it is re-checked by
- *     the execution (a stale entry costs a repeated execution, never a wrong answer).  RSQ_ENGINE_NO_PLAN_MEMO starts every query cold. */
-enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u };
+ *     the execution (a stale entry costs a repeated execution, never a wrong answer).  RSQ_ENGINE_NO_PLAN_MEMO starts every query cold.
+ * RSQ_ENGINE_NESTED_LOOPS (off by default) lets the context plan and execute nested-loops joins (planner.h:458-469: FROM lists whose
+ * tables are not all linked by equalities; RSQ_OP_NESTEDLOOPSJOIN in a plan description).  Such a join costs outer x inner pairs, so
+ * a host enables it explicitly and bounds it with rsq_config.nested_loops_max_pairs.  Without the flag those plans are refused
+ * (RSQ_ERR_UNSUPPORTED) as before. */
+enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u };
 
 /* Semantics switches.  The default (0) computes what the reference's SOURCE specifies; a bit selects what its asmjit back end
  * actually executes where the two differ, for a drop-in host that must return the JIT's own answers:
@@ -295,7 +301,8 @@ int   rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_
  * `tables` is the database: every table a FROM clause may name (rsq_table carries name, schema and
  * row count — what Database::relations holds, src/dbdata.h).  Scan operators of the plan index into it,
  * so the same array goes to rsq_query_compile.  Errors: RSQ_ERR_INVALID "Syntax error." (execute.h:520-523),
- * "Table x does not exist." (planner.h:437-439); RSQ_ERR_UNSUPPORTED for plans that need a nested-loops join. */
+ * "Table x does not exist." (planner.h:437-439); RSQ_ERR_UNSUPPORTED for plans that need a nested-loops join, unless the context
+ * has RSQ_ENGINE_NESTED_LOOPS (the pieces are then folded left-deep into RSQ_OP_NESTEDLOOPSJOIN nodes, as planner.h:458-469 does). */
 typedef struct rsq_sql_plan rsq_sql_plan;
 int  rsq_sql_plan_select(rsq_ctx* ctx, const char* sql, rsq_table* const* tables, int32_t n_tables, rsq_sql_plan** out);
 const rsq_plan_desc* rsq_sql_plan_desc(const rsq_sql_plan* plan);

@@ -94,7 +94,7 @@ enum rsq_op_tag {
     RSQ_OP_PROJECTION,      /* operators/projection.h:5-74   */
     RSQ_OP_SELECTION,       /* operators/selection.h:6-72    */
     RSQ_OP_MATERIALIZE,     /* operators/materialize.h:9-262 */
-    RSQ_OP_NESTEDLOOPSJOIN, /* out of scope      */
+    RSQ_OP_NESTEDLOOPSJOIN, /* operators/nestedloopsjoin.h   */
     RSQ_OP_HASHJOIN,        /* operators/hashjoin.h:23-256   */
     RSQ_OP_AGGREGATION,     /* operators/aggregation.h:17-345*/
     RSQ_OP_ORDERBY          /* operators/orderby.h:14-141    */
@@ -113,6 +113,13 @@ typedef struct rsq_op {
     int32_t exprs2[RSQ_MAX_OP_EXPRS];
     int32_t single_match;            /* HASHJOIN: HashJoinOp::_singleMatch (hashjoin.h:40, planner.h:353-358) */
 } rsq_op;
+/* NESTEDLOOPSJOIN (operators/nestedloopsjoin.h; executed only by a context with RSQ_ENGINE_NESTED_LOOPS, include/resql_hip.h):
+ *   child[0] = the left child, the INNER side: it is materialised first, in its own order;
+ *   child[1] = the right child, the OUTER side: it streams, and every row of it meets every inner row in inner order, so the pairs
+ *              come outer-major, inner-minor; the output schema is the left child's attributes, then the right child's;
+ *   n_exprs  = 0 or 1: exprs[0] is the optional join condition (NestedLoopsJoinOp::_condition).
+ * A MATERIALIZE directly below the node is the reference's own wrapper (NestedLoopsJoinOp wraps both children in MaterializeOp):
+ * it is not a second materialisation. */
 
 typedef struct rsq_plan_desc {
     const rsq_expr* exprs;

@@ -136,6 +136,13 @@ public:
             d.tag = RSQ_OP_ORDERBY; d.child[0] = op(ob->_child->_child);
             list(ob->_orderExpressions, d.n_exprs, d.exprs);
             if (hasLimit && ob->_hasLimitClause) { *hasLimit = true; *limit = (int64_t)ob->_limit; }
+        } else if (auto* n = dynamic_cast<NestedLoopsJoinOp*>(o)) {
+            // NestedLoopsJoinOp wraps both children in a MaterializeOp (nestedloopsjoin.h); the engine materialises the inner side itself,
+            // so the wrappers are skipped.  Executed by a context with RSQ_ENGINE_NESTED_LOOPS only (JitContextHip's engine_flags).
+            d.tag = RSQ_OP_NESTEDLOOPSJOIN;
+            d.child[0] = op(static_cast<MaterializeOp*>(n->_lChild)->_child);
+            d.child[1] = op(static_cast<MaterializeOp*>(n->_rChild)->_child);
+            if (n->_condition) { d.n_exprs = 1; d.exprs[0] = expr(n->_condition); }
         } else if (auto* m = dynamic_cast<MaterializeOp*>(o)) {
             d.tag = RSQ_OP_MATERIALIZE; d.child[0] = op(m->_child);
             if (hasLimit && m->_hasLimitClause) { *hasLimit = true; *limit = (int64_t)m->_limit; }
@@ -154,11 +161,13 @@ private:
 class JitContextHip {
 public:
     // compat: rsq_compat bits.  The drop-in's default is RSQ_COMPAT_JIT_INT16_CAST: the answers ReSQL's asmjit JIT gives TODAY, bit for
-    // bit; 0 computes what the reference's source specifies (what ReSQL answers once its movsx is fixed)
-    explicit JitContextHip(const JitConfig& cfg, int device = 0, uint32_t compat = RSQ_COMPAT_JIT_INT16_CAST) {
+    // bit; 0 computes what the reference's source specifies (what ReSQL answers once its movsx is fixed).
+    // engineFlags: rsq_engine_flags bits (0: the defaults; RSQ_ENGINE_NESTED_LOOPS lets plans with a NestedLoopsJoinOp run on the GPU)
+    explicit JitContextHip(const JitConfig& cfg, int device = 0, uint32_t compat = RSQ_COMPAT_JIT_INT16_CAST, uint32_t engineFlags = 0) {
         rsq_config c{};
         c.struct_size = sizeof c;
         c.compat_flags = compat;
+        c.engine_flags = engineFlags;
         c.print_assembly = cfg.printAssembly; c.print_flounder = cfg.printFlounder; c.print_performance = cfg.printPerformance;
         c.num_threads = cfg.numThreads; c.emit_machine_code = cfg.emitMachineCode; c.optimize = cfg.optimizeFlounder;
         c.device = device;

@@ -71,7 +71,9 @@ rsq_config readConfig(const rsq_config* cfg) {
     c.struct_size = (uint32_t)sizeof(rsq_config);
     if (c.emission_order != RSQ_EMIT_REFERENCE && c.emission_order != RSQ_EMIT_ANY) failInvalid("rsq_config.emission_order must be RSQ_EMIT_REFERENCE (0) or RSQ_EMIT_ANY (1)");
     if (c.compat_flags & ~(uint32_t)RSQ_COMPAT_JIT_INT16_CAST) failInvalid("rsq_config.compat_flags has bits this library does not know");
-    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO)) failInvalid("rsq_config.engine_flags has bits this library does not know");
+    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO | RSQ_ENGINE_NESTED_LOOPS)) failInvalid("rsq_config.engine_flags has bits this library does not know");
+    if (c.nested_loops_max_pairs < 0) failInvalid("rsq_config.nested_loops_max_pairs is negative (0: the default of 2^36 pairs)");
+    if (c.nested_loops_max_pairs == 0) c.nested_loops_max_pairs = (int64_t)1 << 36;
     return c;
 }
 }  // namespace rsq
@@ -472,7 +474,7 @@ int rsq_sql_plan_select(rsq_ctx* ctx, const char* sqlText, rsq_table* const* tab
         for (int i = 0; i < n_tables; i++) { if (!tables[i]) failInvalid("null table"); db.push_back(T(tables[i])); }
         rsq::sql::parse(sqlText, p->pool, p->st);
         if (p->st.kind != rsq::sql::Statement::SELECT) failInvalid("not a select statement");
-        rsq::sql::planSelect(p->st, p->pool, db, p->plan);
+        rsq::sql::planSelect(p->st, p->pool, db, p->plan, (C(ctx)->cfg.engine_flags & RSQ_ENGINE_NESTED_LOOPS) != 0);
         p->db = db;
         *out = p.release();
     });

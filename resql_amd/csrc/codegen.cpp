@@ -56,8 +56,71 @@ void Walker::produce(OpNode* o, std::vector<std::string> request) {
         case RSQ_OP_MATERIALIZE: case RSQ_OP_ORDERBY:
             produce(o->child[0], request);
             break;
+        case RSQ_OP_NESTEDLOOPSJOIN: {              // nestedloopsjoin.h produceFlounder: the inner side is a query of its own (engine.cpp)
+            std::vector<std::string> all = request;
+            for (Expr* e : o->exprs) requiredAttributes(e, all);
+            requestOf[o] = all;
+            produce(o->child[1], all);              // the outer side's pipeline, with the pair loop in it
+            break;
+        }
         default: failUnsupported("operator not supported by the GPU engine");
     }
+}
+
+// ---- nested-loops join (nestedloopsjoin.h consumeFlounder) ----------------------------------------------------------------
+// The outer row meets every row of the materialised inner side, in inner order: the pair loop binds the inner row's attributes and tests
+// the join condition, then the operators above consume the pair.  A lane's pairs come outer-row-major and inner-minor, which is the
+// order the materialisation's count / write passes keep - the reference's order.  All lanes stand at the same inner row at the same
+// moment, so the inner columns are read with wave-uniform scalar loads (rsq::nlj_ld).  The pair's ordinal for the aggregation's
+// first-row tracker is outer row x inner rows + inner position (the order in which the reference meets the pairs).
+void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
+    NljState& n = q.nljs[(size_t)o->nlj];
+    Query& in = *n.inner;
+    if (!in.matOp || in.agg) failUnsupported("the inner side of a nested-loops join must be a materialisation on the device");
+    if (n.outerSrc) failUnsupported("a nested-loops join inside more than one pipeline");
+    n.outerSrc = pipe.src;
+    n.pipeline = (int)q.pipelines.size();      // (finishPipeline appends this pipeline next)
+    n.innerSchema.clear(); n.innerCol.clear();
+    const std::vector<std::string>& req = requestOf[o];
+    for (size_t c = 0; c < in.matSchema.size(); c++) {
+        if (!q.requestAll && !has(req, in.matSchema[c].name)) continue;
+        n.innerSchema.push_back(in.matSchema[c]); n.innerCol.push_back((int)c);
+    }
+    const std::string N = "nlj" + std::to_string(o->nlj);
+    Schema out;
+    for (auto& a : n.innerSchema) out.push_back(a);
+    for (auto& a : from->schema) out.push_back(a);
+    o->schema = out;
+    addArg(N + "_n", "i64", 0);
+    openScope("{");
+    line("const i64 " + N + "_orow = row;");
+    openScope("for (i64 " + N + "_j = 0; " + N + "_j < a." + N + "_n; " + N + "_j++) {");
+    line("const i64 row = " + N + "_orow * a." + N + "_n + " + N + "_j; (void)row;");
+    for (size_t k = 0; k < n.innerSchema.size(); k++) {
+        const Attr& at = n.innerSchema[k];
+        const std::string cn = N + "_c" + std::to_string(k), var = N + "_v" + std::to_string(k);
+        if (at.type.isString() && !(at.type.tag == RSQ_CHAR && at.type.len == 1)) {
+            addArg(cn, "const char*", 0);
+            line("const rsq::Str " + var + " = rsq::str(a." + cn + " + " + N + "_j * " + std::to_string(at.type.len) + ", " + std::to_string(at.type.len) + ");");
+        } else {
+            const std::string ct = ExprGen::ctype(at.type);
+            addArg(cn, "const " + ct + "*", 0);
+            line("const " + ct + " " + var + " = rsq::nlj_ld(a." + cn + ", " + N + "_j);");
+        }
+        eg.symbols[at.name] = Sym{var, at.type};
+        symbolOrigin[at.name] = -2;
+    }
+    multiMatchAbove = true;
+    pipe.gridPerCU = 8;                // the pair loop is arithmetic, not a stream: latency wants waves
+    explainSteps.push_back("nested-loops join: every row meets the " + std::to_string(n.innerSchema.size()) + " bound column(s) of the inner side");
+    if (!o->exprs.empty()) {
+        q.pool.addId(o->exprs[0]);
+        openScope("if (" + eg.emit(o->exprs[0]) + ") {");
+        consume(o->parent, o);
+        closeScope();
+    } else consume(o->parent, o);
+    closeScope();
+    closeScope();
 }
 
 Schema Walker::prune(const Schema& s, const std::vector<std::string>& req) {
@@ -289,7 +352,13 @@ void Walker::consume(OpNode* o, OpNode* from) {
             if (joinPhase[o] == 1) consumeBuild(o, from); else consumeProbe(o, from);
             break;
         case RSQ_OP_AGGREGATION: consumeAggregation(o, from); break;
-        case RSQ_OP_MATERIALIZE: consumeMaterialize(o, from); break;
+        case RSQ_OP_MATERIALIZE:
+            if (o->parent && o->parent->tag == RSQ_OP_NESTEDLOOPSJOIN) {       // the reference's wrapper of the outer side: streams through
+                o->schema = from->schema;
+                consume(o->parent, o);
+            } else consumeMaterialize(o, from);
+            break;
+        case RSQ_OP_NESTEDLOOPSJOIN: consumeNestedLoops(o, from); break;
         default: failUnsupported("operator not supported by the GPU engine");
     }
 }

@@ -922,7 +922,8 @@ void Walker::emitDenseAggregation(OpNode* o) {
         while ((int64_t)gpp * 2 * W * 8 <= 128 * 1024 && gpp * 2 <= (1 << 20)) gpp *= 2;
         const int64_t P = (D + gpp - 1) / gpp;
         int shift = 0; while ((1 << shift) < gpp) shift++;
-        const bool part = P >= 2 && P <= 4096 && envInt("RSQ_PARTITION", 1, 0, 2) != 0;
+        // (not behind a nested-loops join: a record carries row - row0 in 40 bits, and a pair's ordinal is outer row x inner rows + j)
+        const bool part = P >= 2 && P <= 4096 && envInt("RSQ_PARTITION", 1, 0, 2) != 0 && !underNestedLoops();
         if (part) {
             pipe.partitioned = true; pipe.partCount = (int)P; pipe.partGroups = gpp;
             line("#if RSQ_AGG_VARIANT == 1");

@@ -142,8 +142,10 @@ struct ExprGen {
                 failType(std::string(exprTagNames[e->tag]) + " code generation not implemented for datatype");
         };
         auto orderedOk = [&]() {
+            // the reference's own words (ExpressionsJitFlounder.h: emitLessThan says LESS_THAN, emitGreaterThan says ADD)
+            const char* name = e->tag == RSQ_E_LT ? "LESS_THAN" : e->tag == RSQ_E_GT ? "ADD" : exprTagNames[e->tag];
             if (op.tag != RSQ_DECIMAL && op.tag != RSQ_DATE && op.tag != RSQ_BIGINT)
-                failType(std::string(exprTagNames[e->tag]) + " code generation not implemented for datatype");
+                failType(std::string(name) + " code generation not implemented for datatype");
         };
         // string = constant: word-wise against the constant's bytes (rsq_device.h ld_bytes) instead of the byte loop
         auto equalsConstant = [&](bool charSemantics) -> std::string {
@@ -274,6 +276,7 @@ struct Walker {
     std::map<std::string, int> symbolOrigin;   // symbol -> hash table id it was read from (or -1: scan column)
     std::map<std::string, int> symbolWord;     // symbol -> word index in that table
     bool multiMatchAbove = false;
+    bool underNestedLoops() const { return !q.nljs.empty(); }      // the plan pairs rows in a nested-loops join
     // wave-level compaction (see compactThen)
     bool selective = false, compacted = false;
     // the selection directly above the scan: its text over the row's column variables, the columns it reads and the fraction of
@@ -400,6 +403,7 @@ struct Walker {
     void emitJoinEntryAggregation(OpNode* o);
 
     void consumeMaterialize(OpNode* o, OpNode* from);
+    void consumeNestedLoops(OpNode* o, OpNode* from);
 
     std::string postTileFor(const std::string& tile);
     int stagedRounds(int col) { return (8 * strPrefetchWidth[col] + 63) / 64; }

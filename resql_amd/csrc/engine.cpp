@@ -4,6 +4,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <sstream>
 
 #include "engine_internal.h"
@@ -38,7 +39,11 @@ void buildOps(Query& q, const rsq_plan_desc& p) {
             case RSQ_OP_HASHJOIN: o->nChildren = 2; if (d.n_exprs < 1) failInvalid("hash join needs an equality"); break;
             case RSQ_OP_SELECTION: if (d.n_exprs != 1) failInvalid("selection needs one condition"); o->nChildren = 1; break;
             case RSQ_OP_PROJECTION: case RSQ_OP_AGGREGATION: case RSQ_OP_MATERIALIZE: case RSQ_OP_ORDERBY: o->nChildren = 1; break;
-            case RSQ_OP_NESTEDLOOPSJOIN: failUnsupported("NestedLoopsJoin is outside the hot path (SURVEY §2)");
+            case RSQ_OP_NESTEDLOOPSJOIN:
+                if (!(q.ctx.cfg.engine_flags & RSQ_ENGINE_NESTED_LOOPS)) failUnsupported("NestedLoopsJoin is outside the hot path (SURVEY §2)");
+                if (d.n_exprs > 1) failInvalid("nested-loops join takes at most one condition");
+                o->nChildren = 2; o->nlj = (int)q.nljs.size(); q.nljs.emplace_back(); q.nljs.back().op = o;
+                break;
             default: failInvalid("unknown operator tag");
         }
         for (int k = 0; k < o->nChildren; k++) {
@@ -70,7 +75,7 @@ void defineAndDerive(Query& q, OpNode* o) {
     auto all = [&](std::vector<Expr*>& v) { for (Expr* e : v) q.pool.derive(e); };
     switch (o->tag) {
         case RSQ_OP_SCAN: case RSQ_OP_MATERIALIZE: break;
-        case RSQ_OP_SELECTION: case RSQ_OP_PROJECTION: case RSQ_OP_HASHJOIN: all(o->exprs); break;
+        case RSQ_OP_SELECTION: case RSQ_OP_PROJECTION: case RSQ_OP_HASHJOIN: case RSQ_OP_NESTEDLOOPSJOIN: all(o->exprs); break;
         case RSQ_OP_AGGREGATION:
             for (Expr* e : o->exprs) {
                 if (e->tag == RSQ_E_AVG) {
@@ -107,12 +112,17 @@ uint64_t opSize(OpNode* o, bool local) {
             return opSize(o->child[0], local) / (uint64_t)red;
         }
         case RSQ_OP_MATERIALIZE: { uint64_t s = opSize(o->child[0], local); if (o->hasLimit && (uint64_t)o->limit < s) s = (uint64_t)o->limit; return s; }
+        case RSQ_OP_NESTEDLOOPSJOIN: {            // nestedloopsjoin.h getSize
+            const uint64_t l = opSize(o->child[0], local), r = opSize(o->child[1], local);
+            return l + r <= 10000 ? l * r : (l + r) * 2;
+        }
         default: return 0;
     }
 }
 
 Query::~Query() {
     if (bgCompiler.joinable()) bgCompiler.join();
+    for (NljState& n : nljs) for (void* p : n.dCols) ctx.free(p);
     destroyTailState(tailState);
     if (dtArena.dev || dtArena.pinned) {
         // the arenas go back to the context for the next query, unless it already holds a pair
@@ -390,6 +400,36 @@ static void rememberPlan(Query& q) {
     }
 }
 
+// The inner side of a nested-loops join: the left subtree under a MATERIALIZE (the reference's own wrapper where the plan has it), every
+// attribute, no limit - a plan description of its own, compiled as a query of its own.
+static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
+    int left = -1;
+    for (int i = 0; i < plan.n_ops; i++) if (q.ops[(size_t)i].get() == n.op) left = plan.ops[i].child[0];
+    if (left < 0) failInvalid("nested-loops join without a left child");
+    std::vector<rsq_op> ops;
+    std::map<int, int> remap;
+    std::function<int(int)> copy = [&](int i) -> int {
+        auto it = remap.find(i);
+        if (it != remap.end()) return it->second;
+        rsq_op d = plan.ops[i];
+        for (int k = 0; k < 2; k++) if (d.child[k] >= 0) d.child[k] = copy(d.child[k]);
+        ops.push_back(d);
+        return remap[i] = (int)ops.size() - 1;
+    };
+    int root = copy(left);
+    if (ops[(size_t)root].tag != RSQ_OP_MATERIALIZE) {
+        rsq_op m;
+        memset(&m, 0, sizeof m);
+        m.tag = RSQ_OP_MATERIALIZE; m.child[0] = root; m.child[1] = -1; m.table = -1;
+        ops.push_back(m);
+        root = (int)ops.size() - 1;
+    }
+    rsq_plan_desc sub = plan;
+    sub.ops = ops.data(); sub.n_ops = (int32_t)ops.size(); sub.root = root;
+    sub.request_all = 1; sub.has_limit = 0; sub.limit = 0;
+    n.inner.reset(compileQuery(q.ctx, sub, tables, nTables));
+}
+
 Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
     double t0 = nowMs();
     std::unique_ptr<Query> q(new Query(ctx));
@@ -405,6 +445,18 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     q->exprs = q->pool.build(plan);
     buildOps(*q, plan);
     defineAndDerive(*q, q->root);
+    // (a join in the left subtree of another one belongs to that one's inner query, which compiles it itself)
+    for (NljState& n : q->nljs) {
+        bool inInner = false;
+        for (OpNode* c = n.op; c->parent; c = c->parent)
+            if (c->parent->tag == RSQ_OP_NESTEDLOOPSJOIN && c->parent->child[0] == c) inInner = true;
+        if (!inInner) {
+            compileNestedLoopsInner(*q, n, plan, tables, nTables);
+            // The reference numbers expressions with one counter in produce order, and NestedLoopsJoinOp produces its left child first:
+            // the names of this query's expressions (`exprN` of an aggregate's column) come after the inner side's
+            q->pool.exprIdGen += n.inner->pool.exprIdGen - 1;        // (both counters start at 1)
+        }
+    }
     const double tBuilt0 = nowMs();
     buildPipelines(*q);
     const double tBuilt = nowMs();
@@ -610,6 +662,44 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
     rememberPlan(q);
 }
 
+// The inner sides of the nested-loops joins: each runs as its own query, and its result columns (struct of arrays, strings by value) are
+// copied into device columns this query owns.  Then the pair budget: outer rows x inner rows above rsq_config.nested_loops_max_pairs
+// ends the execution before the outer pipeline starts.
+static void prepareNestedLoops(Query& q) {
+    Context& ctx = q.ctx;
+    for (NljState& n : q.nljs) {
+        if (!n.inner || !n.outerSrc) continue;           // (a join of an inner side: that side's query prepares it)
+        Query& in = *n.inner;
+        const int64_t outer = n.outerSrc->nRows;
+        n.nInner = 0;
+        if (outer > 0) {                                 // (an empty outer side needs no inner rows)
+            executeQuery(in, false);
+            n.nInner = in.matRows;
+            q.report.num_kernels += in.report.num_kernels;
+            q.report.bytes_read += in.report.bytes_read;
+        }
+        const int64_t budget = ctx.cfg.nested_loops_max_pairs;
+        const long double pairs = (long double)outer * (long double)n.nInner;
+        if (pairs > (long double)budget)
+            failUnsupported("nested-loops join: " + std::to_string((long long)outer) + " outer rows x " + std::to_string((long long)n.nInner) +
+                            " inner rows is more than rsq_config.nested_loops_max_pairs (" + std::to_string((long long)budget) + " pairs)");
+        // a materialisation counts tuples per lane and per 128-row tile in 32 bits: 128 outer rows x the inner rows must stay below 2^32
+        if (n.pipeline >= 0 && q.pipelines[(size_t)n.pipeline].sink == SinkKind::MATERIALIZE && 128.0L * (long double)n.nInner >= 4294967296.0L)
+            failUnsupported("nested-loops join: " + std::to_string((long long)n.nInner) + " inner rows - a 128-row tile of the outer side could emit "
+                            "2^32 or more tuples, beyond the materialisation's 32-bit tile counts");
+        if (n.nInner > n.innerCapacity) {
+            for (void* p : n.dCols) ctx.free(p);
+            n.dCols.clear();
+            n.innerCapacity = std::max<int64_t>(n.nInner, 64);
+            for (auto& a : n.innerSchema) n.dCols.push_back(ctx.alloc((size_t)n.innerCapacity * (size_t)columnWidth(a.type)));
+        }
+        for (size_t k = 0; k < n.innerSchema.size() && n.nInner > 0; k++) {
+            const void* src = in.dMatCols[(size_t)n.innerCol[k]];
+            RSQ_HIP(hipMemcpyAsync(n.dCols[k], src, (size_t)n.nInner * (size_t)columnWidth(n.innerSchema[k].type), hipMemcpyDefault, ctx.stream));
+        }
+    }
+}
+
 static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     Context& ctx = q.ctx;
     if (ctx.device < 0) throw Error(RSQ_ERR_DEVICE, "this context has no device (compile-only)");
@@ -624,6 +714,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
+    if (!q.nljs.empty()) prepareNestedLoops(q);      // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
         // the full kernels are in the cache now: the quick tier's are replaced (same arguments, same tables - nothing else changes).
         // (A full tier that failed to compile leaves the query on the quick one.)

@@ -33,6 +33,7 @@ struct OpNode {
     std::vector<Expr*> splitAgg;     // aggregation.h:167-179
     Schema schema;                   // RelOperator::_schema
     int hashTable = -1;              // HASHJOIN: index into Query::hashTables
+    int nlj = -1;                    // NESTEDLOOPSJOIN: index into Query::nljs
 };
 
 // ---- device hash table (join build side; optionally carries aggregates "at the entry") ----------
@@ -263,6 +264,21 @@ struct Pipeline {
 struct TailState;
 void destroyTailState(TailState* t);
 
+// A nested-loops join (operators/nestedloopsjoin.h).  Its left child, the inner side, is a query of its own (compiled with the statement:
+// MATERIALIZE over the left subtree, every attribute); its result columns are copied into query-owned device columns before the pipeline
+// of the right child, the outer side, runs.  That pipeline pairs each of its rows with every inner row in inner order (codegen.cpp).
+struct NljState {
+    OpNode* op = nullptr;
+    std::unique_ptr<Query> inner;
+    Schema innerSchema;              // the inner attributes the pair loop binds (all of them for `select *`)
+    std::vector<int> innerCol;       // ... their column in inner->resultSchema
+    const Table* outerSrc = nullptr; // the table the outer pipeline scans (the pair budget counts its rows)
+    int pipeline = -1;               // index of that pipeline in Query::pipelines
+    std::vector<void*> dCols;        // device columns [innerCapacity] per bound attribute
+    int64_t innerCapacity = 0;
+    int64_t nInner = 0;              // rows of the inner side in this execution
+};
+
 struct Query {
     Context& ctx;
     ExprPool pool;
@@ -276,6 +292,7 @@ struct Query {
     // device side
     std::vector<Pipeline> pipelines;
     std::vector<std::unique_ptr<HashTable>> hashTables;
+    std::vector<NljState> nljs;            // nested-loops joins (OpNode::nlj)
     OpNode* agg = nullptr;                 // the aggregation whose input pipeline runs on the device (may be null)
     AggMode aggMode = AggMode::NONE;
     std::vector<DenseKey> denseKeys;

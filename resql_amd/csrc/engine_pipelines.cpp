@@ -44,6 +44,13 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
         size_t k = (size_t)atoi(a.name.c_str() + 1);
         return k < q.dMatCols.size() ? (uint64_t)(uintptr_t)q.dMatCols[k] : 0;
     }
+    if (a.name.compare(0, 3, "nlj") == 0) {         // nested-loops join: the inner side's row count and bound columns (engine.cpp)
+        const size_t us = a.name.find('_');
+        const NljState& n = q.nljs[(size_t)atoi(a.name.c_str() + 3)];
+        if (a.name.compare(us, 2, "_n") == 0) return (uint64_t)n.nInner;
+        const size_t k = (size_t)atoi(a.name.c_str() + us + 2);
+        return k < n.dCols.size() ? (uint64_t)(uintptr_t)n.dCols[k] : 0;
+    }
     if (a.name.compare(0, 2, "ht") == 0) {
         size_t us = a.name.find('_');
         int id = atoi(a.name.substr(2, us - 2).c_str());

@@ -298,6 +298,12 @@ RSQ_DEV bool top_byte_is_space(i64 w) {
 }
 RSQ_DEV bool ends_with_space(const Str& s) { const int n = str_len_exact(s); return n > 0 && s.p[n - 1] == ' '; }
 RSQ_DEV i64 str_addr(const Str& s) { return (i64)(u64)reinterpret_cast<unsigned long long>(s.p); }
+// Row j of an inner column of a nested-loops join.  Every lane of the wave asks for the same row at the same moment (the pair loop's
+// counter is wave-uniform), and the columns do not change while the kernel runs: read through the constant address space, so the
+// load is a scalar one (s_load) into an SGPR that all lanes share, not one vector load per lane and pair.
+template <typename T> RSQ_DEV T nlj_ld(const T* col, i64 j) {
+    return reinterpret_cast<const __attribute__((address_space(4))) T*>(reinterpret_cast<unsigned long long>(col))[j];
+}
 RSQ_DEV Str str_from_addr(i64 w, int cap) { return str(reinterpret_cast<const char*>((unsigned long long)(u64)w), cap); }
 
 // LIKE ('%' any run, '_' any one character) with the reference's results (stringLikeCheck, src/qlib/scalar.h:49-118;

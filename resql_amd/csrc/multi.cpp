@@ -317,6 +317,8 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
     if (!m || !plan || !out || n_tables < 0 || (n_tables > 0 && !tables)) return RSQ_ERR_INVALID;
     *out = nullptr;
     return guardedM(m, [&] {
+        for (int i = 0; i < plan->n_ops; i++)
+            if (plan->ops && plan->ops[i].tag == RSQ_OP_NESTEDLOOPSJOIN) failUnsupported("a nested-loops join is not executed across GPUs (rsq_multi_*): run it on one context");
         const int n = (int)m->ctxs.size();
         std::unique_ptr<rsq_multi_query> mq(new rsq_multi_query());
         mq->m = m;

@@ -509,6 +509,7 @@ void collectAttributes(const Expr* e, std::vector<std::string>& out) {     // pl
 // ---- plan under construction ----
 struct POp {
     int tag = RSQ_OP_UNDEFINED;
+    int seq = 0;                       // creation order: what the reference's std::set of operator addresses iterates by (see planSelect)
     POp* child[2] = {nullptr, nullptr};
     int table = -1;
     ExprVec exprs, exprs2;
@@ -529,6 +530,7 @@ struct Planner {
         ops.emplace_back(new POp());
         POp* o = ops.back().get();
         o->tag = tag; o->child[0] = c0; o->child[1] = c1;
+        o->seq = (int)ops.size() - 1;
         return o;
     }
     Expr* and_(Expr* l, Expr* r) { l->next = r; Expr* e = pool.make(RSQ_E_AND, BINARY, "and"); e->child = l; return e; }
@@ -712,7 +714,7 @@ struct PlanBuilder {
 };
 
 // planner.h:409-497 buildQuery
-void planSelect(Statement& st, ExprPool& pool, const std::vector<Table*>& db, PlanDesc& out) {
+void planSelect(Statement& st, ExprPool& pool, const std::vector<Table*>& db, PlanDesc& out, bool nestedLoops) {
     if (st.kind != Statement::SELECT) failInvalid("not a select statement");
     ExprVec select = listToVector(st.selectExpr);
     ExprVec from = listToVector(st.fromExpr);
@@ -762,10 +764,23 @@ void planSelect(Statement& st, ExprPool& pool, const std::vector<Table*>& db, Pl
     }
     where = pl.pushDownSelection(where);
     where = pl.addEqualityHashJoins(where);
-    // planner.h:458-469 folds the remaining pieces into nested-loops joins in the order of a std::set of operator
-    // ADDRESSES; the engine has no nested-loops join, so more than one piece is refused either way
+    // planner.h:458-469 folds the remaining pieces left-deep into nested-loops joins in the order of a std::set of operator
+    // ADDRESSES.  Operators of a fresh statement are allocated one after the other, so that order is the order in which each
+    // piece's root (scan, pushed-down selection or hash join) was created - not the piece's position in the list.  Each
+    // NestedLoopsJoinOp wraps both of its children in a MaterializeOp (nestedloopsjoin.h); the description keeps those wrappers.
+    // Without RSQ_ENGINE_NESTED_LOOPS on the context such a plan is refused.
     POp* plan = nullptr;
-    if (pl.pieces.size() > 1) failUnsupported("the plan needs a nested-loops join (tables without an equality join condition)");
+    if (pl.pieces.size() > 1) {
+        if (!nestedLoops) failUnsupported("the plan needs a nested-loops join (tables without an equality join condition)");
+        std::vector<POp*> order = pl.pieces;
+        std::sort(order.begin(), order.end(), [](const POp* a, const POp* b) { return a->seq < b->seq; });
+        plan = order[0];
+        for (size_t i = 1; i < order.size(); i++) {
+            POp* inner = pl.op(RSQ_OP_MATERIALIZE, plan);
+            POp* outer = pl.op(RSQ_OP_MATERIALIZE, order[i]);
+            plan = pl.op(RSQ_OP_NESTEDLOOPSJOIN, inner, outer);
+        }
+    }
     if (pl.pieces.size() == 1) plan = pl.pieces[0];
     if (!plan) failUnsupported("select without a from-clause");
     if (!where.empty()) {
@@ -818,6 +833,7 @@ static void dumpOp(const rsq_plan_desc& d, const std::vector<Expr*>& ex, const s
         case RSQ_OP_AGGREGATION: out += "AGGREGATION"; dumpVec(ex, o.exprs, o.n_exprs, out); dumpVec(ex, o.exprs2, o.n_exprs2, out); break;
         case RSQ_OP_MATERIALIZE: out += "MATERIALIZE"; break;
         case RSQ_OP_ORDERBY: out += "ORDERBY"; dumpVec(ex, o.exprs, o.n_exprs, out); break;
+        case RSQ_OP_NESTEDLOOPSJOIN: out += "NESTEDLOOPSJOIN"; if (o.n_exprs > 0) dumpVec(ex, o.exprs, o.n_exprs, out); nChildren = 2; break;
         default: out += "UNDEFINED"; nChildren = 0; break;
     }
     out += " {";

@@ -45,8 +45,9 @@ struct PlanDesc {
     rsq_plan_desc desc;
 };
 
-// buildQuery (planner.h:409-497) over the tables of `db` (scan operators index into it)
-void planSelect(Statement& st, ExprPool& pool, const std::vector<Table*>& db, PlanDesc& out);
+// buildQuery (planner.h:409-497) over the tables of `db` (scan operators index into it).  nestedLoops: fold pieces that no
+// equality links into nested-loops joins (RSQ_ENGINE_NESTED_LOOPS) instead of refusing the statement
+void planSelect(Statement& st, ExprPool& pool, const std::vector<Table*>& db, PlanDesc& out, bool nestedLoops = false);
 
 std::string dumpPlan(const rsq_plan_desc& d, const std::vector<Table*>& db);
 

@@ -27,13 +27,13 @@ class rsq_config(C.Structure):
                 ("num_threads", C.c_int32), ("emit_machine_code", C.c_int32), ("optimize", C.c_int32),
                 ("device", C.c_int32), ("kernel_cache_dir", C.c_char_p), ("emission_order", C.c_int32),
                 ("compat_flags", C.c_uint32), ("engine_flags", C.c_uint32), ("reserved0", C.c_uint32),
-                ("arena_reserve_bytes", C.c_int64), ("arena_keep_bytes", C.c_int64)]
+                ("arena_reserve_bytes", C.c_int64), ("arena_keep_bytes", C.c_int64), ("nested_loops_max_pairs", C.c_int64)]
 
     @classmethod
     def make(cls, device: int, cache_dir=None, print_source: bool = False, emission_order: int = 0, compat_flags: int = 0,
-             engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0):
+             engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0, nested_loops_max_pairs: int = 0):
         return cls(C.sizeof(cls), 1 if print_source else 0, 0, 0, 1, 1, 0, device, cache_dir, emission_order, compat_flags,
-                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes)
+                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes, nested_loops_max_pairs)
 
 
 class rsq_report(C.Structure):
@@ -58,7 +58,7 @@ class rsq_multi_config(C.Structure):
 MERGE_AUTO, MERGE_RCCL, MERGE_PEER_COPY = 0, 1, 2
 EMIT_REFERENCE, EMIT_ANY = 0, 1
 COMPAT_JIT_INT16_CAST = 1      # rsq_compat: TYPECAST INT -> BIGINT as the reference's asmjit JIT executes it (low 16 bits)
-ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO = 1, 2      # rsq_engine_flags
+ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS = 1, 2, 4      # rsq_engine_flags
 
 
 class EngineError(RuntimeError):
@@ -217,13 +217,15 @@ class Context:
         return self
 
     def __init__(self, device: int = 0, cache_dir: Optional[str] = None, print_source: bool = False, emission_order: int = 0,
-                 compat_flags: int = 0, engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0):
+                 compat_flags: int = 0, engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0,
+                 nested_loops_max_pairs: int = 0):
         """emission_order: EMIT_REFERENCE (0: rows of an unsorted aggregation in the reference's hash-table order) or EMIT_ANY;
         compat_flags: rsq_compat bits (COMPAT_JIT_INT16_CAST); engine_flags: rsq_engine_flags bits (ENGINE_DRIVER_ALLOC,
-        ENGINE_NO_PLAN_MEMO); arena_*: see rsq_config"""
+        ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS); arena_*, nested_loops_max_pairs (0: 2^36 pairs): see rsq_config"""
         self._L = lib()
         self._cache = cache_dir.encode() if cache_dir else None
-        cfg = rsq_config.make(device, self._cache, print_source, emission_order, compat_flags, engine_flags, arena_reserve_bytes, arena_keep_bytes)
+        cfg = rsq_config.make(device, self._cache, print_source, emission_order, compat_flags, engine_flags, arena_reserve_bytes, arena_keep_bytes,
+                              nested_loops_max_pairs)
         h = C.c_void_p()
         rc = self._L.rsq_ctx_create(C.byref(cfg), C.byref(h))
         if rc != 0:

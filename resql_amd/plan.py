@@ -317,6 +317,9 @@ class Plan:
     def aggregation(self, aggs: Sequence[int], groups: Sequence[int], child: int):
         return self._o(OpNode("AGGREGATION", [child], exprs=list(aggs), exprs2=list(groups)))
     def materialize(self, child: int): return self._o(OpNode("MATERIALIZE", [child]))
+    def nestedloopsjoin(self, left: int, right: int, cond: Optional[int] = None):
+        """left = the inner side (materialised first), right = the outer side (streams); cond: optional join condition"""
+        return self._o(OpNode("NESTEDLOOPSJOIN", [left, right], exprs=[] if cond is None else [cond]))
     def orderby(self, exprs: Sequence[int], child: int): return self._o(OpNode("ORDERBY", [child], exprs=list(exprs)))
 
     def set_root(self, op: int, limit: Optional[int] = None, request_all: bool = False):
