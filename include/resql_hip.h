@@ -367,7 +367,21 @@ void rsq_db_destroy(rsq_db* db);
  *
  * devices may list a GPU more than once (shards that share a GPU: how a one-GPU box runs N shards); RCCL cannot hold a device
  * twice, so such handles — and any handle created with RSQ_MERGE_PEER_COPY — move the partial tables with peer copies to
- * the root and reduce them with the engine's merge kernel. */
+ * the root and reduce them with the engine's merge kernel.
+ *
+ * Nested-loops joins (base->engine_flags has RSQ_ENGINE_NESTED_LOOPS; without it rsq_multi_query_compile refuses them,
+ * RSQ_ERR_UNSUPPORTED): the plan holds one top-level RSQ_OP_NESTEDLOOPSJOIN on its last pipeline, and its pair space is split by the
+ * OUTER side's rows; every shard pairs its outer rows with the WHOLE inner side in the reference's inner order, so pair ordinals
+ * (outer row x inner rows + inner position, rows numbered over the whole table) and the merged result are the one-context ones.
+ *   - outer table (the one the join's pipeline scans): sharded - each shard scans its own rows; replicated (equal row0, row count and
+ *     statistics on every shard) - each shard scans the slice rsq_multi_shard_rows(n, N, i) of its copy.
+ *   - inner side (child[0], run as a query of its own): all its tables replicated - computed on every shard; exactly one table sharded,
+ *     and it is the source of the inner side's materialising pipeline - every shard computes its part and the parts are all-gathered
+ *     in shard order into every shard with peer copies (its shards must hold increasing row ranges).
+ *   - any other sharded table (a build side, a second inner table, one under a nested inner side): RSQ_ERR_UNSUPPORTED naming it.
+ * rsq_config.nested_loops_max_pairs bounds the statement: total outer rows x total inner rows, checked after the gather and before
+ * any outer pipeline runs.  The report counts the inner sides' kernels and bytes, rsq_multi_query_collective_ms includes the gather,
+ * rsq_multi_query_merge_name states the split ("nested-loops: outer rows over N shards, inner side gathered (...)" / "replicated"). */
 enum rsq_merge_mode { RSQ_MERGE_AUTO = 0, RSQ_MERGE_RCCL = 1, RSQ_MERGE_PEER_COPY = 2 };
 typedef struct rsq_multi_config {
     uint32_t struct_size;       /* sizeof(rsq_multi_config) of the header the host was compiled against (as rsq_config.struct_size) */

@@ -664,39 +664,91 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
 
 // The inner sides of the nested-loops joins: each runs as its own query, and its result columns (struct of arrays, strings by value) are
 // copied into device columns this query owns.  Then the pair budget: outer rows x inner rows above rsq_config.nested_loops_max_pairs
-// ends the execution before the outer pipeline starts.
+// ends the execution before the outer pipeline starts.  Across GPUs multi.cpp runs the same steps itself (nestedLoops* below): every
+// shard's inner part, then the budget over the whole statement, then the all-gather of the parts.
+static void runNestedLoopsInner(NljState& n, bool run) {
+    n.nInner = 0; n.innerKernels = 0; n.innerBytes = 0;
+    if (!run) return;
+    Query& in = *n.inner;
+    executeQuery(in, false);
+    n.nInner = in.matRows;
+    n.innerKernels = in.report.num_kernels; n.innerBytes = in.report.bytes_read;
+}
+
+static void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner) {
+    Context& ctx = q.ctx;
+    n.nInner = nInner;
+    const int64_t budget = ctx.cfg.nested_loops_max_pairs;
+    const long double pairs = (long double)outer * (long double)n.nInner;
+    if (pairs > (long double)budget)
+        failUnsupported("nested-loops join: " + std::to_string((long long)outer) + " outer rows x " + std::to_string((long long)n.nInner) +
+                        " inner rows is more than rsq_config.nested_loops_max_pairs (" + std::to_string((long long)budget) + " pairs)");
+    // a materialisation counts tuples per lane and per 128-row tile in 32 bits: 128 outer rows x the inner rows must stay below 2^32
+    if (n.pipeline >= 0 && q.pipelines[(size_t)n.pipeline].sink == SinkKind::MATERIALIZE && 128.0L * (long double)n.nInner >= 4294967296.0L)
+        failUnsupported("nested-loops join: " + std::to_string((long long)n.nInner) + " inner rows - a 128-row tile of the outer side could emit "
+                        "2^32 or more tuples, beyond the materialisation's 32-bit tile counts");
+    if (n.nInner > n.innerCapacity) {
+        for (void* p : n.dCols) ctx.free(p);
+        n.dCols.clear();
+        n.innerCapacity = std::max<int64_t>(n.nInner, 64);
+        for (auto& a : n.innerSchema) n.dCols.push_back(ctx.alloc((size_t)n.innerCapacity * (size_t)columnWidth(a.type)));
+    }
+}
+
 static void prepareNestedLoops(Query& q) {
     Context& ctx = q.ctx;
     for (NljState& n : q.nljs) {
         if (!n.inner || !n.outerSrc) continue;           // (a join of an inner side: that side's query prepares it)
         Query& in = *n.inner;
         const int64_t outer = n.outerSrc->nRows;
-        n.nInner = 0;
-        if (outer > 0) {                                 // (an empty outer side needs no inner rows)
-            executeQuery(in, false);
-            n.nInner = in.matRows;
-            q.report.num_kernels += in.report.num_kernels;
-            q.report.bytes_read += in.report.bytes_read;
-        }
-        const int64_t budget = ctx.cfg.nested_loops_max_pairs;
-        const long double pairs = (long double)outer * (long double)n.nInner;
-        if (pairs > (long double)budget)
-            failUnsupported("nested-loops join: " + std::to_string((long long)outer) + " outer rows x " + std::to_string((long long)n.nInner) +
-                            " inner rows is more than rsq_config.nested_loops_max_pairs (" + std::to_string((long long)budget) + " pairs)");
-        // a materialisation counts tuples per lane and per 128-row tile in 32 bits: 128 outer rows x the inner rows must stay below 2^32
-        if (n.pipeline >= 0 && q.pipelines[(size_t)n.pipeline].sink == SinkKind::MATERIALIZE && 128.0L * (long double)n.nInner >= 4294967296.0L)
-            failUnsupported("nested-loops join: " + std::to_string((long long)n.nInner) + " inner rows - a 128-row tile of the outer side could emit "
-                            "2^32 or more tuples, beyond the materialisation's 32-bit tile counts");
-        if (n.nInner > n.innerCapacity) {
-            for (void* p : n.dCols) ctx.free(p);
-            n.dCols.clear();
-            n.innerCapacity = std::max<int64_t>(n.nInner, 64);
-            for (auto& a : n.innerSchema) n.dCols.push_back(ctx.alloc((size_t)n.innerCapacity * (size_t)columnWidth(a.type)));
-        }
+        runNestedLoopsInner(n, outer > 0);               // (an empty outer side needs no inner rows)
+        q.report.num_kernels += n.innerKernels;
+        q.report.bytes_read += n.innerBytes;
+        bindNestedLoops(q, n, outer, n.nInner);
         for (size_t k = 0; k < n.innerSchema.size() && n.nInner > 0; k++) {
             const void* src = in.dMatCols[(size_t)n.innerCol[k]];
             RSQ_HIP(hipMemcpyAsync(n.dCols[k], src, (size_t)n.nInner * (size_t)columnWidth(n.innerSchema[k].type), hipMemcpyDefault, ctx.stream));
         }
+    }
+}
+
+// the plan's one nested-loops join that is not inside another one's inner side (multi.cpp accepts no other plan)
+static NljState& topNestedLoops(Query& q) {
+    NljState* top = nullptr;
+    for (NljState& n : q.nljs)
+        if (n.inner && n.outerSrc) {
+            if (top) failUnsupported("more than one nested-loops join outside each other's inner side");
+            top = &n;
+        }
+    if (!top) failInvalid("the plan has no nested-loops join");
+    return *top;
+}
+
+bool queryHasNestedLoops(const Query& q) { return !q.nljs.empty(); }
+const Table* nestedLoopsOuterSource(Query& q) { return topNestedLoops(q).outerSrc; }
+void setNestedLoopsExternal(Query& q, const Table* gathered) {
+    (void)topNestedLoops(q);
+    q.nljExternal = true;
+    q.gatheredTables.clear();
+    if (gathered) q.gatheredTables.push_back(gathered);
+}
+void nestedLoopsRunInner(Query& q, bool run, int64_t* rows, uint64_t* kernels, uint64_t* bytes) {
+    NljState& n = topNestedLoops(q);
+    RSQ_HIP(hipSetDevice(q.ctx.device));
+    runNestedLoopsInner(n, run);
+    *rows = n.nInner; *kernels = n.innerKernels; *bytes = n.innerBytes;
+}
+void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows) {
+    RSQ_HIP(hipSetDevice(q.ctx.device));
+    bindNestedLoops(q, topNestedLoops(q), outerRows, innerRows);
+}
+void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths) {
+    NljState& n = topNestedLoops(q);
+    part->clear(); bound->clear(); widths->clear();
+    for (size_t k = 0; k < n.innerSchema.size(); k++) {
+        part->push_back(n.inner->dMatCols.empty() ? nullptr : n.inner->dMatCols[(size_t)n.innerCol[k]]);
+        bound->push_back(k < n.dCols.size() ? n.dCols[k] : nullptr);
+        widths->push_back((size_t)columnWidth(n.innerSchema[k].type));
     }
 }
 
@@ -714,7 +766,12 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
-    if (!q.nljs.empty()) prepareNestedLoops(q);      // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
+    // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
+    if (!q.nljs.empty() && !q.nljExternal) prepareNestedLoops(q);
+    else if (q.nljExternal) {                        // (multi.cpp ran and bound the inner side: its work is part of this execution's)
+        const NljState& n = topNestedLoops(q);
+        q.report.num_kernels += n.innerKernels; q.report.bytes_read += n.innerBytes;
+    }
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
         // the full kernels are in the cache now: the quick tier's are replaced (same arguments, same tables - nothing else changes).
         // (A full tier that failed to compile leaves the query on the quick one.)
@@ -1637,6 +1694,11 @@ bool shardGroupsDisjoint(const std::vector<Query*>& parts, std::string& why) {
             const Table* tab = nullptr; int col = -1;
             for (Table* t : parts[i]->tables) { int c = t->findCol(g->symbol); if (c >= 0) { tab = t; col = c; break; } }
             if (!tab) { usable = false; break; }
+            if (std::find(parts[i]->gatheredTables.begin(), parts[i]->gatheredTables.end(), tab) != parts[i]->gatheredTables.end()) {
+                // (the gathered inner side of a nested-loops join: every shard pairs with ALL of its rows, whatever its own rows hold)
+                why = "group key " + g->symbol + " comes from a gathered inner side, which every shard sees whole";
+                usable = false; break;
+            }
             if (tab->nRows == 0) continue;
             const ColumnStats& st = tab->shardStats((size_t)col);      // what THIS shard's rows hold (stats may be the union over all shards)
             if (!st.valid || !st.distinctBytes.empty() || tab->cols[(size_t)col].type.isString()) { usable = false; break; }

@@ -334,6 +334,17 @@ size_t tableStatsBytes(const Table& t);
 void exportTableStats(const Table& t, void* buf, size_t bytes);
 void unifyShardStats(Table& t, const void* blobs, int nShards, size_t blobBytes);
 bool queryOrderedWithLimit(const Query& q);             // ORDER BY ... LIMIT k at the root
+// Nested-loops joins across shards (multi.cpp; engine.cpp prepareNestedLoops is the one-context form).  The plan's top-level join: the
+// table its outer pipeline scans; then per execution: the inner side run on this shard (`run` false: no rows), the pair budget and the
+// bound columns sized for the whole statement, and the device columns of this shard's inner part and of the bound (gathered) inner side.
+// With setNestedLoopsExternal, executeQuery runs the outer side only; `gathered` (may be null) is a table every shard sees whole through
+// the inner side (it never proves shards disjoint in a group key).
+bool queryHasNestedLoops(const Query& q);
+const Table* nestedLoopsOuterSource(Query& q);
+void setNestedLoopsExternal(Query& q, const Table* gathered);
+void nestedLoopsRunInner(Query& q, bool run, int64_t* rows, uint64_t* kernels, uint64_t* bytes);
+void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows);
+void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths);
 bool queryAsyncCapable(const Query& q);                 // every pipeline can be enqueued without the host in between
 bool queryIsDense(const Query& q);              // its aggregation ends in a dense partial table ([min | max | sum] words)
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr);

@@ -276,7 +276,8 @@ struct NljState {
     int pipeline = -1;               // index of that pipeline in Query::pipelines
     std::vector<void*> dCols;        // device columns [innerCapacity] per bound attribute
     int64_t innerCapacity = 0;
-    int64_t nInner = 0;              // rows of the inner side in this execution
+    int64_t nInner = 0;              // rows of the inner side in this execution (across GPUs: of the whole inner side, all shards' parts)
+    uint64_t innerKernels = 0, innerBytes = 0;      // what the inner side's own execution launched and read
 };
 
 struct Query {
@@ -293,6 +294,10 @@ struct Query {
     std::vector<Pipeline> pipelines;
     std::vector<std::unique_ptr<HashTable>> hashTables;
     std::vector<NljState> nljs;            // nested-loops joins (OpNode::nlj)
+    // rsq_multi_*: the inner side of the top-level nested-loops join is run and bound by multi.cpp (nestedLoops* in engine.h) in front of
+    // the execution, which then runs the outer side only.  `gatheredTables`: tables whose rows every shard sees through that inner side.
+    bool nljExternal = false;
+    std::vector<const Table*> gatheredTables;
     OpNode* agg = nullptr;                 // the aggregation whose input pipeline runs on the device (may be null)
     AggMode aggMode = AggMode::NONE;
     std::vector<DenseKey> denseKeys;

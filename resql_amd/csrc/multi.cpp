@@ -96,7 +96,19 @@ struct rsq_multi_query {
     std::vector<double> shardKernelMs;
     hipEvent_t evMerge0 = nullptr, evMerge1 = nullptr;      // on the root's stream, around the group-by merge of the last execution
     double collectiveMs = 0;
+    // a nested-loops join (see "Nested-loops joins across GPUs" below): its pair space split by the outer side's rows
+    bool nlj = false;
+    bool nljGathered = false;           // the inner side is sharded: every shard's part is all-gathered into every shard (else replicated)
+    std::string mergeBase;              // mergeText behind the split's description
+    std::vector<std::unique_ptr<Table>> outerSlices;      // a replicated outer table: shard i's slice of its copy (views, no rows of their own)
+    std::vector<hipEvent_t> innerDone;  // shard i's inner part is materialised (the gather's copies wait for it)
+    std::vector<hipEvent_t> gather0, gather1;             // around the gather's copies on shard i's stream
+    int64_t gatherBytes = 0;            // moved between shards by the last gather
     ~rsq_multi_query() {
+        for (size_t i = 0; i < innerDone.size(); i++) {      // (a compilation that failed part-way made some of them only)
+            (void)hipSetDevice(m->ctxs[i]->device);
+            for (hipEvent_t e : {innerDone[i], gather0[i], gather1[i]}) if (e) (void)hipEventDestroy(e);
+        }
         if (evMerge0 && m && !m->ctxs.empty()) { (void)hipSetDevice(m->ctxs[0]->device); (void)hipEventDestroy(evMerge0); (void)hipEventDestroy(evMerge1); }
         if (gathered && m && !m->ctxs.empty()) { (void)hipSetDevice(m->ctxs[0]->device); m->ctxs[0]->free(gathered); }
         for (size_t i = 0; i < ready.size(); i++) if (ready[i]) { (void)hipSetDevice(m->ctxs[i]->device); (void)hipEventDestroy(ready[i]); }
@@ -170,6 +182,187 @@ void enqueueMergeUntimed(rsq_multi_query& mq) {
             RSQ_HIP(hipMemcpyPeerAsync(mq.gathered + (size_t)i * (size_t)words, root.device, part[(size_t)i], c.device, (size_t)words * 8, root.stream));
     }
     mergePartialsAsync(root, mq.gathered, n, words, mq.nMin, mq.nMax, mq.nSum, part[0]);
+}
+
+// ---- Nested-loops joins across GPUs ---------------------------------------------------------------------------------------------
+// The pair space is split by the OUTER side's rows: every shard pairs its outer rows with the WHOLE inner side, in the reference's inner
+// order.  Outer rows are numbered over the whole table (row0) and inner positions over the whole inner side, so a shard's pair ordinals
+// (outer row x inner rows + inner position, codegen.cpp consumeNestedLoops) and first-row trackers are the one-context ones, and the
+// dense or the general merge gives the one-context bytes.
+//   outer side (the table the join's pipeline scans): sharded - each shard scans its own rows; replicated - each shard scans the slice
+//              rsq_multi_shard_rows of its copy, through a view with its own identity (key indexes and the plan memo key on uid, row0, rows);
+//   inner side (the left subtree, a query of its own): every table replicated - computed on every shard; exactly one table sharded, and
+//              it is the source of the inner side's materialising pipeline - each shard computes its part, and the parts are all-gathered
+//              in shard order with peer copies.  Everything else (a sharded build side, two sharded inner tables, a sharded table under a
+//              nested inner side) is refused.
+
+// the scan a plan operator's pipeline starts at (codegen.cpp Walker::produce: a hash join's probe side and a nested-loops join's outer
+// side continue the pipeline, every other operator its one child)
+int pipelineScan(const rsq_plan_desc& p, int op) {
+    for (int steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops; steps++) {
+        const rsq_op& o = p.ops[op];
+        if (o.tag == RSQ_OP_SCAN) return op;
+        op = o.tag == RSQ_OP_HASHJOIN || o.tag == RSQ_OP_NESTEDLOOPSJOIN ? o.child[1] : o.child[0];
+    }
+    failInvalid("malformed plan: an operator chain ends without a scan");
+}
+void subtreeOps(const rsq_plan_desc& p, int op, std::vector<int>& out) {
+    if (op < 0 || op >= p.n_ops) failInvalid("malformed plan: operator index out of range");
+    if (std::find(out.begin(), out.end(), op) != out.end()) return;
+    out.push_back(op);
+    for (int k = 0; k < 2; k++) if (p.ops[op].child[k] >= 0) subtreeOps(p, p.ops[op].child[k], out);
+}
+
+// Decides how a nested-loops plan is split (the rules above).  `sharded[t]`: table t's instances differ between the shards.  Returns the
+// plan operator of the outer side's scan; `gatheredTable` is the sharded inner table (-1: the inner side is replicated).
+int planNestedLoopsSplit(rsq_multi& m, const rsq_plan_desc& p, rsq_table* const* tables, int nTables, const std::vector<bool>& sharded,
+                         int* gatheredTable) {
+    const int n = (int)m.ctxs.size();
+    auto tab = [&](int i, int t) { return reinterpret_cast<const Table*>(tables[(size_t)i * (size_t)nTables + (size_t)t]); };
+    auto tableOf = [&](int scan) {
+        const int t = p.ops[scan].table;
+        if (t < 0 || t >= nTables) failInvalid("malformed plan: a scan names no table");
+        return t;
+    };
+    std::vector<int> all;
+    subtreeOps(p, p.root, all);
+    // the top-level join: not inside another join's inner side (those belong to the inner query)
+    std::vector<int> inInner;
+    for (int o : all)
+        if (p.ops[o].tag == RSQ_OP_NESTEDLOOPSJOIN) subtreeOps(p, p.ops[o].child[0], inInner);
+    int nlj = -1;
+    for (int o : all)
+        if (p.ops[o].tag == RSQ_OP_NESTEDLOOPSJOIN && std::find(inInner.begin(), inInner.end(), o) == inInner.end()) {
+            if (nlj >= 0) failUnsupported("across GPUs a plan holds one nested-loops join (and joins inside its inner side)");
+            nlj = o;
+        }
+    // ... on the plan's last pipeline: its outer rows are split, so it must not fill a join table every shard needs whole
+    bool onLast = false;
+    for (int op = p.root, steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops && p.ops[op].tag != RSQ_OP_SCAN; steps++) {
+        if (op == nlj) onLast = true;
+        op = p.ops[op].tag == RSQ_OP_HASHJOIN || p.ops[op].tag == RSQ_OP_NESTEDLOOPSJOIN ? p.ops[op].child[1] : p.ops[op].child[0];
+    }
+    if (!onLast) failUnsupported("a nested-loops join that feeds a join's build side is not split across GPUs");
+    const int outerScan = pipelineScan(p, p.ops[nlj].child[1]);
+    const int innerScan = pipelineScan(p, p.ops[nlj].child[0]);
+    std::vector<int> inner;
+    subtreeOps(p, p.ops[nlj].child[0], inner);
+    std::vector<int> shardedInner;
+    for (int o : all) {
+        if (p.ops[o].tag != RSQ_OP_SCAN || o == outerScan || !sharded[(size_t)tableOf(o)]) continue;
+        const std::string name = tab(0, tableOf(o))->name;
+        if (std::find(inner.begin(), inner.end(), o) == inner.end())
+            failUnsupported("table " + name + " is sharded (its shards differ) but is a build side of the nested-loops plan: across GPUs only the "
+                            "nested-loops join's outer table and one table of its inner side may be sharded - replicate " + name);
+        shardedInner.push_back(o);
+    }
+    if (shardedInner.size() > 1)
+        failUnsupported("the inner side of the nested-loops join reads two sharded tables (" + tab(0, tableOf(shardedInner[0]))->name + ", " +
+                        tab(0, tableOf(shardedInner[1]))->name + "): at most one may be sharded - replicate the others");
+    if (!shardedInner.empty() && shardedInner[0] != innerScan)
+        failUnsupported("table " + tab(0, tableOf(shardedInner[0]))->name + " is sharded but is not the source of the nested-loops join's inner side "
+                        "(a build side, or under a nested inner side): replicate it");
+    const int gathered = shardedInner.empty() ? -1 : shardedInner[0];
+    if (gathered >= 0) {
+        // the parts go together in shard order: that is the inner side's order only if the shards hold increasing row ranges
+        const int t = tableOf(gathered);
+        for (int op = p.ops[nlj].child[0]; op != gathered; op = p.ops[op].tag == RSQ_OP_HASHJOIN || p.ops[op].tag == RSQ_OP_NESTEDLOOPSJOIN ? p.ops[op].child[1] : p.ops[op].child[0])
+            if (p.ops[op].tag == RSQ_OP_ORDERBY || p.ops[op].tag == RSQ_OP_AGGREGATION)
+                failUnsupported("table " + tab(0, t)->name + " is sharded, and the nested-loops join's inner side over it is sorted or aggregated: replicate it");
+        for (int i = 1; i < n; i++)
+            if (tab(i, t)->row0 < tab(i - 1, t)->row0 + tab(i - 1, t)->nRows)
+                failUnsupported("table " + tab(0, t)->name + " is the sharded inner side of a nested-loops join, and its shards must hold increasing row "
+                                "ranges (shard " + std::to_string(i) + " starts at row " + std::to_string((long long)tab(i, t)->row0) + ", before the end of shard " +
+                                std::to_string(i - 1) + "'s rows): set each shard's first row (rsq_table_set_first_row)");
+        *gatheredTable = t;
+    } else *gatheredTable = -1;
+    return outerScan;
+}
+
+// rows [start, start + rows) of a table, as a table of its own: offset column pointers, the first row numbered over the whole table, the
+// parent's statistics and row count (it plans as the whole table, like a shard), a fresh identity; the parent keeps the memory
+std::unique_ptr<Table> sliceOf(const Table& t, int64_t start, int64_t rows) {
+    std::unique_ptr<Table> v(new Table());
+    v->ctx = t.ctx; v->name = t.name; v->nRows = rows; v->row0 = t.row0 + start; v->nRowsTotal = t.totalRows();
+    v->cols = t.cols;
+    for (TableColumn& c : v->cols) {
+        c.owned = false;
+        if (c.dptr) c.dptr = (char*)c.dptr + (size_t)start * (size_t)columnWidth(c.type);
+    }
+    return v;
+}
+
+// one execution of a nested-loops plan: every shard's inner part (shard threads), the pair budget of the whole statement, the
+// all-gather of the parts (or each shard binds its own, replicated, inner side), then every shard's outer pipelines
+template <typename OnThreads>
+void executeNestedLoops(rsq_multi_query& mq, OnThreads&& onThreads) {
+    rsq_multi& m = *mq.m;
+    const int n = (int)m.ctxs.size();
+    int64_t outer = 0;
+    for (Query* q : mq.qs) outer += nestedLoopsOuterSource(*q)->nRows;
+    // (a shard whose outer slice is empty still makes its inner part for the others)
+    std::vector<int64_t> rows((size_t)n, 0);
+    std::vector<uint64_t> kernels((size_t)n, 0), bytes((size_t)n, 0);
+    onThreads([&](int i) {
+        Query& q = *mq.qs[(size_t)i];
+        nestedLoopsRunInner(q, outer > 0, &rows[(size_t)i], &kernels[(size_t)i], &bytes[(size_t)i]);
+        RSQ_HIP(hipEventRecord(mq.innerDone[(size_t)i], m.ctxs[(size_t)i]->stream));
+    });
+    int64_t inner = 0;
+    for (int i = 0; i < n; i++) {
+        if (!mq.nljGathered && rows[(size_t)i] != rows[0])
+            throw Error(RSQ_ERR_RUNTIME, "internal: replicated inner sides of a nested-loops join differ between shards (" + std::to_string((long long)rows[0]) +
+                                         " and " + std::to_string((long long)rows[(size_t)i]) + " rows)");
+        inner = mq.nljGathered ? inner + rows[(size_t)i] : rows[0];
+    }
+    try {
+        for (Query* q : mq.qs) nestedLoopsBind(*q, outer, inner);
+    } catch (const Error&) {
+        // refused before any outer pipeline: the report holds the inner sides' work
+        mq.report = rsq_report{};
+        for (int i = 0; i < n; i++) { mq.report.num_kernels += (int32_t)kernels[(size_t)i]; mq.report.bytes_read += bytes[(size_t)i]; }
+        throw;
+    }
+    // the bound columns of shard j: the parts of all shards back to back (gathered), or its own inner side
+    std::vector<std::vector<const void*>> part((size_t)n);
+    std::vector<std::vector<void*>> bound((size_t)n);
+    std::vector<size_t> width;
+    for (int i = 0; i < n; i++) nestedLoopsColumns(*mq.qs[(size_t)i], &part[(size_t)i], &bound[(size_t)i], &width);
+    mq.gatherBytes = 0;
+    for (int j = 0; j < n; j++) {
+        Context& dst = *m.ctxs[(size_t)j];
+        RSQ_HIP(hipSetDevice(dst.device));
+        if (mq.nljGathered) RSQ_HIP(hipEventRecord(mq.gather0[(size_t)j], dst.stream));
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            if (!mq.nljGathered && i != j) continue;
+            const Context& src = *m.ctxs[(size_t)i];
+            if (i != j && rows[(size_t)i] > 0) RSQ_HIP(hipStreamWaitEvent(dst.stream, mq.innerDone[(size_t)i], 0));
+            for (size_t k = 0; k < width.size() && rows[(size_t)i] > 0; k++) {
+                char* to = (char*)bound[(size_t)j][k] + (size_t)at * width[k];
+                const size_t b = (size_t)rows[(size_t)i] * width[k];
+                if (src.device == dst.device) RSQ_HIP(hipMemcpyAsync(to, part[(size_t)i][k], b, hipMemcpyDeviceToDevice, dst.stream));
+                else RSQ_HIP(hipMemcpyPeerAsync(to, dst.device, part[(size_t)i][k], src.device, b, dst.stream));
+                if (i != j) mq.gatherBytes += (int64_t)b;
+            }
+            at += rows[(size_t)i];
+        }
+        if (mq.nljGathered) RSQ_HIP(hipEventRecord(mq.gather1[(size_t)j], dst.stream));
+    }
+    if (mq.nljGathered) mq.mergeText = "nested-loops: outer rows over " + std::to_string(n) + " shards, inner side gathered (peer copies, " +
+                                       std::to_string((long long)mq.gatherBytes) + " bytes); " + mq.mergeBase;
+    onThreads([&](int i) { executeQuery(*mq.qs[(size_t)i], mq.dense); });
+}
+
+// device time of the last gather: the slowest shard's copies (0 without a gather)
+double gatherMs(rsq_multi_query& mq) {
+    double ms = 0;
+    for (size_t i = 0; mq.nljGathered && i < mq.gather0.size(); i++) {
+        float e = 0;
+        RSQ_HIP(hipSetDevice(mq.m->ctxs[i]->device));
+        if (hipEventSynchronize(mq.gather1[i]) == hipSuccess && hipEventElapsedTime(&e, mq.gather0[i], mq.gather1[i]) == hipSuccess) ms = std::max(ms, (double)e);
+    }
+    return ms;
 }
 
 }  // namespace
@@ -317,11 +510,16 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
     if (!m || !plan || !out || n_tables < 0 || (n_tables > 0 && !tables)) return RSQ_ERR_INVALID;
     *out = nullptr;
     return guardedM(m, [&] {
-        for (int i = 0; i < plan->n_ops; i++)
-            if (plan->ops && plan->ops[i].tag == RSQ_OP_NESTEDLOOPSJOIN) failUnsupported("a nested-loops join is not executed across GPUs (rsq_multi_*): run it on one context");
         const int n = (int)m->ctxs.size();
         std::unique_ptr<rsq_multi_query> mq(new rsq_multi_query());
         mq->m = m;
+        for (int i = 0; i < plan->n_ops; i++)
+            if (plan->ops && plan->ops[i].tag == RSQ_OP_NESTEDLOOPSJOIN) {
+                if (!(m->ctxs[0]->cfg.engine_flags & RSQ_ENGINE_NESTED_LOOPS))
+                    failUnsupported("a nested-loops join is not executed across GPUs (rsq_multi_*): run it on one context");
+                mq->nlj = true;
+            }
+        std::vector<bool> sharded((size_t)n_tables, false);     // the table's instances differ between the shards
         for (int i = 0; i < n; i++)
             for (int t = 0; t < n_tables; t++) {
                 const Table* tb = reinterpret_cast<const Table*>(tables[(size_t)i * (size_t)n_tables + (size_t)t]);
@@ -350,12 +548,54 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                     if (memcmp(blobs.data(), blobs.data() + (size_t)i * bb, bb) != 0) replicated = false;
                 }
                 blobBytes[(size_t)t] = replicated ? 0 : bb;
+                sharded[(size_t)t] = !replicated;
             }
             for (int t = 0; t < n_tables; t++)
                 if (blobBytes[(size_t)t])
                     for (int i = 0; i < n; i++) unifyShardStats(*tab(i, t), allBlobs[(size_t)t].data(), n, blobBytes[(size_t)t]);
         }
-        for (int i = 0; i < n; i++) mq->qs.push_back(compileQuery(*m->ctxs[(size_t)i], *plan, tables + (size_t)i * (size_t)n_tables, n_tables));
+        if (!mq->nlj) {
+            for (int i = 0; i < n; i++) mq->qs.push_back(compileQuery(*m->ctxs[(size_t)i], *plan, tables + (size_t)i * (size_t)n_tables, n_tables));
+        } else {
+            int gatheredTable = -1;
+            const int outerScan = planNestedLoopsSplit(*m, *plan, tables, n_tables, sharded, &gatheredTable);
+            const int outerTable = plan->ops[outerScan].table;
+            // a replicated outer table: the outer scan reads shard i's slice of it, a table appended to the shard's array
+            const bool sliced = n > 1 && !sharded[(size_t)outerTable];
+            std::vector<rsq_op> ops(plan->ops, plan->ops + plan->n_ops);
+            rsq_plan_desc p = *plan;
+            if (sliced) { ops[(size_t)outerScan].table = n_tables; p.ops = ops.data(); }
+            const int nt = n_tables + (sliced ? 1 : 0);
+            mq->innerDone.assign((size_t)n, nullptr); mq->gather0.assign((size_t)n, nullptr); mq->gather1.assign((size_t)n, nullptr);
+            for (int i = 0; i < n; i++) {
+                std::vector<rsq_table*> ts(tables + (size_t)i * (size_t)n_tables, tables + (size_t)(i + 1) * (size_t)n_tables);
+                const Table* outer = reinterpret_cast<const Table*>(ts[(size_t)outerTable]);
+                if (sliced) {
+                    int64_t r0, nr;
+                    rsq_multi_shard_rows(outer->nRows, n, i, &r0, &nr);
+                    mq->outerSlices.push_back(sliceOf(*outer, r0, nr));
+                    outer = mq->outerSlices.back().get();
+                    ts.push_back(reinterpret_cast<rsq_table*>(mq->outerSlices.back().get()));
+                }
+                Query* q = compileQuery(*m->ctxs[(size_t)i], p, ts.data(), nt);
+                mq->qs.push_back(q);
+                if (nestedLoopsOuterSource(*q) != outer)
+                    throw Error(RSQ_ERR_RUNTIME, "internal: the nested-loops join's outer pipeline does not scan table " + outer->name);
+                setNestedLoopsExternal(*q, gatheredTable >= 0 ? reinterpret_cast<const Table*>(ts[(size_t)gatheredTable]) : nullptr);
+                RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device));
+                RSQ_HIP(hipEventCreateWithFlags(&mq->innerDone[(size_t)i], hipEventDisableTiming));
+                RSQ_HIP(hipEventCreate(&mq->gather0[(size_t)i])); RSQ_HIP(hipEventCreate(&mq->gather1[(size_t)i]));
+            }
+            mq->nljGathered = gatheredTable >= 0;
+            if (mq->nljGathered)          // (peer copies between distinct GPUs: direct over xGMI where the pair allows it)
+                for (int j = 0; j < n; j++)
+                    for (int i = 0; i < n; i++) {
+                        int can = 0;
+                        if (m->devices[(size_t)i] == m->devices[(size_t)j] || hipDeviceCanAccessPeer(&can, m->devices[(size_t)j], m->devices[(size_t)i]) != hipSuccess || !can) continue;
+                        RSQ_HIP(hipSetDevice(m->devices[(size_t)j]));
+                        if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
+                    }
+        }
         mq->dense = queryIsDense(*mq->qs[0]);
         if (mq->dense) {
             // (with unified statistics every shard derives the same layout; anything else is a defect of this library, not of the data)
@@ -372,9 +612,11 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 mq->ready.assign((size_t)n, nullptr);
                 for (int i = 1; i < n; i++) { RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device)); RSQ_HIP(hipEventCreateWithFlags(&mq->ready[(size_t)i], hipEventDisableTiming)); }
             }
-            mq->async = true;
+            // (a nested-loops plan runs on host threads: the host stands between its inner and its outer sides)
+            mq->async = !mq->nlj;
             for (Query* q : mq->qs) mq->async = mq->async && queryAsyncCapable(*q);
-            mq->mergeText = std::string("dense partial tables: ") + rsq_multi_merge_name(m) + (mq->async ? "" : " (join builds: the shards run on host threads)");
+            mq->mergeText = std::string("dense partial tables: ") + rsq_multi_merge_name(m) +
+                            (mq->async ? "" : mq->nlj ? " (nested-loops join: the shards run on host threads)" : " (join builds: the shards run on host threads)");
         } else {
             for (int i = 1; i < n; i++) if (queryIsDense(*mq->qs[(size_t)i])) throw Error(RSQ_ERR_RUNTIME, "internal: shards planned from the same statistics disagree on the aggregation strategy");
             // Groups may straddle shard boundaries (the reference has ONE hash table all workers reach, aggregation.h:240-295):
@@ -392,6 +634,11 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                                  (forceGeneral ? std::string("forced") : disjoint ? std::string("no ORDER BY ... LIMIT to shorten") : why) + ")";
             if (n > 1 && !mq->orderedFast) for (Query* q : mq->qs) setHoldTail(*q, true);
         }
+        if (mq->nlj) {
+            mq->mergeBase = mq->mergeText;
+            mq->mergeText = "nested-loops: outer rows over " + std::to_string(n) + (n == 1 ? " shard" : " shards") + ", inner side " +
+                            (mq->nljGathered ? "gathered (peer copies)" : "replicated") + "; " + mq->mergeBase;
+        }
         mq->shardKernelMs.assign((size_t)n, 0.0);
         *out = mq.release();
     });
@@ -406,20 +653,32 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
         auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         // every shard's execution on its own host thread (plans whose pipelines need the host between kernels: join builds size
         // their tables, hash aggregations grow theirs)
-        auto onThreads = [&](bool partialOnly) {
+        auto onThreadsDo = [&](auto&& step) {
             std::vector<std::string> errs((size_t)n);
             std::vector<int> status((size_t)n, RSQ_OK);
             std::vector<std::thread> th;
             for (int i = 0; i < n; i++)
-                th.emplace_back([&, i, partialOnly] {
-                    try { executeQuery(*mq->qs[(size_t)i], partialOnly); }
+                th.emplace_back([&, i] {
+                    try { step(i); }
                     catch (const Error& e) { status[(size_t)i] = e.status; errs[(size_t)i] = e.what(); }
                     catch (const std::exception& e) { status[(size_t)i] = RSQ_ERR_RUNTIME; errs[(size_t)i] = e.what(); }
                 });
             for (auto& t : th) t.join();
             for (int i = 0; i < n; i++) if (status[(size_t)i] != RSQ_OK) throw Error(status[(size_t)i], "shard " + std::to_string(i) + ": " + errs[(size_t)i]);
         };
-        if (mq->dense && mq->async) {
+        auto onThreads = [&](bool partialOnly) { onThreadsDo([&](int i) { executeQuery(*mq->qs[(size_t)i], partialOnly); }); };
+        if (mq->nlj) {
+            // inner parts, the budget, the gather, the outer sides - then the merge of the plan's kind
+            executeNestedLoops(*mq, onThreadsDo);
+            if (mq->dense) {
+                enqueueMerge(*mq);
+                finalizeQuery(*mq->qs[0]);
+            } else {
+                double t1 = now();
+                if (n > 1) { if (mq->orderedFast) mergeShardResults(*mq->qs[0], mq->qs); else runTailMerged(*mq->qs[0], mq->qs); }
+                mq->report.finalize_time_ms = now() - t1;
+            }
+        } else if (mq->dense && mq->async) {
             // fan out: enqueue every shard's pipelines (no host synchronisation), then the merge behind them, then ONE
             // synchronising read-back on the root
             for (int i = 0; i < n; i++) executeQuery(*mq->qs[(size_t)i], true, true);
@@ -456,6 +715,7 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
             RSQ_HIP(hipSetDevice(m->ctxs[0]->device));
             if (hipEventSynchronize(mq->evMerge1) == hipSuccess && hipEventElapsedTime(&ms, mq->evMerge0, mq->evMerge1) == hipSuccess) mq->collectiveMs = ms;
         }
+        if (mq->nlj) mq->collectiveMs += gatherMs(*mq);
         rep.execution_time_ms = now() - t0;
         rep.hbm_gbps = rep.kernel_time_ms > 0 ? (double)rep.bytes_read / (rep.kernel_time_ms * 1e-3) / 1e9 : 0;
         mq->report = rep;

@@ -575,11 +575,14 @@ class MultiContext:
     """one host process, N GPUs (include/resql_hip.h rsq_multi_*): shard contexts + the RCCL (or peer-copy) group-by merge"""
 
     def __init__(self, devices: Sequence[int], merge: int = MERGE_AUTO, cache_dir: Optional[str] = None, emission_order: int = 0,
-                 compat_flags: int = 0):
+                 compat_flags: int = 0, engine_flags: int = 0, nested_loops_max_pairs: int = 0):
+        """engine_flags, nested_loops_max_pairs: as for Context, on every shard (ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
+        by its outer side's rows; the budget bounds the whole statement's pairs)"""
         self._L = lib()
         self._devs = (C.c_int32 * len(devices))(*devices)
         self._cache = cache_dir.encode() if cache_dir else None
-        self._base = rsq_config.make(0, self._cache, False, emission_order, compat_flags)
+        self._base = rsq_config.make(0, self._cache, False, emission_order, compat_flags, engine_flags,
+                                     nested_loops_max_pairs=nested_loops_max_pairs)
         cfg = rsq_multi_config(C.sizeof(rsq_multi_config), len(devices), C.pointer(self._base), self._devs, merge, 0)
         h = C.c_void_p()
         rc = self._L.rsq_multi_create(C.byref(cfg), C.byref(h))
