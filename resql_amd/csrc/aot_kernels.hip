@@ -413,6 +413,41 @@ void fillU64Async(Context& ctx, uint64_t* dptr, size_t n, uint64_t value) {
     RSQ_HIP(hipGetLastError());
 }
 
+// ---- derived tables (engine.cpp prepareDerived): packed ReSQL tuples -> one column per attribute ------------------------------
+// A tuple holds its values back to back at sizeInTuple widths (strings len + 1 bytes, CHAR(1) 2 bytes), so a value's offset is any
+// byte; a column holds them at columnWidth (strings by value at their declared width, no terminator).  One thread per row, tuples of
+// consecutive rows in consecutive threads: the wave reads 64 consecutive tuples (whole cache lines) and writes 64 consecutive
+// values of each column.  Reads and writes go byte by byte where the value is not aligned in both places.
+#define DERIVED_MAX_COLS 32
+struct DerivedColsArgs { const unsigned char* tuples; i64 n; int tupleSize, nCols; int off[DERIVED_MAX_COLS], width[DERIVED_MAX_COLS]; unsigned char* out[DERIVED_MAX_COLS]; };
+__global__ void __launch_bounds__(256) k_derived_columns(DerivedColsArgs a) {
+    for (i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x; r < a.n; r += (i64)gridDim.x * blockDim.x) {
+        const unsigned char* t = a.tuples + r * a.tupleSize;
+        for (int c = 0; c < a.nCols; c++) {
+            const int w = a.width[c];
+            const unsigned char* src = t + a.off[c];
+            unsigned char* dst = a.out[c] + r * w;
+            if (w == 8) { u64 v = 0; for (int b = 0; b < 8; b++) v |= (u64)src[b] << (8 * b); *reinterpret_cast<u64*>(dst) = v; }
+            else if (w == 4) { unsigned v = 0; for (int b = 0; b < 4; b++) v |= (unsigned)src[b] << (8 * b); *reinterpret_cast<unsigned*>(dst) = v; }
+            else for (int b = 0; b < w; b++) dst[b] = src[b];
+        }
+    }
+}
+
+void derivedColumns(Context& ctx, const uint8_t* tuples, int64_t nRows, int tupleSize, const std::vector<DerivedColumn>& cols) {
+    if (nRows <= 0 || cols.empty()) return;
+    if (cols.size() > DERIVED_MAX_COLS) throw Error(RSQ_ERR_UNSUPPORTED, "derived table with more than 32 columns");
+    DerivedColsArgs a{};
+    a.tuples = tuples; a.n = nRows; a.tupleSize = tupleSize; a.nCols = (int)cols.size();
+    for (size_t c = 0; c < cols.size(); c++) {
+        if (cols[c].width <= 0 || cols[c].offset < 0 || cols[c].offset + cols[c].width > tupleSize) throw Error(RSQ_ERR_INVALID, "derived column outside the tuple");
+        a.off[c] = cols[c].offset; a.width[c] = cols[c].width; a.out[c] = (unsigned char*)cols[c].out;
+    }
+    const unsigned grid = (unsigned)std::min<int64_t>(4 * (int64_t)ctx.numCUs, (nRows + 255) / 256);
+    hipLaunchKernelGGL(k_derived_columns, dim3(grid), dim3(256), 0, ctx.stream, a);
+    RSQ_HIP(hipGetLastError());
+}
+
 // Each workgroup owns chunks of 256 x COMPACT_PER_THREAD consecutive slots.  All first-row words of a thread are loaded up front
 // (independent, coalesced across the workgroup), the occupied ones are counted, an LDS scan gives every thread its
 // offset and ONE global atomic per workgroup and chunk reserves the output rows: returning atomics on a single word

@@ -132,6 +132,7 @@ Schema Walker::prune(const Schema& s, const std::vector<std::string>& req) {
 // -------------------------------------------------------------------------------------------
 void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // scan.h:221-263
     Table* t = o->table;
+    if (o->derived >= 0) nameDerivedColumns(q, o);
     if (q.requestAll) request.clear();
     pipe = Pipeline();
     pipe.src = t;
@@ -156,7 +157,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
         const TableColumn& c = t->cols[ci];
         // Values::dematerialize(..., required): an empty request set means all attributes
         if (!request.empty() && !has(request, c.name)) continue;
-        if (!c.dptr) {
+        if (!c.dptr && !t->derived) {      // (a derived table's columns are bound per execution)
             if (request.empty()) continue;   // declared without data: cannot be part of `select *`
             failInvalid("column " + c.name + " is needed by the plan but was declared without data");
         }
@@ -181,7 +182,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
             rowArgsTailGuarded += ", (valid ? a.c" + std::to_string(k) + "[r] : (" + ct + ")0)";
         }
     }
-    explainSteps.push_back("scan " + t->name + " [" + std::to_string((long long)t->nRows) + " rows, " +
+    explainSteps.push_back("scan " + t->name + " [" + (t->derived ? std::string("rows of this execution") : std::to_string((long long)t->nRows) + " rows") + ", " +
                            std::to_string((long long)pipe.bytesPerRow) + " B/row]");
     consume(o->parent, o);
     finishPipeline();

@@ -21,7 +21,8 @@ void Walker::collectAccumulators(OpNode* o) {
                 ac.key = "SUM" + structuralKey(s->child); ac.input = eg.emit(s); ac.merge = 0; ac.inputExpr = s->child; break;
             case RSQ_E_MIN: case RSQ_E_MAX:
                 if (s->type.tag != RSQ_DECIMAL && s->type.tag != RSQ_BIGINT && s->type.tag != RSQ_DATE)
-                    failType("LESS_THAN code generation not implemented for datatype");
+                    // (the reference's own words: its MIN update emits a LESS_THAN, its MAX update emitGreaterThan, which says ADD)
+                    failType(s->tag == RSQ_E_MAX ? "ADD code generation not implemented for datatype" : "LESS_THAN code generation not implemented for datatype");
                 ac.key = std::string(s->tag == RSQ_E_MIN ? "MIN" : "MAX") + structuralKey(s->child);
                 ac.input = "((i64)(" + eg.emit(s) + "))"; ac.merge = s->tag == RSQ_E_MIN ? 2 : 3; ac.inputExpr = s->child; break;
             default: failType("Aggregation type not implemented in updateAggregates(..).");
@@ -56,7 +57,8 @@ bool Walker::tryDenseKeys(OpNode* o) {
         if (c.type.isString()) return false;               // string keys: generic hash aggregation (bytes as key words)
         DenseKey k; k.expr = g; k.type = c.type;
         // (an empty SHARD of a table plans with the statistics of the whole table, like every other shard: Table::nRowsTotal)
-        if (t->nRows == 0 && !c.stats.valid) { k.card = 1; k.min = 0; }      // empty input: no row reaches the aggregation
+        if (t->nRows == 0 && !c.stats.valid && !t->derived) { k.card = 1; k.min = 0; }      // empty input: no row reaches the aggregation
+                                                                                        // (a derived table's rows are known only at execution)
         else if (!c.stats.valid) return false;
         else if (!c.stats.distinctBytes.empty()) { k.byteSet = true; k.values = c.stats.distinctBytes; k.card = (int64_t)k.values.size(); }
         else {

@@ -101,7 +101,9 @@ void defineAndDerive(Query& q, OpNode* o) {
 // whole table's (everything that replays the reference: its table sizes decide the emission order)
 uint64_t opSize(OpNode* o, bool local) {
     switch (o->tag) {
-        case RSQ_OP_SCAN: return (uint64_t)(local ? o->table->nRows : o->table->totalRows());      // a shard sizes like the table it is a range of (Table::nRowsTotal)
+        case RSQ_OP_SCAN:
+            if (o->table->derived) return o->table->derivedEstimate;      // the replaced aggregation's estimate, not the rows it gave
+            return (uint64_t)(local ? o->table->nRows : o->table->totalRows());      // a shard sizes like the table it is a range of (Table::nRowsTotal)
         case RSQ_OP_SELECTION: return opSize(o->child[0], local) / 2;
         case RSQ_OP_PROJECTION: case RSQ_OP_ORDERBY: return opSize(o->child[0], local);
         case RSQ_OP_HASHJOIN: return opSize(o->child[0], local) + opSize(o->child[1], local) / 2;
@@ -123,6 +125,7 @@ uint64_t opSize(OpNode* o, bool local) {
 Query::~Query() {
     if (bgCompiler.joinable()) bgCompiler.join();
     for (NljState& n : nljs) for (void* p : n.dCols) ctx.free(p);
+    for (DerivedState& d : derived) { for (void* p : d.dCols) ctx.free(p); if (d.dTuples) ctx.free(d.dTuples); }
     destroyTailState(tailState);
     if (dtArena.dev || dtArena.pinned) {
         // the arenas go back to the context for the next query, unless it already holds a pair
@@ -305,6 +308,7 @@ static std::string planMemoKey(const Query& q) {
 static void applyPlanMemo(Query& q) {
     Context& ctx = q.ctx;
     if (ctx.planMemoOff || ctx.device < 0 || q.genericActive) return;
+    if (!q.derived.empty()) return;          // (what this query learns depends on the derived tables' rows: no memo entry, no key)
     q.memoKey = planMemoKey(q);
     auto it = ctx.planMemo.find(q.memoKey);
     if (it == ctx.planMemo.end()) return;
@@ -430,6 +434,102 @@ static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& 
     n.inner.reset(compileQuery(q.ctx, sub, tables, nTables));
 }
 
+// Derived aggregations (engine_internal.h DerivedState): every AGGREGATION with an ancestor other than PROJECTION / MATERIALIZE / ORDERBY
+// and no such aggregation above it is cut out as a sub-query - MATERIALIZE over its subtree, every attribute, no limit - which compiles the
+// aggregations below it the same way.  The node becomes a scan of the derived table.
+static bool isDerivedAggregation(const OpNode* o) {
+    if (o->tag != RSQ_OP_AGGREGATION) return false;
+    for (const OpNode* a = o->parent; a; a = a->parent)
+        if (a->tag != RSQ_OP_PROJECTION && a->tag != RSQ_OP_MATERIALIZE && a->tag != RSQ_OP_ORDERBY) return true;
+    return false;
+}
+
+static std::string derivedName(const std::vector<Expr*>& groups) {
+    std::string g;
+    for (Expr* e : groups) g += (g.empty() ? "" : ", ") + expressionName(e);
+    return "the derived aggregation grouped by [" + g + "]";
+}
+
+static void compileDerived(Query& q, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
+    std::vector<int> cut;
+    for (int i = 0; i < plan.n_ops; i++) {
+        OpNode* o = q.ops[(size_t)i].get();
+        if (!isDerivedAggregation(o)) continue;
+        if (!q.nljs.empty()) failUnsupported(derivedName(o->exprs2) + ": a derived aggregation inside a nested-loops plan");
+        bool top = true;
+        for (OpNode* a = o->parent; a; a = a->parent) if (isDerivedAggregation(a)) top = false;      // (that one's sub-query cuts this one)
+        if (top) cut.push_back(i);
+    }
+    for (int i : cut) {
+        OpNode* o = q.ops[(size_t)i].get();
+        DerivedState d;
+        d.op = o; d.groups = o->exprs2; d.aggs = o->exprs;
+        const uint64_t estimate = opSize(o);      // (operators above size their tables from it, as the reference's do)
+        std::vector<rsq_op> ops;
+        std::function<int(int)> copy = [&](int k) -> int {
+            rsq_op c = plan.ops[k];
+            for (int j = 0; j < 2; j++) if (c.child[j] >= 0) c.child[j] = copy(c.child[j]);
+            ops.push_back(c);
+            return (int)ops.size() - 1;
+        };
+        const int agg = copy(i);
+        rsq_op m;
+        memset(&m, 0, sizeof m);
+        m.tag = RSQ_OP_MATERIALIZE; m.child[0] = agg; m.child[1] = -1; m.table = -1;
+        ops.push_back(m);
+        rsq_plan_desc sub = plan;
+        sub.ops = ops.data(); sub.n_ops = (int32_t)ops.size(); sub.root = (int32_t)ops.size() - 1;
+        sub.request_all = 1; sub.has_limit = 0; sub.limit = 0;
+        d.sub.reset(compileQuery(q.ctx, sub, tables, nTables));
+        Query& s = *d.sub;
+        if (s.agg == nullptr) failInvalid("derived aggregation without an aggregation");
+        // mergeAverages names an AVG when the aggregation's rows are made (tail.cpp): its id is taken now, so that the counter this
+        // query continues from (Walker::produceScan) has counted it
+        for (Expr* a : s.agg->exprs) if (a->tag == RSQ_E_AVG) s.pool.addId(a);
+        d.table.reset(new Table());
+        Table& t = *d.table;
+        t.ctx = &q.ctx; t.derived = true; t.derivedEstimate = estimate;
+        t.name = "derived" + std::to_string(q.derived.size());
+        for (Expr* g : d.groups) { TableColumn c; c.type = g->type; t.cols.push_back(c); }
+        for (Expr* a : d.aggs) { TableColumn c; c.type = a->type; t.cols.push_back(c); }
+        if (t.cols.size() > 32) failUnsupported(derivedName(d.groups) + " has more than 32 columns");
+        for (auto& c : t.cols) (void)columnWidth(c.type);
+        // the node is a scan from now on (DerivedState keeps its expressions: they name the columns)
+        o->tag = RSQ_OP_SCAN; o->nChildren = 0; o->child[0] = o->child[1] = nullptr; o->table = &t;
+        o->exprs.clear(); o->exprs2.clear(); o->splitAgg.clear();
+        o->derived = (int)q.derived.size();
+        q.derived.push_back(std::move(d));
+    }
+}
+
+// The reference numbers expressions with one counter in produce order, and the derived aggregation's subtree is produced where its scan
+// now stands: the sub-query's names continue this query's counter from here (the `exprN` of an aggregate above it, the fixtures'
+// #schema lines), and the columns take the names this query knows the aggregation's outputs by.
+void nameDerivedColumns(Query& q, OpNode* scan) {
+    DerivedState& d = q.derived[(size_t)scan->derived];
+    if (d.named) return;
+    d.named = true;
+    Query& s = *d.sub;
+    const size_t base = (size_t)q.pool.exprIdGen - 1;
+    for (size_t i = 0; i < q.exprs.size() && i < s.exprs.size(); i++)
+        if (s.exprs[i]->id != 0 && q.exprs[i]->id == 0) q.exprs[i]->id = s.exprs[i]->id + base;
+    q.pool.exprIdGen += s.pool.exprIdGen - 1;                       // (both counters start at 1)
+    Table& t = *d.table;
+    size_t k = 0;
+    for (Expr* g : d.groups) t.cols[k++].name = expressionName(g);
+    for (Expr* a : d.aggs) t.cols[k++].name = expressionName(a);
+}
+
+void refuseDerived(const Query& q, const std::string& what) {
+    failUnsupported(what + " of a plan with " + derivedName(q.derived.at(0).groups) + " (" + q.derived[0].table->name + "): only whole executions on one context run derived tables");
+}
+
+bool queryHasDerived(const Query& q) {
+    if (!q.derived.empty()) return true;
+    for (const NljState& n : q.nljs) if (n.inner && queryHasDerived(*n.inner)) return true;
+    return false;
+}
+
 Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
     double t0 = nowMs();
     std::unique_ptr<Query> q(new Query(ctx));
@@ -445,6 +545,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     q->exprs = q->pool.build(plan);
     buildOps(*q, plan);
     defineAndDerive(*q, q->root);
+    compileDerived(*q, plan, tables, nTables);
     // (a join in the left subtree of another one belongs to that one's inner query, which compiles it itself)
     for (NljState& n : q->nljs) {
         bool inInner = false;
@@ -552,6 +653,15 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
         d << "] (word = block * groups + group)";
         q->explainText += d.str() + "\n";
     }
+    for (size_t i = 0; i < q->derived.size(); i++) {
+        const DerivedState& d = q->derived[i];
+        std::string cols;
+        for (auto& c : d.table->cols) cols += (cols.empty() ? "" : "|") + c.name + ":" + serializeType(c.type);
+        q->explainText += "derived table " + d.table->name + " (" + derivedName(d.groups).substr(4) + ", estimate " + std::to_string(d.table->derivedEstimate) +
+                          " rows, columns " + cols + ", row count and addresses bound per execution) from its sub-query:\n";
+        std::istringstream in(d.sub->explainText);
+        for (std::string l; std::getline(in, l);) q->explainText += "  | " + l + "\n";
+    }
     if (ctx.device >= 0) {
         if (denseMode(*q)) prepareDenseBuffers(*q);
         for (auto& p : q->pipelines) if (p.partitioned) prepareStageBuffers(*q, p);
@@ -657,6 +767,7 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
     for (size_t i = 0; i < q.tables.size() && i < q.tableLayouts.size(); i++)
         if (q.tables[i]->layoutVersion != q.tableLayouts[i])
             throw Error(RSQ_ERR_INVALID, "rows were appended to table " + q.tables[i]->name + " after this statement was compiled: compile it again");
+    if ((partialOnly || async) && !q.derived.empty()) refuseDerived(q, "partial / asynchronous execution");
     executeQueryBody(q, partialOnly, async);
     keepKeyIndexes(q);
     rememberPlan(q);
@@ -752,6 +863,64 @@ void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<vo
     }
 }
 
+// The derived tables (DerivedState), in front of this query's pipelines at every execution: the host may have rewritten adopted input
+// columns in place, so nothing is kept from the previous one.  Each sub-query runs (its own derived tables first), then the writer turns
+// its packed tuples into the table's columns - read where the device tail left them, or uploaded once from the host tail's - and the
+// scan's row count and column addresses are bound (engine_pipelines.cpp argValue).
+static void prepareDerived(Query& q) {
+    Context& ctx = q.ctx;
+    for (DerivedState& d : q.derived) {
+        Query& s = *d.sub;
+        executeQuery(s, false);
+        q.report.num_kernels += s.report.num_kernels;
+        q.report.bytes_read += s.report.bytes_read;
+        Table& t = *d.table;
+        if (s.resultSchema.size() != t.cols.size()) failRuntime("internal error: " + t.name + " has " + std::to_string(t.cols.size()) +
+                                                                 " columns, its sub-query gave " + std::to_string(s.resultSchema.size()));
+        std::vector<DerivedColumn> cols;
+        int off = 0;
+        for (size_t c = 0; c < t.cols.size(); c++) {
+            if (!equalTypes(s.resultSchema[c].type, t.cols[c].type)) failRuntime("internal error: column " + std::to_string(c) + " of " + t.name + " changed its type");
+            cols.push_back({off, columnWidth(t.cols[c].type), nullptr});
+            off += sizeInTuple(t.cols[c].type, true);
+        }
+        const int tupleSize = off;
+        const int64_t n = s.resultRows;
+        if (n > d.capacity || d.dCols.empty()) {
+            for (void* p : d.dCols) ctx.free(p);
+            d.dCols.clear();
+            d.capacity = std::max<int64_t>(n + n / 8, 64);
+            for (auto& c : t.cols) d.dCols.push_back(ctx.alloc((size_t)d.capacity * (size_t)columnWidth(c.type)));
+        }
+        for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.dCols[c]; t.cols[c].dptr = d.dCols[c]; }
+        const uint8_t* tuples = s.resultInPinned ? s.resultDev : nullptr;
+        if (tuples) {      // (the device tail's layout must be the one the writer decodes)
+            const int devTuple = tuples == s.dtRows ? s.dtTupleSize : s.rtTupleSize;
+            if (devTuple != tupleSize) failRuntime("internal error: the device tail of " + t.name + " made " + std::to_string(devTuple) +
+                                                   "-byte tuples, the derived table's columns take " + std::to_string(tupleSize));
+        }
+        if (n > 0 && !tuples) {
+            const size_t bytes = (size_t)n * (size_t)tupleSize;
+            if ((int64_t)bytes > d.tupleCapacity) {
+                if (d.dTuples) ctx.free(d.dTuples);
+                d.tupleCapacity = (int64_t)(bytes + bytes / 8);
+                d.dTuples = ctx.alloc((size_t)d.tupleCapacity);
+            }
+            const uint8_t* host = s.resultInPinned ? s.resultPinned : s.resultTuples.data();
+            RSQ_HIP(hipMemcpyAsync(d.dTuples, host, bytes, hipMemcpyHostToDevice, ctx.stream));
+            tuples = (const uint8_t*)d.dTuples;
+        }
+        if (n > 0) {
+            derivedColumns(ctx, tuples, n, tupleSize, cols);
+            q.report.num_kernels += 1;
+            q.report.bytes_read += (uint64_t)n * (uint64_t)tupleSize;
+        }
+        t.nRows = n;
+        if (getenv("RSQ_TRACE"))
+            fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", t.name.c_str(), (long long)n, s.resultInPinned && s.resultDev ? "device" : "host");
+    }
+}
+
 static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     Context& ctx = q.ctx;
     if (ctx.device < 0) throw Error(RSQ_ERR_DEVICE, "this context has no device (compile-only)");
@@ -766,6 +935,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
+    if (!q.derived.empty()) prepareDerived(q);          // (the interpreters decline plans over derived tables: generic*.cpp)
     // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
     if (!q.nljs.empty() && !q.nljExternal) prepareNestedLoops(q);
     else if (q.nljExternal) {                        // (multi.cpp ran and bound the inner side: its work is part of this execution's)
@@ -1566,6 +1736,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
 
 void finalizeQuery(Query& q) {
     Context& ctx = q.ctx;
+    if (!q.derived.empty()) refuseDerived(q, "finalize");
     if (!denseMode(q)) failUnsupported("partial execution / finalize is available for dense aggregations only");
     RSQ_HIP(hipSetDevice(ctx.device));
     double t1 = nowMs();
@@ -1716,6 +1887,7 @@ bool shardGroupsDisjoint(const std::vector<Query*>& parts, std::string& why) {
 }
 
 void finalizeQueryHost(Query& q, const int64_t* words, size_t nWords) {
+    if (!q.derived.empty()) refuseDerived(q, "finalize");
     if (!denseMode(q)) failUnsupported("host finalize is available for dense aggregations only");
     size_t need = q.accums.size() * (size_t)q.denseGroups;
     if (nWords != need) failInvalid("partial table has " + std::to_string(nWords) + " words, expected " + std::to_string(need));

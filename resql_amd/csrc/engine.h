@@ -61,6 +61,9 @@ struct Table {
     uint64_t layoutVersion = 0;                // counts the times the columns MOVED (rsq_table_append allocates them anew): a statement compiled
                                                // before holds the old addresses and is refused (engine.cpp executeQuery)
     std::string name;
+    bool derived = false;                      // the rows of a derived aggregation (engine_internal.h DerivedState): no statistics, rows and
+                                               // column addresses bound per execution
+    uint64_t derivedEstimate = 0;              // ... and the getSize() of the aggregation it replaces (engine.cpp opSize)
     int64_t nRows = 0;
     int64_t row0 = 0;                          // global index of the first row (row-range shards)
     // A shard of a larger table plans as that table: rsq_table_unify_shard_stats / rsq_multi_query_compile give every shard the row
@@ -303,6 +306,9 @@ struct RowTailCol { int32_t kind, a, b, width, offset, len; };      // kind 0: t
 struct RowTailCols { int32_t n; RowTailCol c[24]; };
 void rowTailFirstKeys(Context& ctx, const int64_t* rows, int stride, int64_t n, uint64_t* keys, uint32_t* idx);
 void rowTailHashes(Context& ctx, const int64_t* rows, int stride, const uint32_t* idx, int64_t n, const RowTailKeys& keys, uint64_t* hashes);
+// derived tables: packed tuples (device memory) -> one column per attribute at columnWidth (aot_kernels.hip k_derived_columns)
+struct DerivedColumn { int32_t offset, width; void* out; };
+void derivedColumns(Context& ctx, const uint8_t* tuples, int64_t nRows, int tupleSize, const std::vector<DerivedColumn>& cols);
 void rowTailResultRows(Context& ctx, const int64_t* rows, int stride, const uint32_t* idx, const uint32_t* order, int64_t nRows, const RowTailCols& cols,
                        int tupleSize, uint8_t* out);
 
@@ -345,6 +351,8 @@ void setNestedLoopsExternal(Query& q, const Table* gathered);
 void nestedLoopsRunInner(Query& q, bool run, int64_t* rows, uint64_t* kernels, uint64_t* bytes);
 void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows);
 void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths);
+bool queryHasDerived(const Query& q);                   // the plan has a derived aggregation (engine_internal.h DerivedState)
+[[noreturn]] void refuseDerived(const Query& q, const std::string& what);      // RSQ_ERR_UNSUPPORTED naming the plan's derived aggregation
 bool queryAsyncCapable(const Query& q);                 // every pipeline can be enqueued without the host in between
 bool queryIsDense(const Query& q);              // its aggregation ends in a dense partial table ([min | max | sum] words)
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr);

@@ -114,6 +114,7 @@ double runDenseDeviceTail(Query& q) {
     phase("packed tuples (device), read back");
     q.resultRows = emit;
     q.resultInPinned = true;
+    q.resultDev = q.dtRows;
     return nowMs() - tTail0;
 }
 
@@ -210,6 +211,7 @@ double runRowsDeviceTail(Query& q, int64_t n) {
     q.resultRows = rowsOut;
     q.resultPinned = (uint8_t*)q.rtPinned;
     q.resultInPinned = true;
+    q.resultDev = q.rtSorts ? nullptr : rows;      // (sorted on the host: the device's tuples are not the result's order)
     return nowMs() - t0;
 }
 

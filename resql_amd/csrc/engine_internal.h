@@ -34,6 +34,7 @@ struct OpNode {
     Schema schema;                   // RelOperator::_schema
     int hashTable = -1;              // HASHJOIN: index into Query::hashTables
     int nlj = -1;                    // NESTEDLOOPSJOIN: index into Query::nljs
+    int derived = -1;                // SCAN of a derived table (a derived aggregation cut out of the plan): index into Query::derived
 };
 
 // ---- device hash table (join build side; optionally carries aggregates "at the entry") ----------
@@ -280,6 +281,22 @@ struct NljState {
     uint64_t innerKernels = 0, innerBytes = 0;      // what the inner side's own execution launched and read
 };
 
+// A derived aggregation: an AGGREGATION with an ancestor other than PROJECTION / MATERIALIZE / ORDERBY (aggregation.h:298-343 hands its
+// groups to whatever parent it has).  Its subtree is a query of its own (MATERIALIZE over it, every attribute, no limit), and the node is
+// replaced by a scan of the derived table: the sub-query's rows - group values, then aggregates, AVG merged - in the reference's emission
+// order, one device column per attribute at columnWidth (strings by value).  The sub-query runs in front of this query's pipelines at
+// every execution; the writer kernel (aot_kernels.hip k_derived_columns) turns its packed tuples into the columns.
+struct DerivedState {
+    OpNode* op = nullptr;            // the scan that stands where the aggregation stood
+    std::vector<Expr*> groups, aggs; // the aggregation's expressions in this query (their names are the derived table's column names)
+    std::unique_ptr<Query> sub;
+    std::unique_ptr<Table> table;    // columns without statistics; nRows and column addresses are set per execution
+    std::vector<void*> dCols;        // [capacity] per column, from the context's arena
+    void* dTuples = nullptr;         // the host tail's tuples uploaded for the writer
+    int64_t capacity = 0, tupleCapacity = 0;
+    bool named = false;              // the walker has given this query's names to the columns
+};
+
 struct Query {
     Context& ctx;
     ExprPool pool;
@@ -294,6 +311,7 @@ struct Query {
     std::vector<Pipeline> pipelines;
     std::vector<std::unique_ptr<HashTable>> hashTables;
     std::vector<NljState> nljs;            // nested-loops joins (OpNode::nlj)
+    std::vector<DerivedState> derived;     // derived aggregations, innermost sub-queries inside theirs (OpNode::derived)
     // rsq_multi_*: the inner side of the top-level nested-loops join is run and bound by multi.cpp (nestedLoops* in engine.h) in front of
     // the execution, which then runs the outer side only.  `gatheredTables`: tables whose rows every shard sees through that inner side.
     bool nljExternal = false;
@@ -400,6 +418,7 @@ struct Query {
     void* dtReplayWork = nullptr; size_t dtReplayBytes = 0;           // work area of the replay on the device (0: host replay)
     uint64_t* hDtHashes = nullptr; uint32_t* hDtOrder = nullptr;      // pinned
     uint8_t* resultPinned = nullptr;       // pinned copy of the result tuples (device tail)
+    const uint8_t* resultDev = nullptr;    // ... and the device buffer they were written to (null: the host tail made the tuples)
     // ... of the group rows of a hash / join-entry aggregation (engine.cpp runRowsDeviceTail): buffers sized for rtCapacity rows
     int rowTail = -1;                      // -1 not analysed yet, 0 no, 1 yes
     RowTailKeys rtKeys{}; RowTailCols rtCols{}; int rtTupleSize = 0; int64_t rtLimitRows = -1; bool rtSorts = false;
@@ -481,6 +500,7 @@ void launchGenericAggregate(Context& ctx, const GenericProgram& prog, const Gene
                             int64_t denseGroups, int64_t tableWords);
 
 uint64_t opSize(OpNode* o, bool local = false);      // getSize() estimates of the reference's operators
+void nameDerivedColumns(Query& q, OpNode* scan);      // engine.cpp: the walker reaches the scan of a derived table
 
 inline double nowMs() {
     using namespace std::chrono;

@@ -44,6 +44,13 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
         size_t k = (size_t)atoi(a.name.c_str() + 1);
         return k < q.dMatCols.size() ? (uint64_t)(uintptr_t)q.dMatCols[k] : 0;
     }
+    if (p.src && p.src->derived) {                  // a derived table: its row count and columns are this execution's (engine.cpp prepareDerived)
+        if (a.name == "n_rows") return (uint64_t)p.src->nRows;
+        if (a.name.size() >= 2 && a.name[0] == 'c' && isdigit((unsigned char)a.name[1])) {
+            const size_t k = (size_t)atoi(a.name.c_str() + 1);
+            return k < p.cols.size() ? (uint64_t)(uintptr_t)p.src->cols[(size_t)p.cols[k]].dptr : 0;
+        }
+    }
     if (a.name.compare(0, 3, "nlj") == 0) {         // nested-loops join: the inner side's row count and bound columns (engine.cpp)
         const size_t us = a.name.find('_');
         const NljState& n = q.nljs[(size_t)atoi(a.name.c_str() + 3)];

@@ -372,6 +372,7 @@ void buildOne(Query& q, size_t pi, OpNode* scan, GenericProgram2& prog) {
 bool buildGenericPlan(Query& q, std::vector<GenericProgram2>& out, std::string& why) {
     out.clear();
     if (!q.nljs.empty()) { why = "a nested-loops join (the interpreters have no pair loop)"; return false; }
+    if (!q.derived.empty()) { why = "a derived table (the programs hold column addresses; a derived table's are bound per execution)"; return false; }
     try {
         if (q.hashTables.size() > G2_MAX_TABLES) throw Error(RSQ_ERR_UNSUPPORTED, "too many hash tables");
         std::vector<OpNode*> scans;

@@ -596,6 +596,8 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                         if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
                     }
         }
+        // (derived aggregations run on one context only: engine.cpp prepareDerived)
+        if (!mq->qs.empty() && queryHasDerived(*mq->qs[0])) refuseDerived(*mq->qs[0], "a multi-GPU compile (rsq_multi_query_compile)");
         mq->dense = queryIsDense(*mq->qs[0]);
         if (mq->dense) {
             // (with unified statistics every shard derives the same layout; anything else is a defect of this library, not of the data)

@@ -528,6 +528,7 @@ static void runTailOn(Query& q, Groups& G);
 void runTail(Query& q) {
     q.tailNeedsAllGroups = false;
     q.resultInPinned = false;
+    q.resultDev = nullptr;
     if (!q.agg) { runMaterializeTail(q); return; }
     const double t0 = nowMs();
     Groups& G = tailState(q).groups;
@@ -548,6 +549,7 @@ void runTail(Query& q) {
 void runTailMerged(Query& root, const std::vector<Query*>& parts) {
     root.tailNeedsAllGroups = false;
     root.resultInPinned = false;
+    root.resultDev = nullptr;
     root.candidateRun = false;
     if (!root.agg) {
         // materialize.h:78-220 appends in scan order: the parts' columns back to back, parts in shard order
