@@ -88,8 +88,10 @@ typedef struct rsq_config {
  * RSQ_ENGINE_NESTED_LOOPS (off by default) lets the context plan and execute nested-loops joins (planner.h:458-469: FROM lists whose
  * tables are not all linked by equalities; RSQ_OP_NESTEDLOOPSJOIN in a plan description).  Such a join costs outer x inner pairs, so
  * a host enables it explicitly and bounds it with rsq_config.nested_loops_max_pairs.  Without the flag those plans are refused
- * (RSQ_ERR_UNSUPPORTED) as before. */
-enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u };
+ * (RSQ_ERR_UNSUPPORTED) as before.
+ * RSQ_ENGINE_DERIVED_MULTI (off by default) lets a multi-GPU handle (rsq_multi_config.base) run plans with derived aggregations; see
+ * rsq_multi_* below.  It is a setting of multi-GPU handles only: rsq_ctx_create refuses it (one context runs such plans without it). */
+enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u, RSQ_ENGINE_DERIVED_MULTI = 8u };
 
 /* Semantics switches.  The default (0) computes what the reference's SOURCE specifies; a bit selects what its asmjit back end
  * actually executes where the two differ, for a drop-in host that must return the JIT's own answers:
@@ -381,7 +383,21 @@ void rsq_db_destroy(rsq_db* db);
  *   - any other sharded table (a build side, a second inner table, one under a nested inner side): RSQ_ERR_UNSUPPORTED naming it.
  * rsq_config.nested_loops_max_pairs bounds the statement: total outer rows x total inner rows, checked after the gather and before
  * any outer pipeline runs.  The report counts the inner sides' kernels and bytes, rsq_multi_query_collective_ms includes the gather,
- * rsq_multi_query_merge_name states the split ("nested-loops: outer rows over N shards, inner side gathered (...)" / "replicated"). */
+ * rsq_multi_query_merge_name states the split ("nested-loops: outer rows over N shards, inner side gathered (...)" / "replicated").
+ *
+ * Derived aggregations (an aggregation below a selection, a join or another aggregation; base->engine_flags has RSQ_ENGINE_DERIVED_MULTI;
+ * without it rsq_multi_query_compile refuses them, RSQ_ERR_UNSUPPORTED).  Every derived table is built on every shard before the plan's
+ * pipelines run, innermost first, and equals the one-context table over the whole tables (rows, emission order, AVG, CHAR spelling):
+ *   - local: every table its sub-query reads is replicated (a derived table below counts as replicated) - each shard computes it;
+ *   - merged: exactly one of them is sharded and it is the source of the sub-query's aggregating pipeline - the shards' groups are
+ *     merged on the root (on the device with peer copies where one context would take its device tail, else on the host) and the
+ *     table goes to every shard;
+ *   - any other sharded table under a derived aggregation, or a sharded build side of the plan: RSQ_ERR_UNSUPPORTED naming it.
+ * A derived table that the plan's last pipeline scans is scanned slice by slice (rsq_multi_shard_rows of its rows); elsewhere every
+ * shard holds it whole.  The other tables keep the contract above: the last pipeline's ordinary source is the caller's shard.  Plans with
+ * both a nested-loops join and a derived aggregation are refused.  The report counts every shard's sub-queries, the collective time
+ * includes the exchanges, and rsq_multi_query_merge_name states the split ("derived0 merged on the device over 3 shards (B bytes),
+ * sliced", "derived0 local, whole"). */
 enum rsq_merge_mode { RSQ_MERGE_AUTO = 0, RSQ_MERGE_RCCL = 1, RSQ_MERGE_PEER_COPY = 2 };
 typedef struct rsq_multi_config {
     uint32_t struct_size;       /* sizeof(rsq_multi_config) of the header the host was compiled against (as rsq_config.struct_size) */

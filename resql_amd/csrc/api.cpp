@@ -60,7 +60,7 @@ Table* makeTable(Context& ctx, const rsq_table_desc& d, bool adopt) {
 
 // rsq_config as the host's header declared it: struct_size bytes are the host's, everything behind them reads as 0
 namespace rsq {
-rsq_config readConfig(const rsq_config* cfg) {
+rsq_config readConfig(const rsq_config* cfg, bool multiBase) {
     rsq_config c{};
     c.struct_size = (uint32_t)sizeof(rsq_config);
     if (!cfg) return c;
@@ -71,7 +71,9 @@ rsq_config readConfig(const rsq_config* cfg) {
     c.struct_size = (uint32_t)sizeof(rsq_config);
     if (c.emission_order != RSQ_EMIT_REFERENCE && c.emission_order != RSQ_EMIT_ANY) failInvalid("rsq_config.emission_order must be RSQ_EMIT_REFERENCE (0) or RSQ_EMIT_ANY (1)");
     if (c.compat_flags & ~(uint32_t)RSQ_COMPAT_JIT_INT16_CAST) failInvalid("rsq_config.compat_flags has bits this library does not know");
-    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO | RSQ_ENGINE_NESTED_LOOPS)) failInvalid("rsq_config.engine_flags has bits this library does not know");
+    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO | RSQ_ENGINE_NESTED_LOOPS | RSQ_ENGINE_DERIVED_MULTI)) failInvalid("rsq_config.engine_flags has bits this library does not know");
+    if ((c.engine_flags & RSQ_ENGINE_DERIVED_MULTI) && !multiBase)
+        failInvalid("rsq_config.engine_flags has RSQ_ENGINE_DERIVED_MULTI, a setting of multi-GPU handles (rsq_multi_config.base) only");
     if (c.nested_loops_max_pairs < 0) failInvalid("rsq_config.nested_loops_max_pairs is negative (0: the default of 2^36 pairs)");
     if (c.nested_loops_max_pairs == 0) c.nested_loops_max_pairs = (int64_t)1 << 36;
     return c;

@@ -265,6 +265,143 @@ void rowTailResultRows(Context& ctx, const int64_t* rows, int stride, const uint
     RSQ_HIP(hipGetLastError());
 }
 
+// ---- the group rows of several shards merged by key (a derived table across GPUs, engine_derived_multi.cpp) ----------------------------
+// The device form of tail.cpp mergeEqualGroups.  Rows [first row | table words | accumulator blocks] of all shards, back to back:
+//   k_gm_insert    one open-addressing table of 2^k >= 2n slots, a slot = (32 hash bits << 32 | row index), claimed with a 64-bit CAS;
+//                  a row whose key equals the slot's row takes that row as its owner.  Keys compare as mergeEqualGroups normalises them:
+//                  INT / DATE by their 32 bits, BOOL / CHAR(1) by their byte, CHAR(n) without trailing spaces, VARCHAR up to its NUL.
+//                  A probe that meets no free slot in `cap` steps sets bit 2 of the error word ("Hash table full") and stops.
+//   k_gm_merge     every other member merges its accumulators into the owner's row: wrapping int64 sum, min, max (64-bit atomics),
+//                  and its first row into the owner's first-row word (min)
+//   k_gm_best      the member whose first row is the group's (first rows are row numbers over the whole table: one member)
+//   scan + k_gm_scatter   the owners' rows, in row order, with the table words (the key's spelling) of that member
+__device__ __forceinline__ int gm_str_len(const i64* w, int len, bool isChar) {
+    int n = 0;
+    while (n < len && row_str_byte(w, n) != 0) n++;
+    if (isChar) while (n > 0 && row_str_byte(w, n - 1) == ' ') n--;
+    return n;
+}
+__device__ u64 gm_hash(const i64* r, const GroupMergeSpec& s) {
+    u64 h = 0x9E3779B97F4A7C15ull;
+    for (int k = 0; k < s.keys.n; k++) {
+        const RowTailKey& key = s.keys.k[k];
+        if (key.len > 1) {
+            const int n = gm_str_len(r + key.word, key.len, key.typeTag == RSQ_CHAR);
+            for (int c = 0; c < n; c++) h = (h ^ (u64)(u8)row_str_byte(r + key.word, c)) * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (u64)n) * 0xBF58476D1CE4E5B9ull;
+        } else {
+            u64 x = (u64)r[key.word];
+            if (key.typeTag == RSQ_INT || key.typeTag == RSQ_DATE) x = (u64)(u32)x;
+            else if (key.typeTag == RSQ_BOOL || key.typeTag == RSQ_CHAR) x = (u64)(u8)x;
+            h = (h ^ x) * 0xBF58476D1CE4E5B9ull;
+        }
+        h ^= h >> 29;
+    }
+    return h;
+}
+__device__ bool gm_equal(const i64* a, const i64* b, const GroupMergeSpec& s) {
+    for (int k = 0; k < s.keys.n; k++) {
+        const RowTailKey& key = s.keys.k[k];
+        if (key.len > 1) {
+            const bool isChar = key.typeTag == RSQ_CHAR;
+            const int n = gm_str_len(a + key.word, key.len, isChar);
+            if (n != gm_str_len(b + key.word, key.len, isChar)) return false;
+            for (int c = 0; c < n; c++) if (row_str_byte(a + key.word, c) != row_str_byte(b + key.word, c)) return false;
+        } else {
+            const u64 x = (u64)a[key.word], y = (u64)b[key.word];
+            if (key.typeTag == RSQ_INT || key.typeTag == RSQ_DATE) { if ((u32)x != (u32)y) return false; }
+            else if (key.typeTag == RSQ_BOOL || key.typeTag == RSQ_CHAR) { if ((u8)x != (u8)y) return false; }
+            else if (x != y) return false;
+        }
+    }
+    return true;
+}
+__global__ void __launch_bounds__(256) k_gm_insert(const i64* __restrict__ rows, i64 n, GroupMergeSpec s, u64* __restrict__ slots, u64 mask,
+                                                   u32* __restrict__ owner, i64* __restrict__ first, u32* err) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+        const i64* r = rows + (size_t)i * (size_t)s.stride;
+        first[i] = r[0];
+        const u64 h = gm_hash(r, s);
+        const u64 tag = (h >> 32) << 32;
+        const u64 mine = tag | (u64)i;
+        u64 at = h & mask;
+        u32 own = 0xffffffffu;
+        for (u64 step = 0; step <= mask; step++, at = (at + 1) & mask) {
+            u64 cur = __hip_atomic_load(&slots[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == ~0ull) {
+                cur = atomicCAS(&slots[at], ~0ull, mine);
+                if (cur == ~0ull) { own = (u32)i; break; }
+            }
+            if ((cur & 0xffffffff00000000ull) == tag && gm_equal(rows + (size_t)(cur & 0xffffffffull) * (size_t)s.stride, r, s)) { own = (u32)(cur & 0xffffffffull); break; }
+        }
+        if (own == 0xffffffffu) { atomicOr(err, 2u); own = (u32)i; }
+        owner[i] = own;
+    }
+}
+__global__ void __launch_bounds__(256) k_gm_merge(i64* __restrict__ rows, i64 n, GroupMergeSpec s, const u32* __restrict__ owner, const i64* __restrict__ first) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+        const u32 o = owner[i];
+        if ((i64)o == i) continue;
+        const i64* src = rows + (size_t)i * (size_t)s.stride;
+        i64* dst = rows + (size_t)o * (size_t)s.stride;
+        for (int w = 0; w < s.nAcc; w++) {
+            const int at = s.accWord[w];
+            if (s.accKind[w] == 0) atomicAdd(reinterpret_cast<u64*>(dst + at), (u64)src[at]);      // (wrapping: the engine's int64 sum)
+            else if (s.accKind[w] == 2) atomicMin(dst + at, src[at]);
+            else atomicMax(dst + at, src[at]);
+        }
+        atomicMin(dst, first[i]);
+    }
+}
+__global__ void __launch_bounds__(256) k_gm_best(const i64* __restrict__ rows, i64 n, int stride, const u32* __restrict__ owner, const i64* __restrict__ first,
+                                                 u32* __restrict__ best, u32* __restrict__ flags) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i <= n; i += (i64)gridDim.x * blockDim.x) {
+        if (i == n) { flags[n] = 0u; continue; }      // (the scan's trailing slot)
+        const u32 o = owner[i];
+        if (first[i] == rows[(size_t)o * (size_t)stride]) best[o] = (u32)i;
+        flags[i] = (i64)o == i ? 1u : 0u;
+    }
+}
+__global__ void __launch_bounds__(256) k_gm_scatter(const i64* __restrict__ rows, i64 n, int stride, int nTab, const u32* __restrict__ owner,
+                                                    const u32* __restrict__ best, const u64* __restrict__ offs, i64* __restrict__ out) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+        if ((i64)owner[i] != i) continue;
+        const i64* r = rows + (size_t)i * (size_t)stride;
+        const i64* b = rows + (size_t)best[i] * (size_t)stride;
+        i64* d = out + (size_t)offs[i] * (size_t)stride;
+        for (int w = 0; w < stride; w++) d[w] = (w >= 1 && w <= nTab) ? b[w] : r[w];
+    }
+}
+size_t groupMergeTempBytes(int64_t n) {
+    uint64_t cap = 16; while (cap < (uint64_t)n * 2) cap <<= 1;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    return up((size_t)cap * 8) + up((size_t)n * 4) * 2 + up((size_t)n * 8) + up((size_t)(n + 1) * 4) + up((size_t)(n + 1) * 8) + up(scanTempBytes(n + 1));
+}
+void mergeGroupRows(Context& ctx, int64_t* rows, int64_t n, const GroupMergeSpec& spec, void* temp, int64_t* out, uint64_t* dCount) {
+    if (n <= 0) { RSQ_HIP(hipMemsetAsync(dCount, 0, 8, ctx.stream)); return; }
+    if (n >= (1ll << 31)) throw Error(RSQ_ERR_UNSUPPORTED, "more than 2^31 group rows in a merge across shards");
+    uint64_t cap = 16; while (cap < (uint64_t)n * 2) cap <<= 1;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    char* p = (char*)temp;
+    u64* slots = (u64*)p; p += up((size_t)cap * 8);
+    u32* owner = (u32*)p; p += up((size_t)n * 4);
+    u32* best = (u32*)p; p += up((size_t)n * 4);
+    i64* first = (i64*)p; p += up((size_t)n * 8);
+    u32* flags = (u32*)p; p += up((size_t)(n + 1) * 4);
+    u64* offs = (u64*)p; p += up((size_t)(n + 1) * 8);
+    void* scanTemp = p;
+    RSQ_HIP(hipMemsetAsync(slots, 0xff, (size_t)cap * 8, ctx.stream));
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 256) / 256));
+    hipLaunchKernelGGL(k_gm_insert, dim3(grid), dim3(256), 0, ctx.stream, (const i64*)rows, (i64)n, spec, slots, (u64)(cap - 1), owner, first, ctx.dErr);
+    hipLaunchKernelGGL(k_gm_merge, dim3(grid), dim3(256), 0, ctx.stream, (i64*)rows, (i64)n, spec, (const u32*)owner, (const i64*)first);
+    hipLaunchKernelGGL(k_gm_best, dim3(grid), dim3(256), 0, ctx.stream, (const i64*)rows, (i64)n, spec.stride, (const u32*)owner, (const i64*)first, best, flags);
+    exclusiveScanCounts(ctx, flags, (uint64_t*)offs, n + 1, scanTemp, scanTempBytes(n + 1));
+    hipLaunchKernelGGL(k_gm_scatter, dim3(grid), dim3(256), 0, ctx.stream, (const i64*)rows, (i64)n, spec.stride, spec.nTab, (const u32*)owner, (const u32*)best,
+                       (const u64*)offs, (i64*)out);
+    RSQ_HIP(hipMemcpyAsync(dCount, offs + n, 8, hipMemcpyDeviceToDevice, ctx.stream));
+    RSQ_HIP(hipGetLastError());
+}
+
 void densePresentGroups(Context& ctx, const int64_t* firstBlock, int64_t D, uint32_t* flags, uint64_t* offs, void* scanTemp, uint64_t* outFirst, uint32_t* outGid) {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (D + 256) / 256));
     hipLaunchKernelGGL(k_present_flags, dim3(grid), dim3(256), 0, ctx.stream, (const i64*)firstBlock, (i64)D, flags);

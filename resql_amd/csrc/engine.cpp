@@ -125,7 +125,7 @@ uint64_t opSize(OpNode* o, bool local) {
 Query::~Query() {
     if (bgCompiler.joinable()) bgCompiler.join();
     for (NljState& n : nljs) for (void* p : n.dCols) ctx.free(p);
-    for (DerivedState& d : derived) { for (void* p : d.dCols) ctx.free(p); if (d.dTuples) ctx.free(d.dTuples); }
+    for (DerivedState& d : derived) { for (void* p : d.dCols) ctx.free(p); if (d.dTuples) ctx.free(d.dTuples); if (d.dMerge) ctx.free(d.dMerge); }
     destroyTailState(tailState);
     if (dtArena.dev || dtArena.pinned) {
         // the arenas go back to the context for the next query, unless it already holds a pair
@@ -759,6 +759,13 @@ static bool fusedEligible(const Query& q) {
 // materialised columns) back, but leaves the tail to the root, which merges all shards' groups first (tail.cpp runTailMerged)
 static void tailUnlessHeld(Query& q) { if (!q.holdTail) runTail(q); }
 
+void fetchHeldGroupRows(Query& q) {
+    if (q.nGroupRows <= 0) return;
+    ensureHostGroupRows(q, (size_t)q.nGroupRows * (size_t)q.groupRowWords);
+    RSQ_HIP(hipSetDevice(q.ctx.device));
+    RSQ_HIP(hipMemcpy(q.hGroupRows, q.dGroupRows, (size_t)q.nGroupRows * (size_t)q.groupRowWords * 8, hipMemcpyDeviceToHost));
+}
+
 static void executeQueryBody(Query& q, bool partialOnly, bool async);
 void executeQuery(Query& q, bool partialOnly, bool async) {
     // rows appended to a table move its columns (rsq_table_append): the kernels' arguments of a statement compiled before point at memory
@@ -767,7 +774,7 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
     for (size_t i = 0; i < q.tables.size() && i < q.tableLayouts.size(); i++)
         if (q.tables[i]->layoutVersion != q.tableLayouts[i])
             throw Error(RSQ_ERR_INVALID, "rows were appended to table " + q.tables[i]->name + " after this statement was compiled: compile it again");
-    if ((partialOnly || async) && !q.derived.empty()) refuseDerived(q, "partial / asynchronous execution");
+    if ((partialOnly || async) && !q.derived.empty() && !(q.derivedExternal && !async)) refuseDerived(q, "partial / asynchronous execution");
     executeQueryBody(q, partialOnly, async);
     keepKeyIndexes(q);
     rememberPlan(q);
@@ -867,57 +874,67 @@ void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<vo
 // columns in place, so nothing is kept from the previous one.  Each sub-query runs (its own derived tables first), then the writer turns
 // its packed tuples into the table's columns - read where the device tail left them, or uploaded once from the host tail's - and the
 // scan's row count and column addresses are bound (engine_pipelines.cpp argValue).
-static void prepareDerived(Query& q) {
+// The writer for derived table `d` of `q`: `s`'s packed tuples (its own sub-query's, or the root's after a merge across shards) into
+// d's columns on q's context - read where the device tail left them (deviceTuples, same device), or uploaded once from the host's.
+void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, uint64_t* kernels, uint64_t* bytes) {
     Context& ctx = q.ctx;
+    Table& t = *d.table;
+    if (s.resultSchema.size() != t.cols.size()) failRuntime("internal error: " + t.name + " has " + std::to_string(t.cols.size()) +
+                                                             " columns, its sub-query gave " + std::to_string(s.resultSchema.size()));
+    std::vector<DerivedColumn> cols;
+    int off = 0;
+    for (size_t c = 0; c < t.cols.size(); c++) {
+        if (!equalTypes(s.resultSchema[c].type, t.cols[c].type)) failRuntime("internal error: column " + std::to_string(c) + " of " + t.name + " changed its type");
+        cols.push_back({off, columnWidth(t.cols[c].type), nullptr});
+        off += sizeInTuple(t.cols[c].type, true);
+    }
+    const int tupleSize = off;
+    const int64_t n = s.resultRows;
+    if (n > d.capacity || d.dCols.empty()) {
+        for (void* p : d.dCols) ctx.free(p);
+        d.dCols.clear();
+        d.capacity = std::max<int64_t>(n + n / 8, 64);
+        for (auto& c : t.cols) d.dCols.push_back(ctx.alloc((size_t)d.capacity * (size_t)columnWidth(c.type)));
+    }
+    for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.dCols[c]; t.cols[c].dptr = d.dCols[c]; }
+    const uint8_t* tuples = deviceTuples && s.resultInPinned ? s.resultDev : nullptr;
+    if (tuples) {      // (the device tail's layout must be the one the writer decodes)
+        const int devTuple = tuples == s.dtRows ? s.dtTupleSize : s.rtTupleSize;
+        if (devTuple != tupleSize) failRuntime("internal error: the device tail of " + t.name + " made " + std::to_string(devTuple) +
+                                               "-byte tuples, the derived table's columns take " + std::to_string(tupleSize));
+    }
+    if (n > 0 && !tuples) {
+        const size_t b = (size_t)n * (size_t)tupleSize;
+        if ((int64_t)b > d.tupleCapacity) {
+            if (d.dTuples) ctx.free(d.dTuples);
+            d.tupleCapacity = (int64_t)(b + b / 8);
+            d.dTuples = ctx.alloc((size_t)d.tupleCapacity);
+        }
+        const uint8_t* host = s.resultInPinned ? s.resultPinned : s.resultTuples.data();
+        RSQ_HIP(hipMemcpyAsync(d.dTuples, host, b, hipMemcpyHostToDevice, ctx.stream));
+        tuples = (const uint8_t*)d.dTuples;
+    }
+    if (n > 0) {
+        derivedColumns(ctx, tuples, n, tupleSize, cols);
+        *kernels += 1;
+        *bytes += (uint64_t)n * (uint64_t)tupleSize;
+    }
+    t.nRows = n; t.row0 = 0; t.nRowsTotal = -1;
+}
+
+// The derived tables (DerivedState), in front of this query's pipelines at every execution: the host may have rewritten adopted input
+// columns in place, so nothing is kept from the previous one.  Each sub-query runs (its own derived tables first), then the writer turns
+// its packed tuples into the table's columns and the scan's row count and column addresses are bound (engine_pipelines.cpp argValue).
+static void prepareDerived(Query& q) {
     for (DerivedState& d : q.derived) {
         Query& s = *d.sub;
         executeQuery(s, false);
         q.report.num_kernels += s.report.num_kernels;
         q.report.bytes_read += s.report.bytes_read;
-        Table& t = *d.table;
-        if (s.resultSchema.size() != t.cols.size()) failRuntime("internal error: " + t.name + " has " + std::to_string(t.cols.size()) +
-                                                                 " columns, its sub-query gave " + std::to_string(s.resultSchema.size()));
-        std::vector<DerivedColumn> cols;
-        int off = 0;
-        for (size_t c = 0; c < t.cols.size(); c++) {
-            if (!equalTypes(s.resultSchema[c].type, t.cols[c].type)) failRuntime("internal error: column " + std::to_string(c) + " of " + t.name + " changed its type");
-            cols.push_back({off, columnWidth(t.cols[c].type), nullptr});
-            off += sizeInTuple(t.cols[c].type, true);
-        }
-        const int tupleSize = off;
-        const int64_t n = s.resultRows;
-        if (n > d.capacity || d.dCols.empty()) {
-            for (void* p : d.dCols) ctx.free(p);
-            d.dCols.clear();
-            d.capacity = std::max<int64_t>(n + n / 8, 64);
-            for (auto& c : t.cols) d.dCols.push_back(ctx.alloc((size_t)d.capacity * (size_t)columnWidth(c.type)));
-        }
-        for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.dCols[c]; t.cols[c].dptr = d.dCols[c]; }
-        const uint8_t* tuples = s.resultInPinned ? s.resultDev : nullptr;
-        if (tuples) {      // (the device tail's layout must be the one the writer decodes)
-            const int devTuple = tuples == s.dtRows ? s.dtTupleSize : s.rtTupleSize;
-            if (devTuple != tupleSize) failRuntime("internal error: the device tail of " + t.name + " made " + std::to_string(devTuple) +
-                                                   "-byte tuples, the derived table's columns take " + std::to_string(tupleSize));
-        }
-        if (n > 0 && !tuples) {
-            const size_t bytes = (size_t)n * (size_t)tupleSize;
-            if ((int64_t)bytes > d.tupleCapacity) {
-                if (d.dTuples) ctx.free(d.dTuples);
-                d.tupleCapacity = (int64_t)(bytes + bytes / 8);
-                d.dTuples = ctx.alloc((size_t)d.tupleCapacity);
-            }
-            const uint8_t* host = s.resultInPinned ? s.resultPinned : s.resultTuples.data();
-            RSQ_HIP(hipMemcpyAsync(d.dTuples, host, bytes, hipMemcpyHostToDevice, ctx.stream));
-            tuples = (const uint8_t*)d.dTuples;
-        }
-        if (n > 0) {
-            derivedColumns(ctx, tuples, n, tupleSize, cols);
-            q.report.num_kernels += 1;
-            q.report.bytes_read += (uint64_t)n * (uint64_t)tupleSize;
-        }
-        t.nRows = n;
+        writeDerivedFrom(q, d, s, true, &q.report.num_kernels, &q.report.bytes_read);
         if (getenv("RSQ_TRACE"))
-            fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", t.name.c_str(), (long long)n, s.resultInPinned && s.resultDev ? "device" : "host");
+            fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", d.table->name.c_str(), (long long)d.table->nRows,
+                    s.resultInPinned && s.resultDev ? "device" : "host");
     }
 }
 
@@ -935,7 +952,9 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
-    if (!q.derived.empty()) prepareDerived(q);          // (the interpreters decline plans over derived tables: generic*.cpp)
+    if (!q.derived.empty() && !q.derivedExternal) prepareDerived(q);          // (the interpreters decline plans over derived tables: generic*.cpp)
+    else if (q.derivedExternal)                     // (engine_derived_multi.cpp built and bound them: its work for this shard is this execution's)
+        for (const DerivedState& d : q.derived) { q.report.num_kernels += d.extKernels; q.report.bytes_read += d.extBytes; }
     // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
     if (!q.nljs.empty() && !q.nljExternal) prepareNestedLoops(q);
     else if (q.nljExternal) {                        // (multi.cpp ran and bound the inner side: its work is part of this execution's)
@@ -1715,7 +1734,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
                     q.hRowsView = nullptr;
                 }
                 else {
-                    if (q.nGroupRows) {
+                    if (q.nGroupRows && !(q.holdTail && q.holdTailOnDevice)) {
                         ensureHostGroupRows(q, (size_t)q.nGroupRows * (size_t)q.groupRowWords);
                         RSQ_HIP(hipMemcpy(q.hGroupRows, q.dGroupRows, (size_t)q.nGroupRows * rowBytes, hipMemcpyDeviceToHost));
                     }
@@ -1736,7 +1755,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
 
 void finalizeQuery(Query& q) {
     Context& ctx = q.ctx;
-    if (!q.derived.empty()) refuseDerived(q, "finalize");
+    if (!q.derived.empty() && !q.derivedExternal) refuseDerived(q, "finalize");
     if (!denseMode(q)) failUnsupported("partial execution / finalize is available for dense aggregations only");
     RSQ_HIP(hipSetDevice(ctx.device));
     double t1 = nowMs();
@@ -1864,6 +1883,11 @@ bool shardGroupsDisjoint(const std::vector<Query*>& parts, std::string& why) {
         for (size_t i = 0; i < parts.size() && usable; i++) {
             const Table* tab = nullptr; int col = -1;
             for (Table* t : parts[i]->tables) { int c = t->findCol(g->symbol); if (c >= 0) { tab = t; col = c; break; } }
+            for (const DerivedState& d : parts[i]->derived)
+                if (d.table->findCol(g->symbol) >= 0) {
+                    // (its columns have no statistics, and a merged or local derived table holds the same groups on every shard)
+                    why = "group key " + g->symbol + " comes from a derived table"; tab = nullptr; break;
+                }
             if (!tab) { usable = false; break; }
             if (std::find(parts[i]->gatheredTables.begin(), parts[i]->gatheredTables.end(), tab) != parts[i]->gatheredTables.end()) {
                 // (the gathered inner side of a nested-loops join: every shard pairs with ALL of its rows, whatever its own rows hold)

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <tuple>
 #include <memory>
@@ -190,7 +191,7 @@ struct Context {
     bool planMemoOff = false;
 };
 
-rsq_config readConfig(const rsq_config* cfg);      // api.cpp: the host's struct (struct_size bytes), validated
+rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // api.cpp: the host's struct (struct_size bytes), validated
 inline bool jitInt16Cast(const Context& c) { return (c.cfg.compat_flags & RSQ_COMPAT_JIT_INT16_CAST) != 0; }
 
 // launch helper: kernel takes one struct of 8-byte slots by value
@@ -306,6 +307,11 @@ struct RowTailCol { int32_t kind, a, b, width, offset, len; };      // kind 0: t
 struct RowTailCols { int32_t n; RowTailCol c[24]; };
 void rowTailFirstKeys(Context& ctx, const int64_t* rows, int stride, int64_t n, uint64_t* keys, uint32_t* idx);
 void rowTailHashes(Context& ctx, const int64_t* rows, int stride, const uint32_t* idx, int64_t n, const RowTailKeys& keys, uint64_t* hashes);
+// group rows of several shards merged by key on one device (devtail.hip k_gm_*): `rows` [n][stride] are merged in place, the groups land in
+// `out` [count][stride] in row order, the count (u64) in *dCount.  `temp` holds groupMergeTempBytes(n).
+struct GroupMergeSpec { int32_t stride, nTab, nAcc, pad; RowTailKeys keys; int32_t accWord[32], accKind[32]; };
+size_t groupMergeTempBytes(int64_t n);
+void mergeGroupRows(Context& ctx, int64_t* rows, int64_t n, const GroupMergeSpec& spec, void* temp, int64_t* out, uint64_t* dCount);
 // derived tables: packed tuples (device memory) -> one column per attribute at columnWidth (aot_kernels.hip k_derived_columns)
 struct DerivedColumn { int32_t offset, width; void* out; };
 void derivedColumns(Context& ctx, const uint8_t* tuples, int64_t nRows, int tupleSize, const std::vector<DerivedColumn>& cols);
@@ -353,6 +359,14 @@ void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows);
 void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths);
 bool queryHasDerived(const Query& q);                   // the plan has a derived aggregation (engine_internal.h DerivedState)
 [[noreturn]] void refuseDerived(const Query& q, const std::string& what);      // RSQ_ERR_UNSUPPORTED naming the plan's derived aggregation
+// Derived aggregations across shards (engine_derived_multi.cpp; engine.cpp prepareDerived is the one-context form).  `qs`: one compiled
+// query per shard, same plan; `tables` [shard][nTables]; `sharded[t]`: table t's instances differ between the shards.  The plan step
+// decides every derived table's split (local / merged, sliced / whole) or refuses naming the table, and marks the queries so that
+// executeQuery leaves their derived tables to the run step, which builds them on every shard (innermost first).
+typedef std::function<void(const std::function<void(int)>&)> ShardThreads;     // runs f(shard) for every shard, on host threads
+struct DerivedMultiRun { int64_t exchangeBytes = 0; double exchangeMs = 0; std::string text; };
+std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* const* tables, int nTables, const std::vector<bool>& sharded);
+void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out);
 bool queryAsyncCapable(const Query& q);                 // every pipeline can be enqueued without the host in between
 bool queryIsDense(const Query& q);              // its aggregation ends in a dense partial table ([min | max | sum] words)
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr);

@@ -1,0 +1,363 @@
+// engine_derived_multi.cpp - derived aggregations across GPUs (rsq_multi_* with RSQ_ENGINE_DERIVED_MULTI; multi.cpp drives it).
+//
+// Every shard compiles the whole plan, so every shard has its own sub-query per derived table (engine.cpp compileDerived).  Each
+// derived table is split by the tables its sub-query reads ("sharded": a table whose instances differ between the shards):
+//   local   every table is replicated (a derived table below counts as replicated): each shard computes the whole table itself;
+//   merged  exactly one table is sharded, and it is the source of the sub-query's aggregating pipeline: each shard runs its sub-query up
+//           to its group rows (tail held back), and the groups are merged across shards into the table one context gives over the whole
+//           tables - the reference has ONE hash table all workers reach (aggregation.h:240-343, JitContextFlounder.h:459-487);
+//   anything else is refused, naming the table.
+// Merged, hash / join-entry groups: on the DEVICE path (where one context's sub-query would take its device tail) the shards' group rows
+// are gathered to the root in shard order with peer copies, merged by key in one device hash table (devtail.hip k_gm_*), and go through
+// the device tail's emission order; the root writes its columns and copies them (or each shard's slice) to the other shards.  On the
+// HOST path the root merges them with runTailMerged and every shard uploads the tuples and writes its own columns.  A dense sub-query
+// merges its partial tables on the root (mergePartialsAsync) and finalises there; its tuples then travel the same two ways.
+// Where the table lands: the source of the plan's last pipeline is scanned slice by slice (rsq_multi_shard_rows of its rows, the slice's
+// first row numbered over the whole table, bound at launch); any other place (a build side, an earlier pipeline's source) holds it whole.
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <map>
+
+#include "engine_internal.h"
+
+namespace rsq {
+
+namespace {
+
+enum { LOCAL = 1, MERGED = 2 };
+
+double wallMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+void scansOf(OpNode* o, std::vector<OpNode*>& out) {
+    if (!o) return;
+    if (o->tag == RSQ_OP_SCAN) { out.push_back(o); return; }
+    for (int k = 0; k < 2; k++) scansOf(o->child[k], out);
+}
+
+const Table* aggregatingSource(const Query& s) {
+    for (const Pipeline& p : s.pipelines) if (p.sink == SinkKind::AGGREGATE) return p.src;
+    return nullptr;
+}
+
+struct Planner {
+    std::map<const Table*, int> index;      // shard 0's tables -> position in the caller's array
+    const std::vector<bool>* sharded = nullptr;
+    bool isSharded(const Table* t) const {
+        if (t->derived) return false;       // (local or merged: the same rows on every shard)
+        auto it = index.find(t);
+        return it != index.end() && (*sharded)[(size_t)it->second];
+    }
+
+    // the derived tables of `qs` (one query per shard), innermost first
+    void classify(const std::vector<Query*>& qs, const std::string& prefix, std::string& text) {
+        for (size_t k = 0; k < qs[0]->derived.size(); k++) {
+            std::vector<Query*> subs;
+            for (Query* q : qs) { subs.push_back(q->derived[k].sub.get()); q->derived[k].sub->derivedExternal = true; }
+            DerivedState& d0 = qs[0]->derived[k];
+            const std::string name = prefix + d0.table->name;
+            classify(subs, name + "/", text);
+            Query& s = *d0.sub;
+            std::vector<OpNode*> scans;
+            scansOf(s.root, scans);
+            std::vector<const Table*> shardedScans;
+            for (OpNode* o : scans) if (isSharded(o->table)) shardedScans.push_back(o->table);
+            int mode = LOCAL;
+            if (shardedScans.size() > 1)
+                failUnsupported("the derived aggregation " + name + " reads two sharded tables (" + shardedScans[0]->name + ", " + shardedScans[1]->name +
+                                "): across GPUs at most one table of a derived aggregation may be sharded - replicate " + shardedScans[1]->name);
+            if (!shardedScans.empty()) {
+                const Table* t = shardedScans[0];
+                if (aggregatingSource(s) != t)
+                    failUnsupported("table " + t->name + " is sharded but is not the source of the aggregating pipeline of the derived aggregation " + name +
+                                    " (a build side): across GPUs replicate " + t->name);
+                if (queryIsDense(s) && !s.derived.empty())
+                    failUnsupported("table " + t->name + " is sharded under the derived aggregation " + name + ", whose dense groups also read a derived table: replicate " + t->name);
+                mode = MERGED;
+            }
+            for (Query* q : qs) { q->derived[k].multi = mode; q->derived[k].sliceShards = 0; q->derived[k].sliceAt = 0; }
+            if (mode == MERGED) text += (text.empty() ? "" : "; ") + name + " merged over " + std::to_string(qs.size()) + " shards";
+        }
+    }
+};
+
+// the columns of shard j's table d are shard 0's (rows [r0, r0 + rows)), by peer copies behind `ready` on the root's stream
+void copyColumns(Context& root, DerivedState& from, Context& dst, DerivedState& to, int64_t r0, int64_t rows, hipEvent_t ready, int64_t* moved) {
+    Table& t = *to.table;
+    const int64_t n = from.table->nRows;
+    if (n > to.capacity || to.dCols.empty()) {
+        for (void* p : to.dCols) dst.free(p);
+        to.dCols.clear();
+        to.capacity = std::max<int64_t>(n + n / 8, 64);
+        for (auto& c : t.cols) to.dCols.push_back(dst.alloc((size_t)to.capacity * (size_t)columnWidth(c.type)));
+    }
+    RSQ_HIP(hipSetDevice(dst.device));
+    RSQ_HIP(hipStreamWaitEvent(dst.stream, ready, 0));
+    for (size_t c = 0; c < t.cols.size(); c++) {
+        const size_t w = (size_t)columnWidth(t.cols[c].type);
+        t.cols[c].dptr = to.dCols[c];
+        if (rows <= 0) continue;
+        char* out = (char*)to.dCols[c] + (size_t)r0 * w;
+        const char* in = (const char*)from.dCols[c] + (size_t)r0 * w;
+        if (dst.device == root.device) RSQ_HIP(hipMemcpyAsync(out, in, (size_t)rows * w, hipMemcpyDeviceToDevice, dst.stream));
+        else RSQ_HIP(hipMemcpyPeerAsync(out, dst.device, in, root.device, (size_t)rows * w, dst.stream));
+        *moved += (int64_t)((size_t)rows * w);
+    }
+    t.nRows = n; t.row0 = 0; t.nRowsTotal = -1;
+}
+
+// shard i scans its slice of the whole table: offset columns, its first row numbered over the whole table, the whole table's row count
+void applySlice(DerivedState& d) {
+    if (d.sliceShards <= 0) return;
+    Table& t = *d.table;
+    const int64_t n = t.nRows;
+    int64_t r0 = 0, rows = 0;
+    rsq_multi_shard_rows(n, d.sliceShards, d.sliceAt, &r0, &rows);
+    for (size_t c = 0; c < t.cols.size(); c++) t.cols[c].dptr = (char*)d.dCols[c] + (size_t)r0 * (size_t)columnWidth(t.cols[c].type);
+    t.row0 = r0; t.nRows = rows; t.nRowsTotal = n;
+}
+
+bool deviceTailOff() { return getenv("RSQ_DEVICE_TAIL") && atoi(getenv("RSQ_DEVICE_TAIL")) == 0; }
+int64_t deviceTailMin() { return getenv("RSQ_DEVICE_TAIL_MIN") ? atoll(getenv("RSQ_DEVICE_TAIL_MIN")) : 65536; }
+
+void* mergeBuffer(Context& root, DerivedState& d, size_t bytes) {
+    if ((int64_t)bytes > d.mergeCapacity || !d.dMerge) {
+        if (d.dMerge) root.free(d.dMerge);
+        d.dMerge = nullptr; d.mergeCapacity = 0;
+        d.dMerge = root.alloc(bytes + bytes / 8);
+        d.mergeCapacity = (int64_t)(bytes + bytes / 8);
+    }
+    return d.dMerge;
+}
+
+struct Runner {
+    const ShardThreads* onThreads = nullptr;
+    DerivedMultiRun* out = nullptr;
+    bool trace = false;
+
+    void run(const std::vector<Query*>& qs, const std::string& prefix) {
+        const int n = (int)qs.size();
+        for (size_t k = 0; k < qs[0]->derived.size(); k++) {
+            std::vector<Query*> subs;
+            for (Query* q : qs) subs.push_back(q->derived[k].sub.get());
+            run(subs, prefix + qs[0]->derived[k].table->name + "/");      // (the tables below it first)
+            const std::string name = prefix + qs[0]->derived[k].table->name;
+            if (qs[0]->derived[k].multi == LOCAL || n == 1) {
+                (*onThreads)([&](int i) {
+                    Query& q = *qs[(size_t)i];
+                    DerivedState& d = q.derived[k];
+                    Query& s = *d.sub;
+                    executeQuery(s, false);
+                    d.extKernels = s.report.num_kernels; d.extBytes = s.report.bytes_read;
+                    writeDerivedFrom(q, d, s, true, &d.extKernels, &d.extBytes);
+                    applySlice(d);
+                });
+                if (trace) fprintf(stderr, "[rsq trace] %s: %lld rows, local on %d shards\n", name.c_str(), (long long)qs[0]->derived[k].table->totalRows(), n);
+                describe(name, "local", qs[0]->derived[k], -1);
+                continue;
+            }
+            merged(qs, k, name);
+        }
+    }
+
+    void describe(const std::string& name, const std::string& how, const DerivedState& d, int64_t bytes) {
+        out->text += (out->text.empty() ? "" : "; ") + name + " " + how + (bytes >= 0 ? " (" + std::to_string((long long)bytes) + " bytes)" : "") +
+                     (d.sliceShards > 0 ? ", sliced" : ", whole");
+    }
+
+    void merged(const std::vector<Query*>& qs, size_t k, const std::string& name) {
+        const int n = (int)qs.size();
+        Query& q0 = *qs[0];
+        DerivedState& d0 = q0.derived[k];
+        Query& s0 = *d0.sub;
+        Context& root = q0.ctx;
+        const bool dense = queryIsDense(s0);
+        std::vector<hipEvent_t> done((size_t)n, nullptr);
+        hipEvent_t written = nullptr;
+        auto cleanup = [&] {
+            for (int i = 0; i < n; i++) if (done[(size_t)i]) { (void)hipSetDevice(qs[(size_t)i]->ctx.device); (void)hipEventDestroy(done[(size_t)i]); }
+            if (written) { (void)hipSetDevice(root.device); (void)hipEventDestroy(written); }
+        };
+        try {
+            // every shard's sub-query up to its group rows (hash) or its partial table (dense)
+            (*onThreads)([&](int i) {
+                Query& s = *qs[(size_t)i]->derived[k].sub;
+                RSQ_HIP(hipSetDevice(s.ctx.device));
+                if (dense) executeQuery(s, true);
+                else { setHoldTail(s, true); s.holdTailOnDevice = true; executeQuery(s, false); }
+                DerivedState& d = qs[(size_t)i]->derived[k];
+                d.extKernels = s.report.num_kernels; d.extBytes = s.report.bytes_read;
+                RSQ_HIP(hipEventCreateWithFlags(&done[(size_t)i], hipEventDisableTiming));
+                RSQ_HIP(hipEventRecord(done[(size_t)i], s.ctx.stream));
+            });
+            const double t0 = wallMs();
+            int64_t moved = 0;
+            std::string path;
+            if (dense) path = exchangeDense(qs, k, done, moved);
+            else path = exchangeRows(qs, k, done, moved);
+            // the root's columns, then every other shard's: copies of the root's (tuples on the root's device) or its own writer over the uploaded tuples
+            const bool devTuples = s0.resultInPinned && s0.resultDev != nullptr;
+            RSQ_HIP(hipSetDevice(root.device));
+            writeDerivedFrom(q0, d0, s0, true, &d0.extKernels, &d0.extBytes);
+            RSQ_HIP(hipEventCreateWithFlags(&written, hipEventDisableTiming));
+            RSQ_HIP(hipEventRecord(written, root.stream));
+            const int64_t rows = d0.table->nRows;
+            for (int j = 1; j < n; j++) {
+                Query& q = *qs[(size_t)j];
+                DerivedState& d = q.derived[k];
+                if (devTuples) {
+                    int64_t r0 = 0, nr = rows;
+                    if (d.sliceShards > 0) rsq_multi_shard_rows(rows, d.sliceShards, d.sliceAt, &r0, &nr);
+                    copyColumns(root, d0, q.ctx, d, r0, nr, written, &moved);
+                } else {
+                    RSQ_HIP(hipSetDevice(q.ctx.device));
+                    writeDerivedFrom(q, d, s0, false, &d.extKernels, &d.extBytes);
+                }
+            }
+            for (int i = 0; i < n; i++) applySlice(qs[(size_t)i]->derived[k]);
+            for (int i = 0; i < n; i++) { RSQ_HIP(hipSetDevice(qs[(size_t)i]->ctx.device)); RSQ_HIP(hipStreamSynchronize(qs[(size_t)i]->ctx.stream)); }
+            const double ms = wallMs() - t0;
+            out->exchangeMs += ms;
+            out->exchangeBytes += moved;
+            if (trace)
+                fprintf(stderr, "[rsq trace] %s: %lld rows merged %s over %d shards (%lld bytes moved, %.3f ms)\n", name.c_str(), (long long)rows,
+                        path.c_str(), n, (long long)moved, ms);
+            describe(name, "merged " + path + " over " + std::to_string(n) + " shards", d0, moved);
+        } catch (...) { cleanup(); throw; }
+        cleanup();
+    }
+
+    // partial tables -> the root's gather buffer (peer copies in shard order) -> the engine's merge kernel -> the root's tail
+    std::string exchangeDense(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
+        const int n = (int)qs.size();
+        Query& s0 = *qs[0]->derived[k].sub;
+        Context& root = s0.ctx;
+        int64_t nMin, nMax, nSum; void* p0;
+        queryDenseLayout(s0, &nMin, &nMax, &nSum, &p0);
+        const int64_t words = nMin + nMax + nSum;
+        int64_t* gathered = (int64_t*)mergeBuffer(root, qs[0]->derived[k], (size_t)n * (size_t)words * 8);
+        RSQ_HIP(hipSetDevice(root.device));
+        for (int i = 0; i < n; i++) {
+            Query& s = *qs[(size_t)i]->derived[k].sub;
+            int64_t a, b, c; void* part;
+            queryDenseLayout(s, &a, &b, &c, &part);
+            if (a != nMin || b != nMax || c != nSum) throw Error(RSQ_ERR_RUNTIME, "internal: shards disagree on the partial table of a derived aggregation");
+            RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
+            int64_t* to = gathered + (size_t)i * (size_t)words;
+            if (s.ctx.device == root.device) RSQ_HIP(hipMemcpyAsync(to, part, (size_t)words * 8, hipMemcpyDeviceToDevice, root.stream));
+            else RSQ_HIP(hipMemcpyPeerAsync(to, root.device, part, s.ctx.device, (size_t)words * 8, root.stream));
+            if (i > 0) moved += words * 8;
+        }
+        mergePartialsAsync(root, gathered, n, words, nMin, nMax, nSum, (int64_t*)p0);
+        const uint64_t before = s0.report.num_kernels;
+        finalizeQuery(s0);
+        qs[0]->derived[k].extKernels += 1 + (s0.report.num_kernels >= before ? s0.report.num_kernels - before : 0);      // (the merge and the tail's launches)
+        return s0.resultInPinned && s0.resultDev ? "on the device (dense partial tables)" : "on the host (dense partial tables, merge kernel on the device)";
+    }
+
+    // group rows: gathered and merged on the root's device (device path), or merged by the host (host path)
+    std::string exchangeRows(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
+        const int n = (int)qs.size();
+        DerivedState& d0 = qs[0]->derived[k];
+        Query& s0 = *d0.sub;
+        Context& root = s0.ctx;
+        std::vector<Query*> subs;
+        int64_t total = 0;
+        for (Query* q : qs) {
+            Query& s = *q->derived[k].sub;
+            if (s.groupRowWords != s0.groupRowWords || s.aggMode != s0.aggMode) throw Error(RSQ_ERR_RUNTIME, "internal: shards disagree on the group rows of a derived aggregation");
+            subs.push_back(&s);
+            total += s.nGroupRows;
+        }
+        if (!s0.agg) failUnsupported("a derived table without an aggregation");
+        bool device = !deviceTailOff() && total >= deviceTailMin() && total < (1ll << 31) && s0.dGroupRows;
+        if (device && s0.rowTail < 0) s0.rowTail = planRowsDeviceTail(s0, s0.rtKeys, s0.rtCols, s0.rtTupleSize, s0.rtLimitRows, s0.rtSorts) ? 1 : 0;
+        device = device && s0.rowTail == 1 && !s0.rtSorts && s0.accums.size() <= 32;
+        if (!device) {
+            for (Query* s : subs) fetchHeldGroupRows(*s);
+            for (int i = 1; i < n; i++) moved += subs[(size_t)i]->nGroupRows * subs[(size_t)i]->groupRowWords * 8;
+            runTailMerged(s0, subs);
+            return "on the host";
+        }
+        const int stride = s0.groupRowWords;
+        const HashTable& ht = *s0.hashTables[(size_t)s0.aggTable];
+        GroupMergeSpec spec{};
+        spec.stride = stride; spec.nTab = (int32_t)(ht.keys.size() + ht.payload.size()); spec.nAcc = (int32_t)s0.accums.size();
+        spec.keys = s0.rtKeys;
+        for (size_t w = 0; w < s0.accums.size(); w++) { spec.accWord[w] = 1 + spec.nTab + s0.accumSlot[w]; spec.accKind[w] = s0.accums[w].merge; }
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t rowBytes = (size_t)total * (size_t)stride * 8;
+        char* buf = (char*)mergeBuffer(root, d0, up(rowBytes) * 2 + up(groupMergeTempBytes(total)) + 256);
+        int64_t* gathered = (int64_t*)buf;
+        int64_t* mergedRows = (int64_t*)(buf + up(rowBytes));
+        void* temp = buf + up(rowBytes) * 2;
+        uint64_t* dCount = (uint64_t*)(buf + up(rowBytes) * 2 + up(groupMergeTempBytes(total)));
+        RSQ_HIP(hipSetDevice(root.device));
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            Query& s = *subs[(size_t)i];
+            RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
+            const size_t b = (size_t)s.nGroupRows * (size_t)stride * 8;
+            if (b) {
+                if (s.ctx.device == root.device) RSQ_HIP(hipMemcpyAsync(gathered + (size_t)at * (size_t)stride, s.dGroupRows, b, hipMemcpyDeviceToDevice, root.stream));
+                else RSQ_HIP(hipMemcpyPeerAsync(gathered + (size_t)at * (size_t)stride, root.device, s.dGroupRows, s.ctx.device, b, root.stream));
+                if (i > 0) moved += (int64_t)b;
+            }
+            at += s.nGroupRows;
+        }
+        mergeGroupRows(root, gathered, total, spec, temp, mergedRows, dCount);
+        uint64_t groups = 0;
+        uint32_t err = 0;
+        RSQ_HIP(hipMemcpyAsync(&groups, dCount, 8, hipMemcpyDeviceToHost, root.stream));
+        RSQ_HIP(hipMemcpyAsync(&err, root.dErr, 4, hipMemcpyDeviceToHost, root.stream));
+        waitForStream(root);
+        if (err) { root.errWordClean = false; checkDeviceError(err); }
+        if (groups > (uint64_t)total) throw Error(RSQ_ERR_RUNTIME, "internal: the merge across shards made more groups than it was given rows");
+        d0.extKernels += 5;
+        d0.extBytes += (uint64_t)rowBytes;
+        s0.resultInPinned = false; s0.resultDev = nullptr;
+        const uint64_t before = s0.report.num_kernels;
+        runRowsDeviceTail(s0, (int64_t)groups, mergedRows);
+        d0.extKernels += s0.report.num_kernels - before;      // (the device tail counts its launches in the sub-query's report)
+        return "on the device";
+    }
+};
+
+}  // namespace
+
+std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* const* tables, int nTables, const std::vector<bool>& sharded) {
+    Planner P;
+    P.sharded = &sharded;
+    for (int t = 0; t < nTables; t++) P.index[reinterpret_cast<const Table*>(tables[t])] = t;
+    std::string text;
+    P.classify(qs, "", text);
+    for (Query* q : qs) q->derivedExternal = true;
+    // the parent's tables: a sharded one must be the source of the last pipeline (the caller's shard, as every rsq_multi_* plan)
+    Query& q0 = *qs[0];
+    const Table* last = q0.pipelines.empty() ? nullptr : q0.pipelines.back().src;
+    std::vector<OpNode*> scans;
+    scansOf(q0.root, scans);
+    for (OpNode* o : scans)
+        if (P.isSharded(o->table) && o->table != last)
+            failUnsupported("table " + o->table->name + " is sharded but is a build side (or the source of an earlier pipeline) of a plan with derived aggregations: "
+                            "across GPUs only the source of the last pipeline and one table of a derived aggregation may be sharded - replicate " + o->table->name);
+    // a derived table the last pipeline scans: every shard scans its slice (else every row would be counted once per shard)
+    if (last && last->derived && qs.size() > 1)
+        for (size_t k = 0; k < q0.derived.size(); k++)
+            if (q0.derived[k].table.get() == last)
+                for (size_t i = 0; i < qs.size(); i++) { qs[i]->derived[k].sliceShards = (int)qs.size(); qs[i]->derived[k].sliceAt = (int)i; }
+    std::string where;
+    for (size_t k = 0; k < q0.derived.size(); k++)
+        where += (where.empty() ? "" : ", ") + q0.derived[k].table->name + (q0.derived[k].multi == MERGED ? " merged" : " local") +
+                 (q0.derived[k].sliceShards > 0 ? " sliced" : " whole");
+    return where + (text.empty() ? "" : " (" + text + ")");
+}
+
+void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out) {
+    out = DerivedMultiRun();
+    Runner r;
+    r.onThreads = &onThreads; r.out = &out; r.trace = getenv("RSQ_TRACE") != nullptr;
+    r.run(qs, "");
+}
+
+}  // namespace rsq

@@ -133,8 +133,9 @@ bool rowsDeviceTailWanted(Query& q, int64_t n) {
     return q.rowTail == 1;
 }
 
-double runRowsDeviceTail(Query& q, int64_t n) {
+double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows) {
     Context& ctx = q.ctx;
+    const int64_t* src = groupRows ? groupRows : q.dGroupRows;
     const bool trace = getenv("RSQ_TRACE") != nullptr;
     const double t0 = nowMs();
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -167,10 +168,10 @@ double runRowsDeviceTail(Query& q, int64_t n) {
         int64_t maxRow = 1;
         for (auto& p : q.pipelines) if (p.sink == SinkKind::AGGREGATE) maxRow = std::max<int64_t>(maxRow, std::max(p.src->row0 + p.src->nRows, p.src->totalRows()));
         int bits = 1; while (bits < 63 && (maxRow >> bits) != 0) bits++;
-        rowTailFirstKeys(ctx, q.dGroupRows, stride, n, keysA, idxA);
+        rowTailFirstKeys(ctx, src, stride, n, keysA, idxA);
         const bool inB = radixSortPairs(ctx, keysA, idxA, keysB, idxB, n, bits, sortTemp, radixSortTempBytes(cap));
         dIdx = inB ? idxB : idxA;
-        rowTailHashes(ctx, q.dGroupRows, stride, dIdx, n, q.rtKeys, hashes);
+        rowTailHashes(ctx, src, stride, dIdx, n, q.rtKeys, hashes);
         std::vector<std::pair<uint64_t, uint64_t>> levels;
         if (replayLevels((uint64_t)n, opSize(q.agg), levels) && replayDeviceBytes((uint64_t)n, levels.back().first) <= replayBytes) {
             replayEmissionOrderDevice(ctx, hashes, (uint64_t)n, levels, replayWork, order);
@@ -187,7 +188,7 @@ double runRowsDeviceTail(Query& q, int64_t n) {
         }
         dOrder = order;
     }
-    rowTailResultRows(ctx, q.dGroupRows, stride, dIdx, dOrder, emit, q.rtCols, q.rtTupleSize, rows);
+    rowTailResultRows(ctx, src, stride, dIdx, dOrder, emit, q.rtCols, q.rtTupleSize, rows);
     const size_t outBytes = std::max<size_t>((size_t)emit * (size_t)q.rtTupleSize, 8);
     if (q.rtPinnedBytes < outBytes) {
         if (q.rtPinned) ctx.freePinned(q.rtPinned);

@@ -295,6 +295,11 @@ struct DerivedState {
     void* dTuples = nullptr;         // the host tail's tuples uploaded for the writer
     int64_t capacity = 0, tupleCapacity = 0;
     bool named = false;              // the walker has given this query's names to the columns
+    // rsq_multi_* (engine_derived_multi.cpp): how the table is split across shards, and what the run step did for it
+    int multi = 0;                   // 0 one context (prepareDerived); 1 local: every shard computes it; 2 merged: the shards' groups are merged
+    int sliceShards = 0, sliceAt = 0;      // > 0: this shard scans rows rsq_multi_shard_rows(rows, sliceShards, sliceAt) of it
+    uint64_t extKernels = 0, extBytes = 0; // the run step's work for this shard (the sub-query's, the writer's, the exchange's)
+    void* dMerge = nullptr; int64_t mergeCapacity = 0;      // merged, root only: the gathered rows / partial tables, merge scratch, merged rows
 };
 
 struct Query {
@@ -315,6 +320,8 @@ struct Query {
     // rsq_multi_*: the inner side of the top-level nested-loops join is run and bound by multi.cpp (nestedLoops* in engine.h) in front of
     // the execution, which then runs the outer side only.  `gatheredTables`: tables whose rows every shard sees through that inner side.
     bool nljExternal = false;
+    bool derivedExternal = false;          // rsq_multi_*: the derived tables are built and bound by engine_derived_multi.cpp in front of the execution
+    bool holdTailOnDevice = false;         // ... and a held tail leaves its group rows on the device only (the merge across shards reads them there)
     std::vector<const Table*> gatheredTables;
     OpNode* agg = nullptr;                 // the aggregation whose input pipeline runs on the device (may be null)
     AggMode aggMode = AggMode::NONE;
@@ -558,6 +565,8 @@ void runGeneric2Pipeline(Query& q, size_t pi);
 bool denseDeviceTailWanted(Query& q);
 double runDenseDeviceTail(Query& q);
 bool rowsDeviceTailWanted(Query& q, int64_t n);
-double runRowsDeviceTail(Query& q, int64_t n);
+double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows = nullptr);      // (groupRows: rows other than q.dGroupRows, same layout)
+void fetchHeldGroupRows(Query& q);        // the group rows a held tail left on the device, to q.hGroupRows (engine.cpp)
+void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, uint64_t* kernels, uint64_t* bytes);   // engine.cpp
 
 }  // namespace rsq

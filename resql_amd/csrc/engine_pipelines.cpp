@@ -46,6 +46,7 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
     }
     if (p.src && p.src->derived) {                  // a derived table: its row count and columns are this execution's (engine.cpp prepareDerived)
         if (a.name == "n_rows") return (uint64_t)p.src->nRows;
+        if (a.name == "row0") return (uint64_t)p.src->row0;      // (0, or the start of this shard's slice across GPUs: engine_derived_multi.cpp)
         if (a.name.size() >= 2 && a.name[0] == 'c' && isdigit((unsigned char)a.name[1])) {
             const size_t k = (size_t)atoi(a.name.c_str() + 1);
             return k < p.cols.size() ? (uint64_t)(uintptr_t)p.src->cols[(size_t)p.cols[k]].dptr : 0;

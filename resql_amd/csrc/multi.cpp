@@ -104,6 +104,9 @@ struct rsq_multi_query {
     std::vector<hipEvent_t> innerDone;  // shard i's inner part is materialised (the gather's copies wait for it)
     std::vector<hipEvent_t> gather0, gather1;             // around the gather's copies on shard i's stream
     int64_t gatherBytes = 0;            // moved between shards by the last gather
+    // derived aggregations (engine_derived_multi.cpp): built on every shard in front of the parent's pipelines
+    bool derived = false;
+    double derivedMs = 0;               // the last execution's exchanges (part of the collective time)
     ~rsq_multi_query() {
         for (size_t i = 0; i < innerDone.size(); i++) {      // (a compilation that failed part-way made some of them only)
             (void)hipSetDevice(m->ctxs[i]->device);
@@ -394,7 +397,7 @@ int rsq_multi_create(const rsq_multi_config* hostCfg, rsq_multi** out) {
         if (m->merge == RSQ_MERGE_RCCL && m->sharedDevice)
             failInvalid("an RCCL communicator cannot hold the same device twice: use RSQ_MERGE_PEER_COPY for shards that share a GPU");
         for (int i = 0; i < cfg->n_devices; i++) {
-            rsq_config c = readConfig(cfg->base);
+            rsq_config c = readConfig(cfg->base, true);
             c.device = cfg->devices[i];
             m->ctxs.push_back(new Context(c));
         }
@@ -596,8 +599,21 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                         if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
                     }
         }
-        // (derived aggregations run on one context only: engine.cpp prepareDerived)
-        if (!mq->qs.empty() && queryHasDerived(*mq->qs[0])) refuseDerived(*mq->qs[0], "a multi-GPU compile (rsq_multi_query_compile)");
+        // derived aggregations: across the shards with RSQ_ENGINE_DERIVED_MULTI (never inside a nested-loops plan), else on one context only
+        std::string derivedText;
+        if (!mq->qs.empty() && queryHasDerived(*mq->qs[0])) {
+            if (!(m->ctxs[0]->cfg.engine_flags & RSQ_ENGINE_DERIVED_MULTI) || mq->nlj) refuseDerived(*mq->qs[0], "a multi-GPU compile (rsq_multi_query_compile)");
+            mq->derived = true;
+            derivedText = planDerivedAcrossShards(mq->qs, tables, n_tables, sharded);
+            // (peer copies between distinct GPUs: direct over xGMI where the pair allows it)
+            for (int j = 0; j < n; j++)
+                for (int i = 0; i < n; i++) {
+                    int can = 0;
+                    if (m->devices[(size_t)i] == m->devices[(size_t)j] || hipDeviceCanAccessPeer(&can, m->devices[(size_t)j], m->devices[(size_t)i]) != hipSuccess || !can) continue;
+                    RSQ_HIP(hipSetDevice(m->devices[(size_t)j]));
+                    if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
+                }
+        }
         mq->dense = queryIsDense(*mq->qs[0]);
         if (mq->dense) {
             // (with unified statistics every shard derives the same layout; anything else is a defect of this library, not of the data)
@@ -615,10 +631,11 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 for (int i = 1; i < n; i++) { RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device)); RSQ_HIP(hipEventCreateWithFlags(&mq->ready[(size_t)i], hipEventDisableTiming)); }
             }
             // (a nested-loops plan runs on host threads: the host stands between its inner and its outer sides)
-            mq->async = !mq->nlj;
+            mq->async = !mq->nlj && !mq->derived;
             for (Query* q : mq->qs) mq->async = mq->async && queryAsyncCapable(*q);
             mq->mergeText = std::string("dense partial tables: ") + rsq_multi_merge_name(m) +
-                            (mq->async ? "" : mq->nlj ? " (nested-loops join: the shards run on host threads)" : " (join builds: the shards run on host threads)");
+                            (mq->async ? "" : mq->nlj ? " (nested-loops join: the shards run on host threads)" : mq->derived ? " (derived tables: the shards run on host threads)"
+                                                                                                                  : " (join builds: the shards run on host threads)");
         } else {
             for (int i = 1; i < n; i++) if (queryIsDense(*mq->qs[(size_t)i])) throw Error(RSQ_ERR_RUNTIME, "internal: shards planned from the same statistics disagree on the aggregation strategy");
             // Groups may straddle shard boundaries (the reference has ONE hash table all workers reach, aggregation.h:240-295):
@@ -640,6 +657,10 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             mq->mergeBase = mq->mergeText;
             mq->mergeText = "nested-loops: outer rows over " + std::to_string(n) + (n == 1 ? " shard" : " shards") + ", inner side " +
                             (mq->nljGathered ? "gathered (peer copies)" : "replicated") + "; " + mq->mergeBase;
+        }
+        if (mq->derived) {
+            mq->mergeBase = mq->mergeText;
+            mq->mergeText = "derived tables: " + derivedText + "; " + mq->mergeBase;
         }
         mq->shardKernelMs.assign((size_t)n, 0.0);
         *out = mq.release();
@@ -669,6 +690,15 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
             for (int i = 0; i < n; i++) if (status[(size_t)i] != RSQ_OK) throw Error(status[(size_t)i], "shard " + std::to_string(i) + ": " + errs[(size_t)i]);
         };
         auto onThreads = [&](bool partialOnly) { onThreadsDo([&](int i) { executeQuery(*mq->qs[(size_t)i], partialOnly); }); };
+        mq->derivedMs = 0;
+        if (mq->derived) {
+            // the derived tables on every shard, innermost first (their sub-queries, exchanges and writers), then the parent as below
+            const ShardThreads threads = [&](const std::function<void(int)>& f) { onThreadsDo(f); };
+            DerivedMultiRun run;
+            runDerivedAcrossShards(mq->qs, threads, run);
+            mq->derivedMs = run.exchangeMs;
+            mq->mergeText = "derived tables: " + run.text + "; " + mq->mergeBase;
+        }
         if (mq->nlj) {
             // inner parts, the budget, the gather, the outer sides - then the merge of the plan's kind
             executeNestedLoops(*mq, onThreadsDo);
@@ -718,6 +748,7 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
             if (hipEventSynchronize(mq->evMerge1) == hipSuccess && hipEventElapsedTime(&ms, mq->evMerge0, mq->evMerge1) == hipSuccess) mq->collectiveMs = ms;
         }
         if (mq->nlj) mq->collectiveMs += gatherMs(*mq);
+        mq->collectiveMs += mq->derivedMs;
         rep.execution_time_ms = now() - t0;
         rep.hbm_gbps = rep.kernel_time_ms > 0 ? (double)rep.bytes_read / (rep.kernel_time_ms * 1e-3) / 1e9 : 0;
         mq->report = rep;

@@ -58,7 +58,7 @@ class rsq_multi_config(C.Structure):
 MERGE_AUTO, MERGE_RCCL, MERGE_PEER_COPY = 0, 1, 2
 EMIT_REFERENCE, EMIT_ANY = 0, 1
 COMPAT_JIT_INT16_CAST = 1      # rsq_compat: TYPECAST INT -> BIGINT as the reference's asmjit JIT executes it (low 16 bits)
-ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS = 1, 2, 4      # rsq_engine_flags
+ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS, ENGINE_DERIVED_MULTI = 1, 2, 4, 8      # rsq_engine_flags
 
 
 class EngineError(RuntimeError):
@@ -576,7 +576,8 @@ class MultiContext:
 
     def __init__(self, devices: Sequence[int], merge: int = MERGE_AUTO, cache_dir: Optional[str] = None, emission_order: int = 0,
                  compat_flags: int = 0, engine_flags: int = 0, nested_loops_max_pairs: int = 0):
-        """engine_flags, nested_loops_max_pairs: as for Context, on every shard (ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
+        """engine_flags, nested_loops_max_pairs: as for Context, on every shard (ENGINE_DERIVED_MULTI, for these handles only, runs derived
+        aggregations across the shards; ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
         by its outer side's rows; the budget bounds the whole statement's pairs)"""
         self._L = lib()
         self._devs = (C.c_int32 * len(devices))(*devices)
