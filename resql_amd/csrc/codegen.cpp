@@ -75,7 +75,7 @@ void Walker::produce(OpNode* o, std::vector<std::string> request) {
 // first-row tracker is outer row x inner rows + inner position (the order in which the reference meets the pairs).
 void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
     NljState& n = q.nljs[(size_t)o->nlj];
-    Query& in = *n.inner;
+    Query& in = *n.sub.query;
     if (!in.matOp || in.agg) failUnsupported("the inner side of a nested-loops join must be a materialisation on the device");
     if (n.outerSrc) failUnsupported("a nested-loops join inside more than one pipeline");
     n.outerSrc = pipe.src;

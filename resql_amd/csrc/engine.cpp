@@ -124,8 +124,8 @@ uint64_t opSize(OpNode* o, bool local) {
 
 Query::~Query() {
     if (bgCompiler.joinable()) bgCompiler.join();
-    for (NljState& n : nljs) for (void* p : n.dCols) ctx.free(p);
-    for (DerivedState& d : derived) { for (void* p : d.dCols) ctx.free(p); if (d.dTuples) ctx.free(d.dTuples); if (d.dMerge) ctx.free(d.dMerge); }
+    for (NljState& n : nljs) n.sub.freeColumns(ctx);
+    for (DerivedState& d : derived) { d.sub.freeColumns(ctx); if (d.dTuples) ctx.free(d.dTuples); if (d.dMerge) ctx.free(d.dMerge); }
     destroyTailState(tailState);
     if (dtArena.dev || dtArena.pinned) {
         // the arenas go back to the context for the next query, unless it already holds a pair
@@ -404,12 +404,10 @@ static void rememberPlan(Query& q) {
     }
 }
 
-// The inner side of a nested-loops join: the left subtree under a MATERIALIZE (the reference's own wrapper where the plan has it), every
-// attribute, no limit - a plan description of its own, compiled as a query of its own.
-static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
-    int left = -1;
-    for (int i = 0; i < plan.n_ops; i++) if (q.ops[(size_t)i].get() == n.op) left = plan.ops[i].child[0];
-    if (left < 0) failInvalid("nested-loops join without a left child");
+// A sub-query (engine_internal.h SubQuery): the subtree under plan op `at` under a MATERIALIZE (the reference's own wrapper where the
+// subtree's root is one), every attribute, no limit - a plan description of its own, compiled as a query of its own.  The copy keeps the
+// plan's op order (children first), which fixes the sub-query's expression ids and hence its kernel text.
+static Query* compileSubQuery(Context& ctx, const rsq_plan_desc& plan, int at, rsq_table* const* tables, int nTables) {
     std::vector<rsq_op> ops;
     std::map<int, int> remap;
     std::function<int(int)> copy = [&](int i) -> int {
@@ -420,7 +418,7 @@ static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& 
         ops.push_back(d);
         return remap[i] = (int)ops.size() - 1;
     };
-    int root = copy(left);
+    int root = copy(at);
     if (ops[(size_t)root].tag != RSQ_OP_MATERIALIZE) {
         rsq_op m;
         memset(&m, 0, sizeof m);
@@ -431,12 +429,19 @@ static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& 
     rsq_plan_desc sub = plan;
     sub.ops = ops.data(); sub.n_ops = (int32_t)ops.size(); sub.root = root;
     sub.request_all = 1; sub.has_limit = 0; sub.limit = 0;
-    n.inner.reset(compileQuery(q.ctx, sub, tables, nTables));
+    return compileQuery(ctx, sub, tables, nTables);
+}
+
+// The inner side of a nested-loops join: the sub-query of its left subtree
+static void compileNestedLoopsInner(Query& q, NljState& n, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables) {
+    int left = -1;
+    for (int i = 0; i < plan.n_ops; i++) if (q.ops[(size_t)i].get() == n.op) left = plan.ops[i].child[0];
+    if (left < 0) failInvalid("nested-loops join without a left child");
+    n.sub.query.reset(compileSubQuery(q.ctx, plan, left, tables, nTables));
 }
 
 // Derived aggregations (engine_internal.h DerivedState): every AGGREGATION with an ancestor other than PROJECTION / MATERIALIZE / ORDERBY
-// and no such aggregation above it is cut out as a sub-query - MATERIALIZE over its subtree, every attribute, no limit - which compiles the
-// aggregations below it the same way.  The node becomes a scan of the derived table.
+// and no such aggregation above it is cut out as a sub-query, which compiles the aggregations below it the same way.  The node becomes a scan of the derived table.
 static bool isDerivedAggregation(const OpNode* o) {
     if (o->tag != RSQ_OP_AGGREGATION) return false;
     for (const OpNode* a = o->parent; a; a = a->parent)
@@ -465,23 +470,8 @@ static void compileDerived(Query& q, const rsq_plan_desc& plan, rsq_table* const
         DerivedState d;
         d.op = o; d.groups = o->exprs2; d.aggs = o->exprs;
         const uint64_t estimate = opSize(o);      // (operators above size their tables from it, as the reference's do)
-        std::vector<rsq_op> ops;
-        std::function<int(int)> copy = [&](int k) -> int {
-            rsq_op c = plan.ops[k];
-            for (int j = 0; j < 2; j++) if (c.child[j] >= 0) c.child[j] = copy(c.child[j]);
-            ops.push_back(c);
-            return (int)ops.size() - 1;
-        };
-        const int agg = copy(i);
-        rsq_op m;
-        memset(&m, 0, sizeof m);
-        m.tag = RSQ_OP_MATERIALIZE; m.child[0] = agg; m.child[1] = -1; m.table = -1;
-        ops.push_back(m);
-        rsq_plan_desc sub = plan;
-        sub.ops = ops.data(); sub.n_ops = (int32_t)ops.size(); sub.root = (int32_t)ops.size() - 1;
-        sub.request_all = 1; sub.has_limit = 0; sub.limit = 0;
-        d.sub.reset(compileQuery(q.ctx, sub, tables, nTables));
-        Query& s = *d.sub;
+        d.sub.query.reset(compileSubQuery(q.ctx, plan, i, tables, nTables));
+        Query& s = *d.sub.query;
         if (s.agg == nullptr) failInvalid("derived aggregation without an aggregation");
         // mergeAverages names an AVG when the aggregation's rows are made (tail.cpp): its id is taken now, so that the counter this
         // query continues from (Walker::produceScan) has counted it
@@ -509,7 +499,7 @@ void nameDerivedColumns(Query& q, OpNode* scan) {
     DerivedState& d = q.derived[(size_t)scan->derived];
     if (d.named) return;
     d.named = true;
-    Query& s = *d.sub;
+    Query& s = *d.sub.query;
     const size_t base = (size_t)q.pool.exprIdGen - 1;
     for (size_t i = 0; i < q.exprs.size() && i < s.exprs.size(); i++)
         if (s.exprs[i]->id != 0 && q.exprs[i]->id == 0) q.exprs[i]->id = s.exprs[i]->id + base;
@@ -526,7 +516,7 @@ void refuseDerived(const Query& q, const std::string& what) {
 
 bool queryHasDerived(const Query& q) {
     if (!q.derived.empty()) return true;
-    for (const NljState& n : q.nljs) if (n.inner && queryHasDerived(*n.inner)) return true;
+    for (const NljState& n : q.nljs) if (n.sub.query && queryHasDerived(*n.sub.query)) return true;
     return false;
 }
 
@@ -555,7 +545,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
             compileNestedLoopsInner(*q, n, plan, tables, nTables);
             // The reference numbers expressions with one counter in produce order, and NestedLoopsJoinOp produces its left child first:
             // the names of this query's expressions (`exprN` of an aggregate's column) come after the inner side's
-            q->pool.exprIdGen += n.inner->pool.exprIdGen - 1;        // (both counters start at 1)
+            q->pool.exprIdGen += n.sub.query->pool.exprIdGen - 1;        // (both counters start at 1)
         }
     }
     const double tBuilt0 = nowMs();
@@ -659,7 +649,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
         for (auto& c : d.table->cols) cols += (cols.empty() ? "" : "|") + c.name + ":" + serializeType(c.type);
         q->explainText += "derived table " + d.table->name + " (" + derivedName(d.groups).substr(4) + ", estimate " + std::to_string(d.table->derivedEstimate) +
                           " rows, columns " + cols + ", row count and addresses bound per execution) from its sub-query:\n";
-        std::istringstream in(d.sub->explainText);
+        std::istringstream in(d.sub.query->explainText);
         for (std::string l; std::getline(in, l);) q->explainText += "  | " + l + "\n";
     }
     if (ctx.device >= 0) {
@@ -766,6 +756,12 @@ void fetchHeldGroupRows(Query& q) {
     RSQ_HIP(hipMemcpy(q.hGroupRows, q.dGroupRows, (size_t)q.nGroupRows * (size_t)q.groupRowWords * 8, hipMemcpyDeviceToHost));
 }
 
+// rsq_multi_* builds the derived tables in front of the execution (engine_derived_multi.cpp marks every one of them)
+static bool derivedExternal(const Query& q) {
+    for (const DerivedState& d : q.derived) if (!d.sub.external) return false;
+    return true;
+}
+
 static void executeQueryBody(Query& q, bool partialOnly, bool async);
 void executeQuery(Query& q, bool partialOnly, bool async) {
     // rows appended to a table move its columns (rsq_table_append): the kernels' arguments of a statement compiled before point at memory
@@ -774,26 +770,28 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
     for (size_t i = 0; i < q.tables.size() && i < q.tableLayouts.size(); i++)
         if (q.tables[i]->layoutVersion != q.tableLayouts[i])
             throw Error(RSQ_ERR_INVALID, "rows were appended to table " + q.tables[i]->name + " after this statement was compiled: compile it again");
-    if ((partialOnly || async) && !q.derived.empty() && !(q.derivedExternal && !async)) refuseDerived(q, "partial / asynchronous execution");
+    if ((partialOnly || async) && !q.derived.empty() && !(derivedExternal(q) && !async)) refuseDerived(q, "partial / asynchronous execution");
     executeQueryBody(q, partialOnly, async);
     keepKeyIndexes(q);
     rememberPlan(q);
 }
 
-// The inner sides of the nested-loops joins: each runs as its own query, and its result columns (struct of arrays, strings by value) are
-// copied into device columns this query owns.  Then the pair budget: outer rows x inner rows above rsq_config.nested_loops_max_pairs
-// ends the execution before the outer pipeline starts.  Across GPUs multi.cpp runs the same steps itself (nestedLoops* below): every
-// shard's inner part, then the budget over the whole statement, then the all-gather of the parts.
-static void runNestedLoopsInner(NljState& n, bool run) {
-    n.nInner = 0; n.innerKernels = 0; n.innerBytes = 0;
-    if (!run) return;
-    Query& in = *n.inner;
-    executeQuery(in, false);
-    n.nInner = in.matRows;
-    n.innerKernels = in.report.num_kernels; n.innerBytes = in.report.bytes_read;
+void runSubQuery(SubQuery& s, bool partialOnly) {
+    executeQuery(*s.query, partialOnly);
+    s.kernels = s.query->report.num_kernels; s.bytes = s.query->report.bytes_read;
 }
 
-static void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner) {
+// The inner side of a nested-loops join, and the pair budget: outer rows x inner rows above rsq_config.nested_loops_max_pairs ends the
+// execution before the outer pipeline starts.  Across GPUs multi.cpp runs the steps itself: every shard's inner part, then the budget over
+// the whole statement, then the all-gather of the parts into the bound columns.
+void runNestedLoopsInner(NljState& n, bool run) {
+    n.nInner = 0; n.sub.kernels = 0; n.sub.bytes = 0;
+    if (!run) return;
+    runSubQuery(n.sub);
+    n.nInner = n.sub.query->matRows;
+}
+
+void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner) {
     Context& ctx = q.ctx;
     n.nInner = nInner;
     const int64_t budget = ctx.cfg.nested_loops_max_pairs;
@@ -805,36 +803,13 @@ static void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner
     if (n.pipeline >= 0 && q.pipelines[(size_t)n.pipeline].sink == SinkKind::MATERIALIZE && 128.0L * (long double)n.nInner >= 4294967296.0L)
         failUnsupported("nested-loops join: " + std::to_string((long long)n.nInner) + " inner rows - a 128-row tile of the outer side could emit "
                         "2^32 or more tuples, beyond the materialisation's 32-bit tile counts");
-    if (n.nInner > n.innerCapacity) {
-        for (void* p : n.dCols) ctx.free(p);
-        n.dCols.clear();
-        n.innerCapacity = std::max<int64_t>(n.nInner, 64);
-        for (auto& a : n.innerSchema) n.dCols.push_back(ctx.alloc((size_t)n.innerCapacity * (size_t)columnWidth(a.type)));
-    }
+    n.sub.ensureColumns(ctx, n.innerSchema, n.nInner, std::max<int64_t>(n.nInner, 64));
 }
 
-static void prepareNestedLoops(Query& q) {
-    Context& ctx = q.ctx;
-    for (NljState& n : q.nljs) {
-        if (!n.inner || !n.outerSrc) continue;           // (a join of an inner side: that side's query prepares it)
-        Query& in = *n.inner;
-        const int64_t outer = n.outerSrc->nRows;
-        runNestedLoopsInner(n, outer > 0);               // (an empty outer side needs no inner rows)
-        q.report.num_kernels += n.innerKernels;
-        q.report.bytes_read += n.innerBytes;
-        bindNestedLoops(q, n, outer, n.nInner);
-        for (size_t k = 0; k < n.innerSchema.size() && n.nInner > 0; k++) {
-            const void* src = in.dMatCols[(size_t)n.innerCol[k]];
-            RSQ_HIP(hipMemcpyAsync(n.dCols[k], src, (size_t)n.nInner * (size_t)columnWidth(n.innerSchema[k].type), hipMemcpyDefault, ctx.stream));
-        }
-    }
-}
-
-// the plan's one nested-loops join that is not inside another one's inner side (multi.cpp accepts no other plan)
-static NljState& topNestedLoops(Query& q) {
+NljState& topNestedLoops(Query& q) {
     NljState* top = nullptr;
     for (NljState& n : q.nljs)
-        if (n.inner && n.outerSrc) {
+        if (n.sub.query && n.outerSrc) {
             if (top) failUnsupported("more than one nested-loops join outside each other's inner side");
             top = &n;
         }
@@ -842,41 +817,10 @@ static NljState& topNestedLoops(Query& q) {
     return *top;
 }
 
-bool queryHasNestedLoops(const Query& q) { return !q.nljs.empty(); }
-const Table* nestedLoopsOuterSource(Query& q) { return topNestedLoops(q).outerSrc; }
-void setNestedLoopsExternal(Query& q, const Table* gathered) {
-    (void)topNestedLoops(q);
-    q.nljExternal = true;
-    q.gatheredTables.clear();
-    if (gathered) q.gatheredTables.push_back(gathered);
-}
-void nestedLoopsRunInner(Query& q, bool run, int64_t* rows, uint64_t* kernels, uint64_t* bytes) {
-    NljState& n = topNestedLoops(q);
-    RSQ_HIP(hipSetDevice(q.ctx.device));
-    runNestedLoopsInner(n, run);
-    *rows = n.nInner; *kernels = n.innerKernels; *bytes = n.innerBytes;
-}
-void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows) {
-    RSQ_HIP(hipSetDevice(q.ctx.device));
-    bindNestedLoops(q, topNestedLoops(q), outerRows, innerRows);
-}
-void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths) {
-    NljState& n = topNestedLoops(q);
-    part->clear(); bound->clear(); widths->clear();
-    for (size_t k = 0; k < n.innerSchema.size(); k++) {
-        part->push_back(n.inner->dMatCols.empty() ? nullptr : n.inner->dMatCols[(size_t)n.innerCol[k]]);
-        bound->push_back(k < n.dCols.size() ? n.dCols[k] : nullptr);
-        widths->push_back((size_t)columnWidth(n.innerSchema[k].type));
-    }
-}
-
-// The derived tables (DerivedState), in front of this query's pipelines at every execution: the host may have rewritten adopted input
-// columns in place, so nothing is kept from the previous one.  Each sub-query runs (its own derived tables first), then the writer turns
-// its packed tuples into the table's columns - read where the device tail left them, or uploaded once from the host tail's - and the
-// scan's row count and column addresses are bound (engine_pipelines.cpp argValue).
 // The writer for derived table `d` of `q`: `s`'s packed tuples (its own sub-query's, or the root's after a merge across shards) into
-// d's columns on q's context - read where the device tail left them (deviceTuples, same device), or uploaded once from the host's.
-void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, uint64_t* kernels, uint64_t* bytes) {
+// d's columns on q's context - read where the device tail left them (deviceTuples, same device), or uploaded once from the host's - and
+// the scan's row count and column addresses bound (engine_pipelines.cpp argValue).  Its launch and the tuples it reads are d.sub's work.
+void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples) {
     Context& ctx = q.ctx;
     Table& t = *d.table;
     if (s.resultSchema.size() != t.cols.size()) failRuntime("internal error: " + t.name + " has " + std::to_string(t.cols.size()) +
@@ -890,13 +834,8 @@ void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, ui
     }
     const int tupleSize = off;
     const int64_t n = s.resultRows;
-    if (n > d.capacity || d.dCols.empty()) {
-        for (void* p : d.dCols) ctx.free(p);
-        d.dCols.clear();
-        d.capacity = std::max<int64_t>(n + n / 8, 64);
-        for (auto& c : t.cols) d.dCols.push_back(ctx.alloc((size_t)d.capacity * (size_t)columnWidth(c.type)));
-    }
-    for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.dCols[c]; t.cols[c].dptr = d.dCols[c]; }
+    d.sub.ensureColumns(ctx, t.cols, std::max<int64_t>(n, 1), std::max<int64_t>(n + n / 8, 64));      // (an empty table has its columns too)
+    for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.sub.dCols[c]; t.cols[c].dptr = d.sub.dCols[c]; }
     const uint8_t* tuples = deviceTuples && s.resultInPinned ? s.resultDev : nullptr;
     if (tuples) {      // (the device tail's layout must be the one the writer decodes)
         const int devTuple = tuples == s.dtRows ? s.dtTupleSize : s.rtTupleSize;
@@ -916,25 +855,46 @@ void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, ui
     }
     if (n > 0) {
         derivedColumns(ctx, tuples, n, tupleSize, cols);
-        *kernels += 1;
-        *bytes += (uint64_t)n * (uint64_t)tupleSize;
+        d.sub.kernels += 1;
+        d.sub.bytes += (uint64_t)n * (uint64_t)tupleSize;
     }
     t.nRows = n; t.row0 = 0; t.nRowsTotal = -1;
 }
 
-// The derived tables (DerivedState), in front of this query's pipelines at every execution: the host may have rewritten adopted input
-// columns in place, so nothing is kept from the previous one.  Each sub-query runs (its own derived tables first), then the writer turns
-// its packed tuples into the table's columns and the scan's row count and column addresses are bound (engine_pipelines.cpp argValue).
-static void prepareDerived(Query& q) {
-    for (DerivedState& d : q.derived) {
-        Query& s = *d.sub;
-        executeQuery(s, false);
-        q.report.num_kernels += s.report.num_kernels;
-        q.report.bytes_read += s.report.bytes_read;
-        writeDerivedFrom(q, d, s, true, &q.report.num_kernels, &q.report.bytes_read);
-        if (getenv("RSQ_TRACE"))
-            fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", d.table->name.c_str(), (long long)d.table->nRows,
-                    s.resultInPinned && s.resultDev ? "device" : "host");
+void buildDerived(Query& q, DerivedState& d) {
+    runSubQuery(d.sub);
+    writeDerivedFrom(q, d, *d.sub.query, true);
+}
+
+// The sub-queries, in front of this query's pipelines at every execution (the host may have rewritten adopted input columns in place, so
+// nothing is kept from the previous one).  Each runs here, or rsq_multi_* has run it (external); either way its recorded work is this
+// execution's.  A derived table: its sub-query (its own derived tables first), then the writer.  A nested-loops join: the inner side, its
+// work counted even when the pair budget then ends the execution, then its result columns (struct of arrays, strings by value) copied
+// into the bound columns.
+static void runSubQueries(Query& q) {
+    Context& ctx = q.ctx;
+    auto account = [&](const SubQuery& s) { q.report.num_kernels += s.kernels; q.report.bytes_read += s.bytes; };
+    for (DerivedState& d : q.derived) {              // (the interpreters decline plans over derived tables: generic*.cpp)
+        if (!d.sub.external) {
+            buildDerived(q, d);
+            if (getenv("RSQ_TRACE"))
+                fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", d.table->name.c_str(), (long long)d.table->nRows,
+                        d.sub.query->resultInPinned && d.sub.query->resultDev ? "device" : "host");
+        }
+        account(d.sub);
+    }
+    for (NljState& n : q.nljs) {                     // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
+        if (!n.sub.query || !n.outerSrc) continue;   // (a join of an inner side: that side's query runs it)
+        const int64_t outer = n.outerSrc->nRows;
+        if (!n.sub.external) runNestedLoopsInner(n, outer > 0);      // (an empty outer side needs no inner rows)
+        account(n.sub);
+        if (n.sub.external) continue;
+        bindNestedLoops(q, n, outer, n.nInner);
+        const Query& in = *n.sub.query;
+        for (size_t k = 0; k < n.innerSchema.size() && n.nInner > 0; k++) {
+            const void* src = in.dMatCols[(size_t)n.innerCol[k]];
+            RSQ_HIP(hipMemcpyAsync(n.sub.dCols[k], src, (size_t)n.nInner * (size_t)columnWidth(n.innerSchema[k].type), hipMemcpyDefault, ctx.stream));
+        }
     }
 }
 
@@ -952,15 +912,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
-    if (!q.derived.empty() && !q.derivedExternal) prepareDerived(q);          // (the interpreters decline plans over derived tables: generic*.cpp)
-    else if (q.derivedExternal)                     // (engine_derived_multi.cpp built and bound them: its work for this shard is this execution's)
-        for (const DerivedState& d : q.derived) { q.report.num_kernels += d.extKernels; q.report.bytes_read += d.extBytes; }
-    // (nested-loops plans never run on the interpreters: generic*.cpp decline them)
-    if (!q.nljs.empty() && !q.nljExternal) prepareNestedLoops(q);
-    else if (q.nljExternal) {                        // (multi.cpp ran and bound the inner side: its work is part of this execution's)
-        const NljState& n = topNestedLoops(q);
-        q.report.num_kernels += n.innerKernels; q.report.bytes_read += n.innerBytes;
-    }
+    runSubQueries(q);
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
         // the full kernels are in the cache now: the quick tier's are replaced (same arguments, same tables - nothing else changes).
         // (A full tier that failed to compile leaves the query on the quick one.)
@@ -1755,7 +1707,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
 
 void finalizeQuery(Query& q) {
     Context& ctx = q.ctx;
-    if (!q.derived.empty() && !q.derivedExternal) refuseDerived(q, "finalize");
+    if (!q.derived.empty() && !derivedExternal(q)) refuseDerived(q, "finalize");
     if (!denseMode(q)) failUnsupported("partial execution / finalize is available for dense aggregations only");
     RSQ_HIP(hipSetDevice(ctx.device));
     double t1 = nowMs();

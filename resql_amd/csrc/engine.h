@@ -346,20 +346,9 @@ size_t tableStatsBytes(const Table& t);
 void exportTableStats(const Table& t, void* buf, size_t bytes);
 void unifyShardStats(Table& t, const void* blobs, int nShards, size_t blobBytes);
 bool queryOrderedWithLimit(const Query& q);             // ORDER BY ... LIMIT k at the root
-// Nested-loops joins across shards (multi.cpp; engine.cpp prepareNestedLoops is the one-context form).  The plan's top-level join: the
-// table its outer pipeline scans; then per execution: the inner side run on this shard (`run` false: no rows), the pair budget and the
-// bound columns sized for the whole statement, and the device columns of this shard's inner part and of the bound (gathered) inner side.
-// With setNestedLoopsExternal, executeQuery runs the outer side only; `gathered` (may be null) is a table every shard sees whole through
-// the inner side (it never proves shards disjoint in a group key).
-bool queryHasNestedLoops(const Query& q);
-const Table* nestedLoopsOuterSource(Query& q);
-void setNestedLoopsExternal(Query& q, const Table* gathered);
-void nestedLoopsRunInner(Query& q, bool run, int64_t* rows, uint64_t* kernels, uint64_t* bytes);
-void nestedLoopsBind(Query& q, int64_t outerRows, int64_t innerRows);
-void nestedLoopsColumns(Query& q, std::vector<const void*>* part, std::vector<void*>* bound, std::vector<size_t>* widths);
 bool queryHasDerived(const Query& q);                   // the plan has a derived aggregation (engine_internal.h DerivedState)
 [[noreturn]] void refuseDerived(const Query& q, const std::string& what);      // RSQ_ERR_UNSUPPORTED naming the plan's derived aggregation
-// Derived aggregations across shards (engine_derived_multi.cpp; engine.cpp prepareDerived is the one-context form).  `qs`: one compiled
+// Derived aggregations across shards (engine_derived_multi.cpp; engine.cpp buildDerived is the one-context form).  `qs`: one compiled
 // query per shard, same plan; `tables` [shard][nTables]; `sharded[t]`: table t's instances differ between the shards.  The plan step
 // decides every derived table's split (local / merged, sliced / whole) or refuses naming the table, and marks the queries so that
 // executeQuery leaves their derived tables to the run step, which builds them on every shard (innermost first).
@@ -367,6 +356,9 @@ typedef std::function<void(const std::function<void(int)>&)> ShardThreads;     /
 struct DerivedMultiRun { int64_t exchangeBytes = 0; double exchangeMs = 0; std::string text; };
 std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* const* tables, int nTables, const std::vector<bool>& sharded);
 void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out);
+// multi.cpp: `bytes` from device memory on srcDevice to device memory on dstDevice, enqueued on `stream` (dstDevice's): a device-to-device
+// copy when both are one device, else a peer copy
+void copyDeviceAsync(void* dst, int dstDevice, const void* src, int srcDevice, size_t bytes, hipStream_t stream);
 bool queryAsyncCapable(const Query& q);                 // every pipeline can be enqueued without the host in between
 bool queryIsDense(const Query& q);              // its aggregation ends in a dense partial table ([min | max | sum] words)
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr);

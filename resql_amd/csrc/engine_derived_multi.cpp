@@ -53,11 +53,11 @@ struct Planner {
     void classify(const std::vector<Query*>& qs, const std::string& prefix, std::string& text) {
         for (size_t k = 0; k < qs[0]->derived.size(); k++) {
             std::vector<Query*> subs;
-            for (Query* q : qs) { subs.push_back(q->derived[k].sub.get()); q->derived[k].sub->derivedExternal = true; }
+            for (Query* q : qs) { subs.push_back(q->derived[k].sub.query.get()); q->derived[k].sub.external = true; }
             DerivedState& d0 = qs[0]->derived[k];
             const std::string name = prefix + d0.table->name;
             classify(subs, name + "/", text);
-            Query& s = *d0.sub;
+            Query& s = *d0.sub.query;
             std::vector<OpNode*> scans;
             scansOf(s.root, scans);
             std::vector<const Table*> shardedScans;
@@ -85,22 +85,14 @@ struct Planner {
 void copyColumns(Context& root, DerivedState& from, Context& dst, DerivedState& to, int64_t r0, int64_t rows, hipEvent_t ready, int64_t* moved) {
     Table& t = *to.table;
     const int64_t n = from.table->nRows;
-    if (n > to.capacity || to.dCols.empty()) {
-        for (void* p : to.dCols) dst.free(p);
-        to.dCols.clear();
-        to.capacity = std::max<int64_t>(n + n / 8, 64);
-        for (auto& c : t.cols) to.dCols.push_back(dst.alloc((size_t)to.capacity * (size_t)columnWidth(c.type)));
-    }
+    to.sub.ensureColumns(dst, t.cols, std::max<int64_t>(n, 1), std::max<int64_t>(n + n / 8, 64));      // (engine.cpp writeDerivedFrom's rule)
     RSQ_HIP(hipSetDevice(dst.device));
     RSQ_HIP(hipStreamWaitEvent(dst.stream, ready, 0));
     for (size_t c = 0; c < t.cols.size(); c++) {
         const size_t w = (size_t)columnWidth(t.cols[c].type);
-        t.cols[c].dptr = to.dCols[c];
+        t.cols[c].dptr = to.sub.dCols[c];
         if (rows <= 0) continue;
-        char* out = (char*)to.dCols[c] + (size_t)r0 * w;
-        const char* in = (const char*)from.dCols[c] + (size_t)r0 * w;
-        if (dst.device == root.device) RSQ_HIP(hipMemcpyAsync(out, in, (size_t)rows * w, hipMemcpyDeviceToDevice, dst.stream));
-        else RSQ_HIP(hipMemcpyPeerAsync(out, dst.device, in, root.device, (size_t)rows * w, dst.stream));
+        copyDeviceAsync((char*)to.sub.dCols[c] + (size_t)r0 * w, dst.device, (const char*)from.sub.dCols[c] + (size_t)r0 * w, root.device, (size_t)rows * w, dst.stream);
         *moved += (int64_t)((size_t)rows * w);
     }
     t.nRows = n; t.row0 = 0; t.nRowsTotal = -1;
@@ -113,7 +105,7 @@ void applySlice(DerivedState& d) {
     const int64_t n = t.nRows;
     int64_t r0 = 0, rows = 0;
     rsq_multi_shard_rows(n, d.sliceShards, d.sliceAt, &r0, &rows);
-    for (size_t c = 0; c < t.cols.size(); c++) t.cols[c].dptr = (char*)d.dCols[c] + (size_t)r0 * (size_t)columnWidth(t.cols[c].type);
+    for (size_t c = 0; c < t.cols.size(); c++) t.cols[c].dptr = (char*)d.sub.dCols[c] + (size_t)r0 * (size_t)columnWidth(t.cols[c].type);
     t.row0 = r0; t.nRows = rows; t.nRowsTotal = n;
 }
 
@@ -139,18 +131,14 @@ struct Runner {
         const int n = (int)qs.size();
         for (size_t k = 0; k < qs[0]->derived.size(); k++) {
             std::vector<Query*> subs;
-            for (Query* q : qs) subs.push_back(q->derived[k].sub.get());
+            for (Query* q : qs) subs.push_back(q->derived[k].sub.query.get());
             run(subs, prefix + qs[0]->derived[k].table->name + "/");      // (the tables below it first)
             const std::string name = prefix + qs[0]->derived[k].table->name;
             if (qs[0]->derived[k].multi == LOCAL || n == 1) {
                 (*onThreads)([&](int i) {
                     Query& q = *qs[(size_t)i];
-                    DerivedState& d = q.derived[k];
-                    Query& s = *d.sub;
-                    executeQuery(s, false);
-                    d.extKernels = s.report.num_kernels; d.extBytes = s.report.bytes_read;
-                    writeDerivedFrom(q, d, s, true, &d.extKernels, &d.extBytes);
-                    applySlice(d);
+                    buildDerived(q, q.derived[k]);
+                    applySlice(q.derived[k]);
                 });
                 if (trace) fprintf(stderr, "[rsq trace] %s: %lld rows, local on %d shards\n", name.c_str(), (long long)qs[0]->derived[k].table->totalRows(), n);
                 describe(name, "local", qs[0]->derived[k], -1);
@@ -169,7 +157,7 @@ struct Runner {
         const int n = (int)qs.size();
         Query& q0 = *qs[0];
         DerivedState& d0 = q0.derived[k];
-        Query& s0 = *d0.sub;
+        Query& s0 = *d0.sub.query;
         Context& root = q0.ctx;
         const bool dense = queryIsDense(s0);
         std::vector<hipEvent_t> done((size_t)n, nullptr);
@@ -181,12 +169,11 @@ struct Runner {
         try {
             // every shard's sub-query up to its group rows (hash) or its partial table (dense)
             (*onThreads)([&](int i) {
-                Query& s = *qs[(size_t)i]->derived[k].sub;
+                SubQuery& sub = qs[(size_t)i]->derived[k].sub;
+                Query& s = *sub.query;
                 RSQ_HIP(hipSetDevice(s.ctx.device));
-                if (dense) executeQuery(s, true);
-                else { setHoldTail(s, true); s.holdTailOnDevice = true; executeQuery(s, false); }
-                DerivedState& d = qs[(size_t)i]->derived[k];
-                d.extKernels = s.report.num_kernels; d.extBytes = s.report.bytes_read;
+                if (!dense) { setHoldTail(s, true); s.holdTailOnDevice = true; }
+                runSubQuery(sub, dense);
                 RSQ_HIP(hipEventCreateWithFlags(&done[(size_t)i], hipEventDisableTiming));
                 RSQ_HIP(hipEventRecord(done[(size_t)i], s.ctx.stream));
             });
@@ -198,7 +185,7 @@ struct Runner {
             // the root's columns, then every other shard's: copies of the root's (tuples on the root's device) or its own writer over the uploaded tuples
             const bool devTuples = s0.resultInPinned && s0.resultDev != nullptr;
             RSQ_HIP(hipSetDevice(root.device));
-            writeDerivedFrom(q0, d0, s0, true, &d0.extKernels, &d0.extBytes);
+            writeDerivedFrom(q0, d0, s0, true);
             RSQ_HIP(hipEventCreateWithFlags(&written, hipEventDisableTiming));
             RSQ_HIP(hipEventRecord(written, root.stream));
             const int64_t rows = d0.table->nRows;
@@ -211,7 +198,7 @@ struct Runner {
                     copyColumns(root, d0, q.ctx, d, r0, nr, written, &moved);
                 } else {
                     RSQ_HIP(hipSetDevice(q.ctx.device));
-                    writeDerivedFrom(q, d, s0, false, &d.extKernels, &d.extBytes);
+                    writeDerivedFrom(q, d, s0, false);
                 }
             }
             for (int i = 0; i < n; i++) applySlice(qs[(size_t)i]->derived[k]);
@@ -230,7 +217,7 @@ struct Runner {
     // partial tables -> the root's gather buffer (peer copies in shard order) -> the engine's merge kernel -> the root's tail
     std::string exchangeDense(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
         const int n = (int)qs.size();
-        Query& s0 = *qs[0]->derived[k].sub;
+        Query& s0 = *qs[0]->derived[k].sub.query;
         Context& root = s0.ctx;
         int64_t nMin, nMax, nSum; void* p0;
         queryDenseLayout(s0, &nMin, &nMax, &nSum, &p0);
@@ -238,20 +225,19 @@ struct Runner {
         int64_t* gathered = (int64_t*)mergeBuffer(root, qs[0]->derived[k], (size_t)n * (size_t)words * 8);
         RSQ_HIP(hipSetDevice(root.device));
         for (int i = 0; i < n; i++) {
-            Query& s = *qs[(size_t)i]->derived[k].sub;
+            Query& s = *qs[(size_t)i]->derived[k].sub.query;
             int64_t a, b, c; void* part;
             queryDenseLayout(s, &a, &b, &c, &part);
             if (a != nMin || b != nMax || c != nSum) throw Error(RSQ_ERR_RUNTIME, "internal: shards disagree on the partial table of a derived aggregation");
             RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
             int64_t* to = gathered + (size_t)i * (size_t)words;
-            if (s.ctx.device == root.device) RSQ_HIP(hipMemcpyAsync(to, part, (size_t)words * 8, hipMemcpyDeviceToDevice, root.stream));
-            else RSQ_HIP(hipMemcpyPeerAsync(to, root.device, part, s.ctx.device, (size_t)words * 8, root.stream));
+            copyDeviceAsync(to, root.device, part, s.ctx.device, (size_t)words * 8, root.stream);
             if (i > 0) moved += words * 8;
         }
         mergePartialsAsync(root, gathered, n, words, nMin, nMax, nSum, (int64_t*)p0);
         const uint64_t before = s0.report.num_kernels;
         finalizeQuery(s0);
-        qs[0]->derived[k].extKernels += 1 + (s0.report.num_kernels >= before ? s0.report.num_kernels - before : 0);      // (the merge and the tail's launches)
+        qs[0]->derived[k].sub.kernels += 1 + (s0.report.num_kernels >= before ? s0.report.num_kernels - before : 0);      // (the merge and the tail's launches)
         return s0.resultInPinned && s0.resultDev ? "on the device (dense partial tables)" : "on the host (dense partial tables, merge kernel on the device)";
     }
 
@@ -259,12 +245,12 @@ struct Runner {
     std::string exchangeRows(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
         const int n = (int)qs.size();
         DerivedState& d0 = qs[0]->derived[k];
-        Query& s0 = *d0.sub;
+        Query& s0 = *d0.sub.query;
         Context& root = s0.ctx;
         std::vector<Query*> subs;
         int64_t total = 0;
         for (Query* q : qs) {
-            Query& s = *q->derived[k].sub;
+            Query& s = *q->derived[k].sub.query;
             if (s.groupRowWords != s0.groupRowWords || s.aggMode != s0.aggMode) throw Error(RSQ_ERR_RUNTIME, "internal: shards disagree on the group rows of a derived aggregation");
             subs.push_back(&s);
             total += s.nGroupRows;
@@ -299,8 +285,7 @@ struct Runner {
             RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
             const size_t b = (size_t)s.nGroupRows * (size_t)stride * 8;
             if (b) {
-                if (s.ctx.device == root.device) RSQ_HIP(hipMemcpyAsync(gathered + (size_t)at * (size_t)stride, s.dGroupRows, b, hipMemcpyDeviceToDevice, root.stream));
-                else RSQ_HIP(hipMemcpyPeerAsync(gathered + (size_t)at * (size_t)stride, root.device, s.dGroupRows, s.ctx.device, b, root.stream));
+                copyDeviceAsync(gathered + (size_t)at * (size_t)stride, root.device, s.dGroupRows, s.ctx.device, b, root.stream);
                 if (i > 0) moved += (int64_t)b;
             }
             at += s.nGroupRows;
@@ -313,12 +298,12 @@ struct Runner {
         waitForStream(root);
         if (err) { root.errWordClean = false; checkDeviceError(err); }
         if (groups > (uint64_t)total) throw Error(RSQ_ERR_RUNTIME, "internal: the merge across shards made more groups than it was given rows");
-        d0.extKernels += 5;
-        d0.extBytes += (uint64_t)rowBytes;
+        d0.sub.kernels += 5;
+        d0.sub.bytes += (uint64_t)rowBytes;
         s0.resultInPinned = false; s0.resultDev = nullptr;
         const uint64_t before = s0.report.num_kernels;
         runRowsDeviceTail(s0, (int64_t)groups, mergedRows);
-        d0.extKernels += s0.report.num_kernels - before;      // (the device tail counts its launches in the sub-query's report)
+        d0.sub.kernels += s0.report.num_kernels - before;      // (the device tail counts its launches in the sub-query's report)
         return "on the device";
     }
 };
@@ -330,8 +315,7 @@ std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* co
     P.sharded = &sharded;
     for (int t = 0; t < nTables; t++) P.index[reinterpret_cast<const Table*>(tables[t])] = t;
     std::string text;
-    P.classify(qs, "", text);
-    for (Query* q : qs) q->derivedExternal = true;
+    P.classify(qs, "", text);      // (it marks every derived table, at every level, as built by runDerivedAcrossShards)
     // the parent's tables: a sharded one must be the source of the last pipeline (the caller's shard, as every rsq_multi_* plan)
     Query& q0 = *qs[0];
     const Table* last = q0.pipelines.empty() ? nullptr : q0.pipelines.back().src;

@@ -265,40 +265,55 @@ struct Pipeline {
 struct TailState;
 void destroyTailState(TailState* t);
 
-// A nested-loops join (operators/nestedloopsjoin.h).  Its left child, the inner side, is a query of its own (compiled with the statement:
-// MATERIALIZE over the left subtree, every attribute); its result columns are copied into query-owned device columns before the pipeline
-// of the right child, the outer side, runs.  That pipeline pairs each of its rows with every inner row in inner order (codegen.cpp).
+// A sub-query: a subtree cut out of the plan and compiled as a query of its own (engine.cpp compileSubQuery: MATERIALIZE over it, every
+// attribute, no limit).  It runs in front of this query's pipelines at every execution, and its rows go to device columns this query owns.
+struct SubQuery {
+    std::unique_ptr<Query> query;
+    std::vector<void*> dCols;        // [capacity] per column, from the context's arena
+    int64_t capacity = 0;
+    uint64_t kernels = 0, bytes = 0; // what its last run launched and read (with what the caller added: the writer's, the exchange's)
+    bool external = false;           // rsq_multi_*: multi.cpp / engine_derived_multi.cpp run it (and fill the columns) in front of the execution
+
+    // columns of at least `rows` rows: when they hold fewer, they are given back and `newCapacity` rows allocated per column (contents dropped)
+    template <class Columns>         // (Schema, Table::cols)
+    void ensureColumns(Context& ctx, const Columns& cols, int64_t rows, int64_t newCapacity) {
+        if (rows <= capacity) return;
+        for (void* p : dCols) ctx.free(p);
+        dCols.clear();
+        capacity = newCapacity;
+        for (auto& c : cols) dCols.push_back(ctx.alloc((size_t)capacity * (size_t)columnWidth(c.type)));
+    }
+    void freeColumns(Context& ctx) { for (void* p : dCols) ctx.free(p); dCols.clear(); capacity = 0; }
+};
+
+// A nested-loops join (operators/nestedloopsjoin.h).  Its left child, the inner side, is a sub-query; its result columns are copied into
+// the sub-query's columns before the pipeline of the right child, the outer side, runs.  That pipeline pairs each of its rows with every
+// inner row in inner order (codegen.cpp).
 struct NljState {
     OpNode* op = nullptr;
-    std::unique_ptr<Query> inner;
+    SubQuery sub;                    // the inner side, columns per bound attribute (query null: a join inside another one's inner side, which that side compiles)
     Schema innerSchema;              // the inner attributes the pair loop binds (all of them for `select *`)
-    std::vector<int> innerCol;       // ... their column in inner->resultSchema
+    std::vector<int> innerCol;       // ... their column in sub.query->resultSchema
     const Table* outerSrc = nullptr; // the table the outer pipeline scans (the pair budget counts its rows)
     int pipeline = -1;               // index of that pipeline in Query::pipelines
-    std::vector<void*> dCols;        // device columns [innerCapacity] per bound attribute
-    int64_t innerCapacity = 0;
     int64_t nInner = 0;              // rows of the inner side in this execution (across GPUs: of the whole inner side, all shards' parts)
-    uint64_t innerKernels = 0, innerBytes = 0;      // what the inner side's own execution launched and read
 };
 
 // A derived aggregation: an AGGREGATION with an ancestor other than PROJECTION / MATERIALIZE / ORDERBY (aggregation.h:298-343 hands its
-// groups to whatever parent it has).  Its subtree is a query of its own (MATERIALIZE over it, every attribute, no limit), and the node is
-// replaced by a scan of the derived table: the sub-query's rows - group values, then aggregates, AVG merged - in the reference's emission
-// order, one device column per attribute at columnWidth (strings by value).  The sub-query runs in front of this query's pipelines at
-// every execution; the writer kernel (aot_kernels.hip k_derived_columns) turns its packed tuples into the columns.
+// groups to whatever parent it has).  Its subtree is a sub-query, and the node is replaced by a scan of the derived table: the sub-query's
+// rows - group values, then aggregates, AVG merged - in the reference's emission order, one device column per attribute at columnWidth
+// (strings by value).  The writer kernel (aot_kernels.hip k_derived_columns) turns the sub-query's packed tuples into the columns.
 struct DerivedState {
     OpNode* op = nullptr;            // the scan that stands where the aggregation stood
     std::vector<Expr*> groups, aggs; // the aggregation's expressions in this query (their names are the derived table's column names)
-    std::unique_ptr<Query> sub;
+    SubQuery sub;                    // columns: one per table column
     std::unique_ptr<Table> table;    // columns without statistics; nRows and column addresses are set per execution
-    std::vector<void*> dCols;        // [capacity] per column, from the context's arena
     void* dTuples = nullptr;         // the host tail's tuples uploaded for the writer
-    int64_t capacity = 0, tupleCapacity = 0;
+    int64_t tupleCapacity = 0;
     bool named = false;              // the walker has given this query's names to the columns
-    // rsq_multi_* (engine_derived_multi.cpp): how the table is split across shards, and what the run step did for it
-    int multi = 0;                   // 0 one context (prepareDerived); 1 local: every shard computes it; 2 merged: the shards' groups are merged
+    // rsq_multi_* (engine_derived_multi.cpp): how the table is split across shards
+    int multi = 0;                   // 0 one context (buildDerived); 1 local: every shard computes it; 2 merged: the shards' groups are merged
     int sliceShards = 0, sliceAt = 0;      // > 0: this shard scans rows rsq_multi_shard_rows(rows, sliceShards, sliceAt) of it
-    uint64_t extKernels = 0, extBytes = 0; // the run step's work for this shard (the sub-query's, the writer's, the exchange's)
     void* dMerge = nullptr; int64_t mergeCapacity = 0;      // merged, root only: the gathered rows / partial tables, merge scratch, merged rows
 };
 
@@ -317,12 +332,8 @@ struct Query {
     std::vector<std::unique_ptr<HashTable>> hashTables;
     std::vector<NljState> nljs;            // nested-loops joins (OpNode::nlj)
     std::vector<DerivedState> derived;     // derived aggregations, innermost sub-queries inside theirs (OpNode::derived)
-    // rsq_multi_*: the inner side of the top-level nested-loops join is run and bound by multi.cpp (nestedLoops* in engine.h) in front of
-    // the execution, which then runs the outer side only.  `gatheredTables`: tables whose rows every shard sees through that inner side.
-    bool nljExternal = false;
-    bool derivedExternal = false;          // rsq_multi_*: the derived tables are built and bound by engine_derived_multi.cpp in front of the execution
-    bool holdTailOnDevice = false;         // ... and a held tail leaves its group rows on the device only (the merge across shards reads them there)
-    std::vector<const Table*> gatheredTables;
+    bool holdTailOnDevice = false;         // rsq_multi_*: a held tail leaves its group rows on the device only (the merge across shards reads them there)
+    std::vector<const Table*> gatheredTables;      // rsq_multi_*: tables whose rows every shard sees through the gathered inner side of a nested-loops join
     OpNode* agg = nullptr;                 // the aggregation whose input pipeline runs on the device (may be null)
     AggMode aggMode = AggMode::NONE;
     std::vector<DenseKey> denseKeys;
@@ -567,6 +578,15 @@ double runDenseDeviceTail(Query& q);
 bool rowsDeviceTailWanted(Query& q, int64_t n);
 double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows = nullptr);      // (groupRows: rows other than q.dGroupRows, same layout)
 void fetchHeldGroupRows(Query& q);        // the group rows a held tail left on the device, to q.hGroupRows (engine.cpp)
-void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples, uint64_t* kernels, uint64_t* bytes);   // engine.cpp
+// engine.cpp: sub-queries (SubQuery).  runSubQuery executes one and records its work; buildDerived runs a derived table's sub-query and
+// writes the table; writeDerivedFrom writes d's columns on q's context from s's packed tuples (d's own sub-query's, or the root's after
+// a merge across shards), adding the writer's work to d.sub's.  The nested-loops steps: the plan's top-level join (multi.cpp accepts no
+// other plan), its inner side run (`run` false: no rows), and the pair budget and the bound columns sized for `nInner` inner rows.
+void runSubQuery(SubQuery& s, bool partialOnly = false);
+void buildDerived(Query& q, DerivedState& d);
+void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples);
+NljState& topNestedLoops(Query& q);
+void runNestedLoopsInner(NljState& n, bool run);
+void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner);
 
 }  // namespace rsq

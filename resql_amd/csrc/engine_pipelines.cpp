@@ -44,7 +44,7 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
         size_t k = (size_t)atoi(a.name.c_str() + 1);
         return k < q.dMatCols.size() ? (uint64_t)(uintptr_t)q.dMatCols[k] : 0;
     }
-    if (p.src && p.src->derived) {                  // a derived table: its row count and columns are this execution's (engine.cpp prepareDerived)
+    if (p.src && p.src->derived) {                  // a derived table: its row count and columns are this execution's (engine.cpp runSubQueries)
         if (a.name == "n_rows") return (uint64_t)p.src->nRows;
         if (a.name == "row0") return (uint64_t)p.src->row0;      // (0, or the start of this shard's slice across GPUs: engine_derived_multi.cpp)
         if (a.name.size() >= 2 && a.name[0] == 'c' && isdigit((unsigned char)a.name[1])) {
@@ -57,7 +57,7 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
         const NljState& n = q.nljs[(size_t)atoi(a.name.c_str() + 3)];
         if (a.name.compare(us, 2, "_n") == 0) return (uint64_t)n.nInner;
         const size_t k = (size_t)atoi(a.name.c_str() + us + 2);
-        return k < n.dCols.size() ? (uint64_t)(uintptr_t)n.dCols[k] : 0;
+        return k < n.sub.dCols.size() ? (uint64_t)(uintptr_t)n.sub.dCols[k] : 0;
     }
     if (a.name.compare(0, 2, "ht") == 0) {
         size_t us = a.name.find('_');

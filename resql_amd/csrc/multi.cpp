@@ -24,7 +24,7 @@
 #include <set>
 #include <thread>
 
-#include "engine.h"
+#include "engine_internal.h"
 
 using namespace rsq;
 
@@ -119,7 +119,24 @@ struct rsq_multi_query {
     }
 };
 
+void rsq::copyDeviceAsync(void* dst, int dstDevice, const void* src, int srcDevice, size_t bytes, hipStream_t stream) {
+    if (dstDevice == srcDevice) RSQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+    else RSQ_HIP(hipMemcpyPeerAsync(dst, dstDevice, src, srcDevice, bytes, stream));
+}
+
 namespace {
+
+// peer copies between distinct GPUs: direct over xGMI where the pair allows it
+void enablePeerAccess(rsq_multi& m) {
+    const size_t n = m.devices.size();
+    for (size_t j = 0; j < n; j++)
+        for (size_t i = 0; i < n; i++) {
+            int can = 0;
+            if (m.devices[i] == m.devices[j] || hipDeviceCanAccessPeer(&can, m.devices[j], m.devices[i]) != hipSuccess || !can) continue;
+            RSQ_HIP(hipSetDevice(m.devices[j]));
+            if (hipDeviceEnablePeerAccess(m.devices[i], 0) != hipSuccess) (void)hipGetLastError();
+        }
+}
 
 template <typename F>
 int guardedM(rsq_multi* m, F&& f) {
@@ -179,10 +196,7 @@ void enqueueMergeUntimed(rsq_multi_query& mq) {
             RSQ_HIP(hipStreamWaitEvent(root.stream, mq.ready[(size_t)i], 0));
         }
         RSQ_HIP(hipSetDevice(root.device));
-        if (c.device == root.device)
-            RSQ_HIP(hipMemcpyAsync(mq.gathered + (size_t)i * (size_t)words, part[(size_t)i], (size_t)words * 8, hipMemcpyDeviceToDevice, root.stream));
-        else
-            RSQ_HIP(hipMemcpyPeerAsync(mq.gathered + (size_t)i * (size_t)words, root.device, part[(size_t)i], c.device, (size_t)words * 8, root.stream));
+        copyDeviceAsync(mq.gathered + (size_t)i * (size_t)words, root.device, part[(size_t)i], c.device, (size_t)words * 8, root.stream);
     }
     mergePartialsAsync(root, mq.gathered, n, words, mq.nMin, mq.nMax, mq.nSum, part[0]);
 }
@@ -301,14 +315,15 @@ template <typename OnThreads>
 void executeNestedLoops(rsq_multi_query& mq, OnThreads&& onThreads) {
     rsq_multi& m = *mq.m;
     const int n = (int)m.ctxs.size();
+    std::vector<NljState*> nl((size_t)n);
     int64_t outer = 0;
-    for (Query* q : mq.qs) outer += nestedLoopsOuterSource(*q)->nRows;
+    for (int i = 0; i < n; i++) { nl[(size_t)i] = &topNestedLoops(*mq.qs[(size_t)i]); outer += nl[(size_t)i]->outerSrc->nRows; }
     // (a shard whose outer slice is empty still makes its inner part for the others)
     std::vector<int64_t> rows((size_t)n, 0);
-    std::vector<uint64_t> kernels((size_t)n, 0), bytes((size_t)n, 0);
     onThreads([&](int i) {
-        Query& q = *mq.qs[(size_t)i];
-        nestedLoopsRunInner(q, outer > 0, &rows[(size_t)i], &kernels[(size_t)i], &bytes[(size_t)i]);
+        RSQ_HIP(hipSetDevice(m.ctxs[(size_t)i]->device));
+        runNestedLoopsInner(*nl[(size_t)i], outer > 0);
+        rows[(size_t)i] = nl[(size_t)i]->nInner;
         RSQ_HIP(hipEventRecord(mq.innerDone[(size_t)i], m.ctxs[(size_t)i]->stream));
     });
     int64_t inner = 0;
@@ -319,33 +334,30 @@ void executeNestedLoops(rsq_multi_query& mq, OnThreads&& onThreads) {
         inner = mq.nljGathered ? inner + rows[(size_t)i] : rows[0];
     }
     try {
-        for (Query* q : mq.qs) nestedLoopsBind(*q, outer, inner);
+        for (int i = 0; i < n; i++) { RSQ_HIP(hipSetDevice(m.ctxs[(size_t)i]->device)); bindNestedLoops(*mq.qs[(size_t)i], *nl[(size_t)i], outer, inner); }
     } catch (const Error&) {
         // refused before any outer pipeline: the report holds the inner sides' work
         mq.report = rsq_report{};
-        for (int i = 0; i < n; i++) { mq.report.num_kernels += (int32_t)kernels[(size_t)i]; mq.report.bytes_read += bytes[(size_t)i]; }
+        for (int i = 0; i < n; i++) { mq.report.num_kernels += (int32_t)nl[(size_t)i]->sub.kernels; mq.report.bytes_read += nl[(size_t)i]->sub.bytes; }
         throw;
     }
     // the bound columns of shard j: the parts of all shards back to back (gathered), or its own inner side
-    std::vector<std::vector<const void*>> part((size_t)n);
-    std::vector<std::vector<void*>> bound((size_t)n);
-    std::vector<size_t> width;
-    for (int i = 0; i < n; i++) nestedLoopsColumns(*mq.qs[(size_t)i], &part[(size_t)i], &bound[(size_t)i], &width);
     mq.gatherBytes = 0;
     for (int j = 0; j < n; j++) {
         Context& dst = *m.ctxs[(size_t)j];
+        const NljState& to = *nl[(size_t)j];
         RSQ_HIP(hipSetDevice(dst.device));
         if (mq.nljGathered) RSQ_HIP(hipEventRecord(mq.gather0[(size_t)j], dst.stream));
         int64_t at = 0;
         for (int i = 0; i < n; i++) {
             if (!mq.nljGathered && i != j) continue;
             const Context& src = *m.ctxs[(size_t)i];
+            const NljState& from = *nl[(size_t)i];
             if (i != j && rows[(size_t)i] > 0) RSQ_HIP(hipStreamWaitEvent(dst.stream, mq.innerDone[(size_t)i], 0));
-            for (size_t k = 0; k < width.size() && rows[(size_t)i] > 0; k++) {
-                char* to = (char*)bound[(size_t)j][k] + (size_t)at * width[k];
-                const size_t b = (size_t)rows[(size_t)i] * width[k];
-                if (src.device == dst.device) RSQ_HIP(hipMemcpyAsync(to, part[(size_t)i][k], b, hipMemcpyDeviceToDevice, dst.stream));
-                else RSQ_HIP(hipMemcpyPeerAsync(to, dst.device, part[(size_t)i][k], src.device, b, dst.stream));
+            for (size_t k = 0; k < to.innerSchema.size() && rows[(size_t)i] > 0; k++) {
+                const size_t w = (size_t)columnWidth(to.innerSchema[k].type);
+                const size_t b = (size_t)rows[(size_t)i] * w;
+                copyDeviceAsync((char*)to.sub.dCols[k] + (size_t)at * w, dst.device, from.sub.query->dMatCols[(size_t)from.innerCol[k]], src.device, b, dst.stream);
                 if (i != j) mq.gatherBytes += (int64_t)b;
             }
             at += rows[(size_t)i];
@@ -582,22 +594,18 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 }
                 Query* q = compileQuery(*m->ctxs[(size_t)i], p, ts.data(), nt);
                 mq->qs.push_back(q);
-                if (nestedLoopsOuterSource(*q) != outer)
+                NljState& top = topNestedLoops(*q);
+                if (top.outerSrc != outer)
                     throw Error(RSQ_ERR_RUNTIME, "internal: the nested-loops join's outer pipeline does not scan table " + outer->name);
-                setNestedLoopsExternal(*q, gatheredTable >= 0 ? reinterpret_cast<const Table*>(ts[(size_t)gatheredTable]) : nullptr);
+                // (executeQuery runs the outer side only; the gathered table is seen whole by every shard: it never proves shards disjoint in a group key)
+                top.sub.external = true;
+                if (gatheredTable >= 0) q->gatheredTables.push_back(reinterpret_cast<const Table*>(ts[(size_t)gatheredTable]));
                 RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device));
                 RSQ_HIP(hipEventCreateWithFlags(&mq->innerDone[(size_t)i], hipEventDisableTiming));
                 RSQ_HIP(hipEventCreate(&mq->gather0[(size_t)i])); RSQ_HIP(hipEventCreate(&mq->gather1[(size_t)i]));
             }
             mq->nljGathered = gatheredTable >= 0;
-            if (mq->nljGathered)          // (peer copies between distinct GPUs: direct over xGMI where the pair allows it)
-                for (int j = 0; j < n; j++)
-                    for (int i = 0; i < n; i++) {
-                        int can = 0;
-                        if (m->devices[(size_t)i] == m->devices[(size_t)j] || hipDeviceCanAccessPeer(&can, m->devices[(size_t)j], m->devices[(size_t)i]) != hipSuccess || !can) continue;
-                        RSQ_HIP(hipSetDevice(m->devices[(size_t)j]));
-                        if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
-                    }
+            if (mq->nljGathered) enablePeerAccess(*m);
         }
         // derived aggregations: across the shards with RSQ_ENGINE_DERIVED_MULTI (never inside a nested-loops plan), else on one context only
         std::string derivedText;
@@ -605,14 +613,7 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             if (!(m->ctxs[0]->cfg.engine_flags & RSQ_ENGINE_DERIVED_MULTI) || mq->nlj) refuseDerived(*mq->qs[0], "a multi-GPU compile (rsq_multi_query_compile)");
             mq->derived = true;
             derivedText = planDerivedAcrossShards(mq->qs, tables, n_tables, sharded);
-            // (peer copies between distinct GPUs: direct over xGMI where the pair allows it)
-            for (int j = 0; j < n; j++)
-                for (int i = 0; i < n; i++) {
-                    int can = 0;
-                    if (m->devices[(size_t)i] == m->devices[(size_t)j] || hipDeviceCanAccessPeer(&can, m->devices[(size_t)j], m->devices[(size_t)i]) != hipSuccess || !can) continue;
-                    RSQ_HIP(hipSetDevice(m->devices[(size_t)j]));
-                    if (hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0) != hipSuccess) (void)hipGetLastError();
-                }
+            enablePeerAccess(*m);
         }
         mq->dense = queryIsDense(*mq->qs[0]);
         if (mq->dense) {
