@@ -85,9 +85,64 @@ static void hostStats(Table& t) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// narrow images (frame of reference + byte width): what the generated scans read instead of the wide column
+// ------------------------------------------------------------------------------------------------
+int narrowWidth(const TableColumn& c) {
+    if (!narrowScansEnabled()) return 0;
+    if (!c.owned || !c.dptr || !c.stats.valid || c.type.isString()) return 0;
+    const int tag = c.type.tag;
+    if (tag != RSQ_INT && tag != RSQ_BIGINT && tag != RSQ_DECIMAL && tag != RSQ_DATE) return 0;
+    if (c.stats.min == INT64_MIN || c.stats.max == INT64_MAX || c.stats.max < c.stats.min) return 0;
+    const uint64_t range = (uint64_t)c.stats.max - (uint64_t)c.stats.min;        // (exact: max - min of two int64 fits a uint64)
+    const int w = range <= 0xffull ? 1 : range <= 0xffffull ? 2 : range <= 0xffffffffull ? 4 : 0;
+    // A 4-byte INT is the type of keys, whose range grows with the table (TPC-H's l_orderkey: 2 bytes at SF 0.01, 4 at SF 10): a
+    // width that followed it would give one plan shape a kernel per scale, and the code-object cache filled from small tables would
+    // not serve the large ones.  INT columns are narrowed only to one byte (small domains whatever the scale); DATE, DECIMAL and
+    // BIGINT ranges follow the value domain, not the row count.
+    if (tag == RSQ_INT && w != 1) return 0;
+    return w > 0 && w < columnWidth(c.type) ? w : 0;
+}
+
+template <typename T, typename N>
+__global__ void __launch_bounds__(256) k_encode(const T* __restrict__ src, N* __restrict__ dst, i64 n, i64 base) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
+        dst[i] = (N)((u64)(i64)src[i] - (u64)base);
+}
+
+template <typename T>
+static void launchEncode(Context& ctx, const TableColumn& c, i64 n) {
+    const unsigned grid = 1024;
+    if (c.nw == 1) hipLaunchKernelGGL((k_encode<T, unsigned char>), dim3(grid), dim3(256), 0, ctx.stream, (const T*)c.dptr, (unsigned char*)c.nptr, n, (i64)c.nbase);
+    else if (c.nw == 2) hipLaunchKernelGGL((k_encode<T, unsigned short>), dim3(grid), dim3(256), 0, ctx.stream, (const T*)c.dptr, (unsigned short*)c.nptr, n, (i64)c.nbase);
+    else hipLaunchKernelGGL((k_encode<T, unsigned>), dim3(grid), dim3(256), 0, ctx.stream, (const T*)c.dptr, (unsigned*)c.nptr, n, (i64)c.nbase);
+}
+
+// (re)builds the images after the statistics: in place where width and base are what they were, else anew - and then a statement
+// compiled over the old image (its address and base are kernel arguments) is refused like one over moved columns
+static void buildNarrowImages(Context& ctx, Table& t) {
+    bool moved = false, launched = false;
+    for (auto& c : t.cols) {
+        const int w = t.nRows > 0 ? narrowWidth(c) : 0;
+        const int64_t base = w ? c.stats.min : 0;
+        const size_t bytes = w ? (((size_t)t.nRows * (size_t)w + 15) & ~(size_t)15) : 0;
+        const bool keep = ctx.device >= 0 && c.nptr && w == c.nw && base == c.nbase && bytes == c.nbytes;
+        if (!keep && c.nptr) { if (ctx.device >= 0) ctx.freeRaw(c.nptr); c.nptr = nullptr; moved = true; }
+        c.nw = w; c.nbase = base; c.nbytes = bytes;
+        if (!w || ctx.device < 0) continue;          // (a compile-only context only needs the width and the base)
+        if (!c.nptr) c.nptr = ctx.allocRaw(bytes);
+        launched = true;
+        if (c.type.tag == RSQ_INT) launchEncode<int>(ctx, c, (i64)t.nRows);
+        else if (c.type.tag == RSQ_DATE) launchEncode<unsigned>(ctx, c, (i64)t.nRows);
+        else launchEncode<i64>(ctx, c, (i64)t.nRows);
+    }
+    if (launched) { RSQ_HIP(hipGetLastError()); RSQ_HIP(hipStreamSynchronize(ctx.stream)); }
+    if (moved) t.layoutVersion++;
+}
+
 void computeColumnStats(Context& ctx, Table& t) {
-    if (ctx.device < 0) { hostStats(t); return; }
-    if (t.nRows == 0) return;
+    if (ctx.device < 0) { hostStats(t); buildNarrowImages(ctx, t); return; }
+    if (t.nRows == 0) { buildNarrowImages(ctx, t); return; }
     RSQ_HIP(hipSetDevice(ctx.device));
     i64* dmm = (i64*)ctx.alloc(4 * sizeof(i64));
     unsigned* dset = (unsigned*)ctx.alloc(8 * sizeof(unsigned));
@@ -116,6 +171,7 @@ void computeColumnStats(Context& ctx, Table& t) {
         }
     }
     ctx.free(dmm); ctx.free(dset);
+    buildNarrowImages(ctx, t);
 }
 
 // ------------------------------------------------------------------------------------------------

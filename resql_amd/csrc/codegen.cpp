@@ -143,16 +143,17 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     // workgroups (of 256 threads) per launch; 0 = 2 per CU.  Measured on MI355X (Q1 SF10): 512 workgroups 0.348 ms,
     // 768: 0.367, 1024: 0.374, 2048: 0.395, 4096: 0.448 - a streaming kernel wants exactly 2 resident workgroups per CU
     pipe.maxGrid = (unsigned)0;
-    colTypes.clear(); colIsString.clear(); rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
+    colTypes.clear(); colIsString.clear(); colNarrow.clear(); rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
     body.clear(); stateDecl.clear(); stateInit.clear(); prologue.clear(); epilogue.clear(); fileScope.clear(); helperFns.clear();
     explainSteps.clear(); indent = 1; matchSlotTable = -1; slotVar.clear(); symbolOrigin.clear(); symbolWord.clear();
     multiMatchAbove = false;
     selective = false; compacted = false; stage2Body.clear(); cqLive.clear();
     leadCond.clear(); leadCols.clear(); leadPass = 1.0; leadPassComplete = true;
     pairSplit = std::string::npos; pairCond.clear();
-    strPrefetch.clear(); strPrefetchWidth.clear(); strStaged.clear(); strStagedBytes = 0; postTile.clear(); eg.strWordVars.clear();
+    strPrefetch.clear(); strPrefetchWidth.clear(); strStaged.clear(); strStagedBytes = 0; postTile.clear(); foldTile.clear(); eg.strWordVars.clear();
     eg.symbols.clear();
     o->schema.clear();
+    const bool narrowScans = narrowScansEnabled();
     for (size_t ci = 0; ci < t->cols.size(); ci++) {
         const TableColumn& c = t->cols[ci];
         // Values::dematerialize(..., required): an empty request set means all attributes
@@ -168,6 +169,11 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
         symbolOrigin[c.name] = -1;
         o->schema.push_back({c.name, c.type});
         pipe.bytesPerRow += columnWidth(c.type);
+        // the column's narrow image where it has one (TableColumn::nw; RSQ_NARROW_SCANS=0: never): the tile registers and the row
+        // function take decoded values, only the loads see the image.  A compile-only context has the width and no image.
+        const int nw = (!t->derived && c.owned && narrowScans && !c.type.isString() && (c.nptr || q.ctx.device < 0)) ? c.nw : 0;
+        colNarrow.push_back(nw);
+        pipe.storedBytesPerRow += nw ? nw : columnWidth(c.type);
         if (c.type.isString()) {
             addArg("c" + std::to_string(k), "const char*", (uint64_t)(uintptr_t)c.dptr);
             colIsString.push_back(1); colTypes.push_back("");
@@ -175,15 +181,19 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
                  std::to_string(c.type.len) + ");");
         } else {
             std::string ct = ExprGen::ctype(c.type);
-            addArg("c" + std::to_string(k), "const " + ct + "*", (uint64_t)(uintptr_t)c.dptr);
+            if (nw) {
+                addArg("c" + std::to_string(k), std::string("const ") + (nw == 1 ? "u8" : nw == 2 ? "u16" : "u32") + "*", (uint64_t)(uintptr_t)c.nptr);
+                addArg("fb" + std::to_string(k), "i64", (uint64_t)c.nbase);      // (the frame's base is an argument: the text holds the width only)
+            } else addArg("c" + std::to_string(k), "const " + ct + "*", (uint64_t)(uintptr_t)c.dptr);
             colIsString.push_back(0); colTypes.push_back(ct);
             rowParams += ", " + ct + " " + var;
-            rowArgsTail += ", a.c" + std::to_string(k) + "[r]";
-            rowArgsTailGuarded += ", (valid ? a.c" + std::to_string(k) + "[r] : (" + ct + ")0)";
+            rowArgsTail += ", " + colAt(k, "r");
+            rowArgsTailGuarded += ", (valid ? " + colAt(k, "r") + " : (" + ct + ")0)";
         }
     }
     explainSteps.push_back("scan " + t->name + " [" + (t->derived ? std::string("rows of this execution") : std::to_string((long long)t->nRows) + " rows") + ", " +
-                           std::to_string((long long)pipe.bytesPerRow) + " B/row]");
+                           std::to_string((long long)pipe.bytesPerRow) + " B/row" +
+                           (pipe.storedBytesPerRow != pipe.bytesPerRow ? ", " + std::to_string((long long)pipe.storedBytesPerRow) + " B/row stored" : std::string()) + "]");
     consume(o->parent, o);
     finishPipeline();
 }
@@ -446,8 +456,8 @@ bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
             bitmapPrefetch.push_back({C, col, false});
             const std::string call = "rsq::bm_word(a." + C + "_bm, a." + C + "_bmmin, a." + C + "_bmbits, (i64)";
             rowParams += ", const u32 pf_" + C;
-            rowArgsTail += ", " + call + "a.c" + std::to_string(col) + "[r])";
-            rowArgsTailGuarded += ", (valid ? " + call + "a.c" + std::to_string(col) + "[r]) : 0u)";
+            rowArgsTail += ", " + call + colAt(col, "r") + ")";
+            rowArgsTailGuarded += ", (valid ? " + call + colAt(col, "r") + ") : 0u)";
             test = "rsq::bit_of_word(pf_" + C + ", (u64)((i64)(" + v1 + ") - a." + C + "_bmmin), a." + C + "_bmbits)";
         }
         if (!v1.empty()) stage1Cond += (stage1Cond.empty() ? "" : " && ") + test;
@@ -484,7 +494,7 @@ bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
         if (lazyOf[k] < 0) line(carried);
         else {
             body += "#if RSQ_LAZY\n";
-            line("const " + ExprGen::ctype(t) + " " + v + " = a.c" + std::to_string(lazyOf[k]) + "[row - a.row0];");
+            line("const " + ExprGen::ctype(t) + " " + v + " = " + colAt(lazyOf[k], "row - a.row0") + ";");
             body += "#else\n";
             line(carried);
             body += "#endif\n";

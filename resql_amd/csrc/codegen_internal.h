@@ -260,6 +260,22 @@ struct Walker {
     Pipeline pipe;
     std::vector<std::string> colTypes;        // device type per scanned (vector-loadable) column
     std::vector<int> colIsString;
+    std::vector<int> colNarrow;               // per scanned column: the byte width of the narrow image it is read from (0: the wide column)
+    // a scanned column's value in row `r` / a lane's two rows of it into `dst`: decoded where the column is read from its narrow image
+    std::string colAt(int k, const std::string& r) const {
+        const std::string K = std::to_string(k);
+        if (k < (int)colNarrow.size() && colNarrow[(size_t)k]) return "rsq::dec<" + colTypes[(size_t)k] + ">(a.c" + K + "[" + r + "], a.fb" + K + ")";
+        return "a.c" + K + "[" + r + "]";
+    }
+    std::string tileLoad(int k, const std::string& dst) const {
+        const std::string K = std::to_string(k);
+        if (k < (int)colNarrow.size() && colNarrow[(size_t)k]) return "rsq::ld2n(a.c" + K + " + b, a.fb" + K + ", " + dst + ");";
+        return "rsq::ld2(a.c" + K + " + b, " + dst + ");";
+    }
+    int storedWidth(int k) const {            // bytes per row the scan fetches of column k (non-string)
+        if (k < (int)colNarrow.size() && colNarrow[(size_t)k]) return colNarrow[(size_t)k];
+        return colTypes[(size_t)k] == "i64" ? 8 : colTypes[(size_t)k] == "i32" ? 4 : 1;
+    }
     std::string rowParams, rowArgsTail, rowArgsTailGuarded;
     // key-bitmap words fetched for both rows of a lane (and all tiles in flight) before the first row is processed:
     // (table name, scanned column index) — see consumeProbe
@@ -326,6 +342,7 @@ struct Walker {
     // is - 128 rows x W contiguous bytes per tile, 16 bytes per lane and load, every line once - and passed through the wave's own LDS
     // region, from which each lane reads its rows' words (ds_read_b64 takes any address on gfx950).  All words of the value then arrive
     // as row-function parameters.
+    std::string foldTile;                                  // code behind every tile of the tile loops: the periodic fold of 32-bit partial sums (codegen_agg.cpp)
     std::string postTile;                                  // code behind the two row_fn calls of a tile in the tile loops ($TILE = the tile's number; wave-uniform)
     std::map<int, int> strStaged;                          // scanned column -> byte offset of its tile in the wave's LDS region
     int strStagedBytes = 0;                                // bytes of that region (128 x the staged widths)

@@ -446,8 +446,8 @@ void Walker::consumeProbe(OpNode* o, OpNode* from) {
                 bitmapPrefetch.push_back({C, col, false});
                 const std::string call = "rsq::bm_word(a." + C + "_bm, a." + C + "_bmmin, a." + C + "_bmbits, (i64)";
                 rowParams += ", const u32 pf_" + C;
-                rowArgsTail += ", " + call + "a.c" + std::to_string(col) + "[r])";
-                rowArgsTailGuarded += ", (valid ? " + call + "a.c" + std::to_string(col) + "[r]) : 0u)";
+                rowArgsTail += ", " + call + colAt(col, "r") + ")";
+                rowArgsTailGuarded += ", (valid ? " + call + colAt(col, "r") + ") : 0u)";
                 openScope("if (rsq::bit_of_word(pf_" + C + ", " + d + ", a." + C + "_bmbits)) {");
             } else openScope("if (rsq::bit_in(a." + C + "_bm, " + d + ", a." + C + "_bmbits)) {");
             compScope = true;
@@ -507,8 +507,8 @@ void Walker::consumeProbe(OpNode* o, OpNode* from) {
             bitmapPrefetch.push_back({T, pfCol, ht.bmInterleaved});
             const std::string call = std::string(ht.bmInterleaved ? "rsq::bmi_load(a." : "rsq::bm_word(a.") + T + "_bm, a." + T + "_bmmin, a." + T + "_bmbits, (i64)";
             rowParams += ", const u32 pf_" + T;
-            rowArgsTail += ", " + call + "a.c" + std::to_string(pfCol) + "[r])";
-            rowArgsTailGuarded += ", (valid ? " + call + "a.c" + std::to_string(pfCol) + "[r]) : 0u)";
+            rowArgsTail += ", " + call + colAt(pfCol, "r") + ")";
+            rowArgsTailGuarded += ", (valid ? " + call + colAt(pfCol, "r") + ") : 0u)";
             openScope("if (" + T + "_d < a." + T + "_bmbits && ((pf_" + T + " >> (" + T + "_d & 31)) & 1u)) {");
         } else
         {

@@ -769,7 +769,7 @@ void executeQuery(Query& q, bool partialOnly, bool async) {
     // BULK INSERT is told to compile it again instead of being answered from freed memory.
     for (size_t i = 0; i < q.tables.size() && i < q.tableLayouts.size(); i++)
         if (q.tables[i]->layoutVersion != q.tableLayouts[i])
-            throw Error(RSQ_ERR_INVALID, "rows were appended to table " + q.tables[i]->name + " after this statement was compiled: compile it again");
+            throw Error(RSQ_ERR_INVALID, "rows were appended to table " + q.tables[i]->name + " (or its narrow column images were rebuilt) after this statement was compiled: compile it again");
     if ((partialOnly || async) && !q.derived.empty() && !(derivedExternal(q) && !async)) refuseDerived(q, "partial / asynchronous execution");
     executeQueryBody(q, partialOnly, async);
     keepKeyIndexes(q);

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <tuple>
@@ -46,7 +47,21 @@ struct TableColumn {
     void* dptr = nullptr;                      // device pointer, nullptr if the column was declared without data
     bool owned = false;
     ColumnStats stats;
+    // Narrow image (frame of reference): row i holds nbase + image[i], the image's values nw bytes wide (1, 2 or 4; 0 = none).
+    // Built with the statistics (computeColumnStats) for owned numeric columns whose range fits a narrower width; nw and nbase
+    // are set in compile-only contexts too (no nptr there), so both generate the same kernel text.  Only the scans of the
+    // generated pipelines read the image: every other reader keeps using dptr.
+    int nw = 0;
+    int64_t nbase = 0;
+    void* nptr = nullptr;
+    size_t nbytes = 0;
 };
+
+// the width of a column's narrow image: a pure function of its type, ownership and statistics (0 = none)
+int narrowWidth(const TableColumn& c);
+// RSQ_NARROW_SCANS=0: no narrow images are built and no scan reads one - the kernels and their text are what they are without them
+// (read where the images are built and where the code generator picks them; flipped by tests/test_gpu_narrow_scan.py)
+inline bool narrowScansEnabled() { const char* e = getenv("RSQ_NARROW_SCANS"); return !e || atoi(e) != 0; }
 
 struct Context;
 

@@ -240,6 +240,7 @@ struct Pipeline {
     std::vector<ArgSlot> args;
     Kernel* kernel = nullptr;
     int64_t bytesPerRow = 0;
+    int64_t storedBytesPerRow = 0;   // ... what the scan fetches of them: narrow images at their width (bytesPerRow stays the logical figure, report.bytes_read)
     bool hasStage2 = false;          // its kernel text has a stage 2 that RSQ_STAGE2_CALL turns into a real call (the quick tier of a cold compile)
     bool compact = false;            // wave-level selection compaction (codegen.cpp compactThen): carried 8-byte values
     int compactWords = 0;

@@ -404,7 +404,7 @@ void runLargeDenseAggregation(Query& q, Pipeline& p) {
     if (p.staged && !force && !sampleAlways && !p.stagedExact && p.leadPass >= 0.0) {
         const double passing = (double)rows * p.leadPass;
         const double direct = passing * (double)std::max(1, p.partAtomicsPerRow) / 25e9;
-        const double parted = (double)rows * (double)p.bytesPerRow / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 80e-6;
+        const double parted = (double)rows * (double)p.storedBytesPerRow / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 80e-6;
         if (trace) fprintf(stderr, "[rsq trace]     large dense aggregation: ~%.0f of %lld rows expected to pass (column statistics); atomics %.3f ms vs partitioned %.3f ms\n",
                            passing, (long long)rows, direct * 1e3, parted * 1e3);
         if (direct <= parted) { launchPipeline(q, p, -1); return; }
@@ -415,8 +415,8 @@ void runLargeDenseAggregation(Query& q, Pipeline& p) {
     if (!force || p.staged) {
         const double passing = (double)countPass(step) * (double)step;
         const double direct = passing * (double)std::max(1, p.partAtomicsPerRow) / 25e9;
-        const double parted = p.staged ? (double)rows * (double)p.bytesPerRow / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 80e-6
-                                       : ((double)rows * 16.0 + (double)rows * (double)p.bytesPerRow) / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 60e-6;
+        const double parted = p.staged ? (double)rows * (double)p.storedBytesPerRow / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 80e-6
+                                       : ((double)rows * 16.0 + (double)rows * (double)p.storedBytesPerRow) / 6e12 + passing * (double)recBytes * 2.0 / 4e12 + 60e-6;
         if (trace) fprintf(stderr, "[rsq trace]     large dense aggregation: ~%.0f of %lld rows pass; atomics %.3f ms vs partitioned %.3f ms\n",
                            passing, (long long)rows, direct * 1e3, parted * 1e3);
         if (!force && direct <= parted) { launchPipeline(q, p, -1); return; }

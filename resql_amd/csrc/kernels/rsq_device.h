@@ -67,6 +67,19 @@ RSQ_DEV void ld2(const i32* p, i32 (&v)[2]) { i32x2 t = *reinterpret_cast<const 
 RSQ_DEV void ld2(const u8* p, u8 (&v)[2]) { u8x2 t = *reinterpret_cast<const u8x2*>(p); v[0] = t.x; v[1] = t.y; }
 #endif
 
+// Narrow images (frame of reference): the column holds value - base in 1, 2 or 4 bytes; a lane's two rows are ONE load of 2, 4 or
+// 8 bytes, decoded into the column's type before the row function sees them (value = base + image, exact: base is the column's min)
+template <typename T, typename N> RSQ_DEV T dec(N x, i64 base) { return (T)(i64)((u64)base + (u64)x); }
+#ifdef RSQ_NT_LOADS
+#define RSQ_LD_NARROW(T, p) __builtin_nontemporal_load(reinterpret_cast<const T*>(p))
+#else
+#define RSQ_LD_NARROW(T, p) (*reinterpret_cast<const T*>(p))
+#endif
+typedef u32 u32v2 __attribute__((ext_vector_type(2)));
+template <typename T> RSQ_DEV void ld2n(const u8* p, i64 base, T (&v)[2]) { const u32 t = RSQ_LD_NARROW(u16, p); v[0] = dec<T>(t & 0xffu, base); v[1] = dec<T>(t >> 8, base); }
+template <typename T> RSQ_DEV void ld2n(const u16* p, i64 base, T (&v)[2]) { const u32 t = RSQ_LD_NARROW(u32, p); v[0] = dec<T>(t & 0xffffu, base); v[1] = dec<T>(t >> 16, base); }
+template <typename T> RSQ_DEV void ld2n(const u32* p, i64 base, T (&v)[2]) { const u32v2 t = RSQ_LD_NARROW(u32v2, p); v[0] = dec<T>(t.x, base); v[1] = dec<T>(t.y, base); }
+
 // One 128-row tile of a W-byte string column = 8 * W chunks of 16 bytes; chunk 64 * R + lane is the lane's load number R (the lanes past the
 // last chunk repeat it: an unconditional load, which the compiler's wait counting needs of every load of the tile).  Tiles start at
 // multiples of 128 rows, so the chunks are 16-byte aligned wherever the column base is.

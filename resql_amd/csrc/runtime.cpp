@@ -263,7 +263,7 @@ void Context::releaseKeyIndex(KeyIndex* k) {
 Table::~Table() {
     if (ctx) ctx->retireKeyIndexes(uid);
     if (ctx && ctx->device >= 0) {
-        for (auto& c : cols) if (c.owned && c.dptr) ctx->freeRaw(c.dptr);
+        for (auto& c : cols) { if (c.owned && c.dptr) ctx->freeRaw(c.dptr); if (c.owned && c.nptr) ctx->freeRaw(c.nptr); }
     } else {
         for (auto& c : cols) if (c.owned && c.dptr) ::free(c.dptr);
     }
