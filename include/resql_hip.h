@@ -148,6 +148,7 @@ typedef struct rsq_memory_stats {
     uint64_t plan_memo_hits;         /* queries that were compiled with a remembered entry */
     uint64_t key_index_entries;      /* key bitmaps of engine-owned key columns kept for every query over the same table version (joins whose build side is that table as it stands) */
     uint64_t key_index_bytes;        /* ... device memory they hold (part of device_used_bytes; freed with the table or when it changes) */
+    uint64_t column_image_bytes;     /* device memory of the tables' narrow and dictionary images (straight from the driver, like the columns) */
 } rsq_memory_stats;
 int  rsq_ctx_memory_stats(const rsq_ctx* ctx, rsq_memory_stats* out);
 

@@ -104,6 +104,205 @@ int narrowWidth(const TableColumn& c) {
     return w > 0 && w < columnWidth(c.type) ? w : 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// dictionary images: what the generated scans read of a string column with at most 256 distinct values (engine.h TableColumn::dict)
+// ------------------------------------------------------------------------------------------------
+enum { DICT_MAX = 256, DICT_SLOTS = 1024, DICT_SAMPLE_ROWS = 65536, DICT_COLLECT_GRID = 512 };
+
+__device__ inline unsigned dictHash(const unsigned char* p, int W) {      // FNV-1a over the W stored bytes
+    unsigned h = 2166136261u;
+    for (int i = 0; i < W; i++) h = (h ^ p[i]) * 16777619u;
+    return h;
+}
+__device__ inline bool dictSame(const unsigned char* a, const unsigned char* b, int W) {
+    for (int i = 0; i < W; i++) if (a[i] != b[i]) return false;
+    return true;
+}
+
+// The distinct values among rows [0, n) of a W-byte column.  Every workgroup keeps a set in LDS: an open-addressing table whose slots hold the
+// ROW a value was first seen in (the bytes stay where they are, so the set takes 8 KB whatever W is).  It writes the values to its slice
+// out[blockIdx.x][256][W] and their number to counts[blockIdx.x].  A workgroup that meets a 257th value raises *overflow and every workgroup
+// ends at its next round of rows.  countsIn (the union pass, whose "column" is the slices of an earlier launch): row r exists if
+// (r & 255) < countsIn[r >> 8].
+__global__ void __launch_bounds__(256) k_dict_collect(const unsigned char* __restrict__ col, i64 n, int W, const unsigned* __restrict__ countsIn,
+                                                      unsigned char* __restrict__ out, unsigned* __restrict__ counts, unsigned* overflow) {
+    __shared__ unsigned long long slot[DICT_SLOTS];
+    __shared__ unsigned cnt, wpos;
+    for (int i = threadIdx.x; i < DICT_SLOTS; i += 256) slot[i] = ~0ull;
+    if (threadIdx.x == 0) { cnt = 0; wpos = 0; }
+    __syncthreads();
+    // (no barrier inside the loop: a round adds at most 256 entries and the round after a 257th sees cnt > 256, so the table holds at most 512)
+    for (i64 base = (i64)blockIdx.x * 256; base < n; base += (i64)gridDim.x * 256) {
+        if (*(volatile unsigned*)&cnt > (unsigned)DICT_MAX || *(volatile unsigned*)overflow) break;
+        const i64 r = base + threadIdx.x;
+        if (r >= n) continue;
+        if (countsIn && (unsigned)(r & 255) >= countsIn[r >> 8]) continue;
+        const unsigned char* v = col + r * W;
+        unsigned h = dictHash(v, W) & (DICT_SLOTS - 1);
+        for (int probe = 0; probe < DICT_SLOTS; probe++, h = (h + 1) & (DICT_SLOTS - 1)) {
+            unsigned long long cur = *(volatile unsigned long long*)&slot[h];
+            if (cur == ~0ull) {
+                cur = atomicCAS(&slot[h], ~0ull, (unsigned long long)r);
+                if (cur == ~0ull) { if (atomicAdd(&cnt, 1u) >= (unsigned)DICT_MAX) atomicExch(overflow, 1u); break; }
+            }
+            if (dictSame(col + (i64)cur * W, v, W)) break;
+        }
+    }
+    __syncthreads();
+    const unsigned total = cnt;
+    if (total > (unsigned)DICT_MAX) { if (threadIdx.x == 0) counts[blockIdx.x] = 0; return; }
+    for (int i = threadIdx.x; i < DICT_SLOTS; i += 256) {
+        const unsigned long long r = slot[i];
+        if (r == ~0ull) continue;
+        const unsigned at = atomicAdd(&wpos, 1u);          // (< total <= 256: inside the slice)
+        unsigned char* o = out + ((i64)blockIdx.x * DICT_MAX + at) * W;
+        for (int b = 0; b < W; b++) o[b] = col[(i64)r * W + b];
+    }
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// codes[r] = the rank of row r's value in the sorted dictionary (N entries of W bytes).  The workgroup hashes the dictionary into LDS (entry
+// numbers; the bytes are read through the cache); a value that is not in it raises *notFound and its code is NOT written.
+__global__ void __launch_bounds__(256) k_dict_encode(const unsigned char* __restrict__ col, i64 n, int W, const unsigned char* __restrict__ dict, int N,
+                                                     unsigned char* __restrict__ codes, unsigned* notFound) {
+    __shared__ unsigned slot[DICT_SLOTS];
+    for (int i = threadIdx.x; i < DICT_SLOTS; i += 256) slot[i] = ~0u;
+    __syncthreads();
+    if ((int)threadIdx.x < N) {
+        unsigned h = dictHash(dict + (i64)threadIdx.x * W, W) & (DICT_SLOTS - 1);
+        while (atomicCAS(&slot[h], ~0u, (unsigned)threadIdx.x) != ~0u) h = (h + 1) & (DICT_SLOTS - 1);      // (at most 256 of 1024 slots are taken)
+    }
+    __syncthreads();
+    for (i64 r = (i64)blockIdx.x * 256 + threadIdx.x; r < n; r += (i64)gridDim.x * 256) {
+        const unsigned char* v = col + r * W;
+        unsigned h = dictHash(v, W) & (DICT_SLOTS - 1);
+        for (int probe = 0; probe < DICT_SLOTS; probe++, h = (h + 1) & (DICT_SLOTS - 1)) {
+            const unsigned e = slot[h];
+            if (e == ~0u) { atomicOr(notFound, 1u); break; }
+            if (dictSame(dict + (i64)e * W, v, W)) { codes[r] = (unsigned char)e; break; }
+        }
+    }
+}
+
+static bool dictCandidate(const Table& t, const TableColumn& c) {
+    if (!dictScansEnabled() || t.derived || t.nRows <= 0 || !c.owned || !c.dptr || !c.type.isString()) return false;
+    return !(c.type.tag == RSQ_CHAR && c.type.len == 1);          // (CHAR(1) keeps its byte set)
+}
+
+// the sorted distinct values of a column, or nothing when there are more than 256
+static bool hostDictionary(const unsigned char* p, int64_t n, int W, std::vector<uint8_t>& dict) {
+    std::vector<const unsigned char*> vals;          // sorted bytewise (memcmp order)
+    const unsigned char* last = nullptr;
+    for (int64_t i = 0; i < n; i++) {
+        const unsigned char* v = p + (size_t)i * (size_t)W;
+        if (last && memcmp(last, v, (size_t)W) == 0) continue;
+        auto at = std::lower_bound(vals.begin(), vals.end(), v, [W](const unsigned char* x, const unsigned char* y) { return memcmp(x, y, (size_t)W) < 0; });
+        last = v;
+        if (at != vals.end() && memcmp(*at, v, (size_t)W) == 0) continue;
+        if (vals.size() == (size_t)DICT_MAX) return false;
+        vals.insert(at, v);
+    }
+    std::vector<uint8_t> out;
+    for (const unsigned char* v : vals) out.insert(out.end(), v, v + W);
+    dict.swap(out);
+    return !vals.empty();
+}
+
+static bool deviceDictionary(Context& ctx, const TableColumn& c, int64_t n, int W, std::vector<uint8_t>& dict) {
+    const unsigned grid = (unsigned)std::min<int64_t>(DICT_COLLECT_GRID, (n + 255) / 256);
+    const size_t slice = (size_t)DICT_MAX * (size_t)W;
+    unsigned* ctl = (unsigned*)ctx.alloc((size_t)(2 + DICT_COLLECT_GRID) * sizeof(unsigned));      // [overflow | union count | counts per workgroup]
+    unsigned char* slices = nullptr;
+    bool ok = false;
+    try {
+        RSQ_HIP(hipMemsetAsync(ctl, 0, (size_t)(2 + DICT_COLLECT_GRID) * sizeof(unsigned), ctx.stream));
+        unsigned h[2] = {0, 0};
+        // the sample: a column of many values (comments, clerks) costs this pass, its 64 slices and no more
+        const int64_t sample = std::min<int64_t>(n, DICT_SAMPLE_ROWS);
+        if (sample < n) {
+            const unsigned sgrid = (unsigned)std::min<int64_t>(64, (sample + 255) / 256);
+            slices = (unsigned char*)ctx.alloc((size_t)sgrid * slice);
+            hipLaunchKernelGGL(k_dict_collect, dim3(sgrid), dim3(256), 0, ctx.stream, (const unsigned char*)c.dptr, (i64)sample, W,
+                               (const unsigned*)nullptr, slices, ctl + 2, ctl);
+            RSQ_HIP(hipGetLastError());
+            RSQ_HIP(hipMemcpyAsync(h, ctl, sizeof(unsigned), hipMemcpyDeviceToHost, ctx.stream));
+            RSQ_HIP(hipStreamSynchronize(ctx.stream));
+            ctx.free(slices); slices = nullptr;
+        }
+        if (!h[0]) {
+            slices = (unsigned char*)ctx.alloc((size_t)(grid + 1) * slice);          // (the union's slice behind the workgroups')
+            unsigned char* uni = slices + (size_t)grid * slice;
+            hipLaunchKernelGGL(k_dict_collect, dim3(grid), dim3(256), 0, ctx.stream, (const unsigned char*)c.dptr, (i64)n, W, (const unsigned*)nullptr, slices, ctl + 2, ctl);
+            hipLaunchKernelGGL(k_dict_collect, dim3(1), dim3(256), 0, ctx.stream, (const unsigned char*)slices, (i64)grid * DICT_MAX, W, (const unsigned*)(ctl + 2), uni, ctl + 1, ctl);
+            RSQ_HIP(hipGetLastError());
+            std::vector<uint8_t> vals(slice);
+            RSQ_HIP(hipMemcpyAsync(h, ctl, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx.stream));
+            RSQ_HIP(hipMemcpyAsync(vals.data(), uni, vals.size(), hipMemcpyDeviceToHost, ctx.stream));
+            RSQ_HIP(hipStreamSynchronize(ctx.stream));
+            if (!h[0] && h[1] >= 1 && h[1] <= (unsigned)DICT_MAX) ok = hostDictionary(vals.data(), (int64_t)h[1], W, dict);      // (sorts them)
+        }
+    } catch (...) { ctx.free(ctl); if (slices) ctx.free(slices); throw; }
+    ctx.free(ctl); if (slices) ctx.free(slices);
+    return ok;
+}
+
+static void dropDictImage(Context& ctx, TableColumn& c) {
+    if (ctx.device >= 0) {
+        if (c.dictPtr) { ctx.freeRaw(c.dictPtr); ctx.columnImageBytes -= (uint64_t)DICT_MAX * (uint64_t)columnWidth(c.type) + 16; }
+        if (c.codePtr) { ctx.freeRaw(c.codePtr); ctx.columnImageBytes -= c.codeBytes; }
+    }
+    c.dictPtr = nullptr; c.codePtr = nullptr; c.codeBytes = 0; c.dictN = 0; c.dict.clear();
+}
+
+// (re)builds the dictionary images.  The same dictionary over the same number of rows is re-encoded where it lies; an image that is
+// moved or dropped bumps t.layoutVersion AT ONCE (a statement compiled before holds its address), whatever happens afterwards.
+static void buildDictImages(Context& ctx, Table& t) {
+    unsigned* dFlag = nullptr;
+    auto drop = [&](TableColumn& c) { if (c.dictPtr || c.codePtr) t.layoutVersion++; dropDictImage(ctx, c); };
+    try {
+        for (auto& c : t.cols) {
+            const int W = columnWidth(c.type);
+            std::vector<uint8_t> dict;
+            bool have = false;
+            if (dictCandidate(t, c)) have = ctx.device >= 0 ? deviceDictionary(ctx, c, t.nRows, W, dict) : hostDictionary((const unsigned char*)c.dptr, t.nRows, W, dict);
+            const int N = have ? (int)(dict.size() / (size_t)W) : 0;
+            const size_t bytes = N ? (((size_t)t.nRows + 15) & ~(size_t)15) : 0;
+            const bool keep = N && c.dictN == N && c.dict == dict && c.codeBytes == bytes && (ctx.device < 0 || (c.dictPtr && c.codePtr));
+            if (!keep) {
+                drop(c);
+                c.dictN = N; c.dict = dict; c.codeBytes = bytes;
+            }
+            if (!N || ctx.device < 0) continue;           // (a compile-only context only needs to know that the column is coded)
+            if (!c.dictPtr) {
+                const size_t dbytes = (size_t)DICT_MAX * (size_t)W + 16;
+                c.dictPtr = ctx.allocRaw(dbytes); ctx.columnImageBytes += dbytes;
+                c.codePtr = ctx.allocRaw(bytes); ctx.columnImageBytes += bytes;
+                RSQ_HIP(hipMemsetAsync(c.dictPtr, 0, dbytes, ctx.stream));
+                RSQ_HIP(hipMemsetAsync(c.codePtr, 0, bytes, ctx.stream));
+                RSQ_HIP(hipMemcpyAsync(c.dictPtr, c.dict.data(), c.dict.size(), hipMemcpyHostToDevice, ctx.stream));
+            }
+            if (!dFlag) { dFlag = (unsigned*)ctx.alloc(sizeof(unsigned)); RSQ_HIP(hipMemsetAsync(dFlag, 0, sizeof(unsigned), ctx.stream)); }
+            hipLaunchKernelGGL(k_dict_encode, dim3((unsigned)std::min<int64_t>(2048, (t.nRows + 255) / 256)), dim3(256), 0, ctx.stream, (const unsigned char*)c.dptr, (i64)t.nRows, W,
+                               (const unsigned char*)c.dictPtr, N, (unsigned char*)c.codePtr, dFlag);
+        }
+        if (dFlag) {
+            unsigned h = 0;
+            RSQ_HIP(hipGetLastError());
+            RSQ_HIP(hipMemcpyAsync(&h, dFlag, sizeof h, hipMemcpyDeviceToHost, ctx.stream));
+            RSQ_HIP(hipStreamSynchronize(ctx.stream));
+            // a row whose value the collecting passes did not report: no image is better than a wrong one
+            if (h) throw Error(RSQ_ERR_DEVICE, "dictionary image of table " + t.name + ": a row holds a value that is not in the column's dictionary");
+        }
+    } catch (...) {
+        // nothing half-built stays: the images go (the columns scan wide), statements that held one are refused, the flag is returned
+        (void)hipStreamSynchronize(ctx.stream);
+        for (auto& c : t.cols) drop(c);
+        if (dFlag) ctx.free(dFlag);
+        throw;
+    }
+    if (dFlag) ctx.free(dFlag);
+}
+
 template <typename T, typename N>
 __global__ void __launch_bounds__(256) k_encode(const T* __restrict__ src, N* __restrict__ dst, i64 n, i64 base) {
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
@@ -127,10 +326,10 @@ static void buildNarrowImages(Context& ctx, Table& t) {
         const int64_t base = w ? c.stats.min : 0;
         const size_t bytes = w ? (((size_t)t.nRows * (size_t)w + 15) & ~(size_t)15) : 0;
         const bool keep = ctx.device >= 0 && c.nptr && w == c.nw && base == c.nbase && bytes == c.nbytes;
-        if (!keep && c.nptr) { if (ctx.device >= 0) ctx.freeRaw(c.nptr); c.nptr = nullptr; moved = true; }
+        if (!keep && c.nptr) { if (ctx.device >= 0) { ctx.freeRaw(c.nptr); ctx.columnImageBytes -= c.nbytes; } c.nptr = nullptr; moved = true; }
         c.nw = w; c.nbase = base; c.nbytes = bytes;
         if (!w || ctx.device < 0) continue;          // (a compile-only context only needs the width and the base)
-        if (!c.nptr) c.nptr = ctx.allocRaw(bytes);
+        if (!c.nptr) { c.nptr = ctx.allocRaw(bytes); ctx.columnImageBytes += bytes; }
         launched = true;
         if (c.type.tag == RSQ_INT) launchEncode<int>(ctx, c, (i64)t.nRows);
         else if (c.type.tag == RSQ_DATE) launchEncode<unsigned>(ctx, c, (i64)t.nRows);
@@ -138,6 +337,7 @@ static void buildNarrowImages(Context& ctx, Table& t) {
     }
     if (launched) { RSQ_HIP(hipGetLastError()); RSQ_HIP(hipStreamSynchronize(ctx.stream)); }
     if (moved) t.layoutVersion++;
+    buildDictImages(ctx, t);
 }
 
 void computeColumnStats(Context& ctx, Table& t) {

@@ -193,6 +193,7 @@ int rsq_ctx_memory_stats(const rsq_ctx* ctx, rsq_memory_stats* out) {
     m.plan_memo_hits = c.planMemoHits;
     m.key_index_entries = c.keyIndexes.size();
     for (auto& kv : c.keyIndexes) m.key_index_bytes += (uint64_t)kv.second.bmBlocks * 32;
+    m.column_image_bytes = c.columnImageBytes;
     memcpy(out, &m, std::min<size_t>(have, sizeof m));
     out->struct_size = have;
     return RSQ_OK;

@@ -143,7 +143,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     // workgroups (of 256 threads) per launch; 0 = 2 per CU.  Measured on MI355X (Q1 SF10): 512 workgroups 0.348 ms,
     // 768: 0.367, 1024: 0.374, 2048: 0.395, 4096: 0.448 - a streaming kernel wants exactly 2 resident workgroups per CU
     pipe.maxGrid = (unsigned)0;
-    colTypes.clear(); colIsString.clear(); colNarrow.clear(); rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
+    colTypes.clear(); colIsString.clear(); colNarrow.clear(); colDict.clear(); nDictTables = 0; rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
     body.clear(); stateDecl.clear(); stateInit.clear(); prologue.clear(); epilogue.clear(); fileScope.clear(); helperFns.clear();
     explainSteps.clear(); indent = 1; matchSlotTable = -1; slotVar.clear(); symbolOrigin.clear(); symbolWord.clear();
     multiMatchAbove = false;
@@ -173,8 +173,21 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
         // function take decoded values, only the loads see the image.  A compile-only context has the width and no image.
         const int nw = (!t->derived && c.owned && narrowScans && !c.type.isString() && (c.nptr || q.ctx.device < 0)) ? c.nw : 0;
         colNarrow.push_back(nw);
-        pipe.storedBytesPerRow += nw ? nw : columnWidth(c.type);
-        if (c.type.isString()) {
+        // ... or its dictionary image (TableColumn::dict): one byte per row, the value an rsq::Str into the dictionary
+        const bool dictCoded = !t->derived && c.owned && c.type.isString() && c.dictN > 0 && dictScansEnabled() && (c.codePtr || q.ctx.device < 0);
+        colDict.push_back(dictCoded ? c.type.len : 0);
+        pipe.storedBytesPerRow += dictCoded ? 1 : nw ? nw : columnWidth(c.type);
+        if (dictCoded) {
+            const std::string K = std::to_string(k);
+            addArg("c" + K, "const u8*", (uint64_t)(uintptr_t)c.codePtr);
+            addArg("d" + K, "const char*", (uint64_t)(uintptr_t)c.dictPtr);      // (the dictionary's address and entry count are arguments: the text
+            addArg("dn" + K, "i64", (uint64_t)c.dictN);                          // holds the width only)
+            colIsString.push_back(0); colTypes.push_back("u8");
+            rowParams += ", u8 vc_" + K;
+            rowArgsTail += ", a.c" + K + "[r]";
+            rowArgsTailGuarded += ", (valid ? a.c" + K + "[r] : (u8)0)";
+            line("const rsq::Str " + var + " = " + dictDecode(k, "vc_" + K) + ";");
+        } else if (c.type.isString()) {
             addArg("c" + std::to_string(k), "const char*", (uint64_t)(uintptr_t)c.dptr);
             colIsString.push_back(1); colTypes.push_back("");
             line("const rsq::Str " + var + " = rsq::str(a.c" + std::to_string(k) + " + lr * " + std::to_string(c.type.len) + ", " +
@@ -310,6 +323,43 @@ void Walker::prefetchComparedStrings(const Expr* e) {
     if (e->tag == RSQ_E_AND || e->tag == RSQ_E_OR) for (Expr* c : e->children()) prefetchComparedStrings(c);
 }
 
+// ---- truth tables over dictionary-coded columns (codegen_internal.h nDictTables) ---------------------------------------------------
+int Walker::dictTableColumn(const Expr* e, int col) {
+    if (e->tag == RSQ_E_ATTRIBUTE) {
+        auto sy = eg.symbols.find(e->symbol);
+        auto so = symbolOrigin.find(e->symbol);
+        if (sy == eg.symbols.end() || so == symbolOrigin.end() || so->second != -1 || sy->second.var.compare(0, 2, "v_") != 0) return -2;
+        const int k = atoi(sy->second.var.c_str() + 2);
+        if (!coded(k) || (col >= 0 && col != k)) return -2;
+        return k;
+    }
+    if (e->tag == RSQ_E_CONSTANT) return col;
+    const bool known = e->tag == RSQ_E_EQ || e->tag == RSQ_E_NEQ || e->tag == RSQ_E_LIKE || e->tag == RSQ_E_AND || e->tag == RSQ_E_OR;
+    if (!known) return -2;
+    for (Expr* c : e->children()) { col = dictTableColumn(c, col); if (col == -2) return -2; }
+    return col;
+}
+
+// registers every outermost qualifying sub-expression of e, so that emit() answers it with the bit test; the caller clears
+// eg.tabled behind its emit (the code variable exists in stage 1 only)
+void Walker::dictTablesWithin(Expr* e) {
+    if (inStage2 || colDict.empty() || !e) return;
+    const bool boolean = e->tag == RSQ_E_EQ || e->tag == RSQ_E_NEQ || e->tag == RSQ_E_LIKE || e->tag == RSQ_E_AND || e->tag == RSQ_E_OR;
+    const int k = boolean && !eg.symbols.count(expressionName(e)) ? dictTableColumn(e) : -2;
+    if (k >= 0) {
+        const std::string K = std::to_string(k), J = std::to_string(nDictTables++), W = std::to_string(colDict[(size_t)k]);
+        helperFns += "static RSQ_DEV u8 dt" + J + "_eval(const Args& a, const rsq::Str v_" + K + ") { (void)a; return " + eg.emit(e) + "; }\n";
+        prologue += "    for (u32 dt_i = 0; dt_i < 4u; dt_i++) {      // truth table " + J + ": bit e = the predicate over entry e of column " + K + "'s dictionary\n"
+                    "        const u32 dt_e = (threadIdx.x & 63u) + 64u * dt_i;\n"
+                    "        const u64 dt_m = __ballot(dt_e < (u32)a.dn" + K + " && dt" + J + "_eval(a, rsq::str(a.d" + K + " + dt_e * " + W + "u, " + W + ")));\n"
+                    "        if ((threadIdx.x & 63u) == 0u) s_dt[" + J + " * 4 + dt_i] = dt_m;      // (every wave writes the same word)\n"
+                    "    }\n";
+        eg.tabled[e] = "rsq::dict_bit(s_dt + " + J + " * 4, vc_" + K + ")";
+        return;
+    }
+    for (Expr* c : e->children()) dictTablesWithin(c);
+}
+
 void Walker::noteLeadingSelection(const Expr* e, const std::string& cond) {
     bool ok = true;
     std::vector<int> cols;
@@ -331,7 +381,9 @@ void Walker::consume(OpNode* o, OpNode* from) {
             {
                 // (RSQ_STRING_PREFETCH=2, measurement: also behind probes, as long as no selection came before)
                 if (from->tag == RSQ_OP_SCAN || (1 == 2 && !wasSelective)) prefetchComparedStrings(o->exprs[0]);
+                dictTablesWithin(o->exprs[0]);
                 const std::string cond = eg.emit(o->exprs[0]);
+                eg.tabled.clear();
                 if (from->tag == RSQ_OP_SCAN && leadCond.empty()) noteLeadingSelection(o->exprs[0], cond);
                 if (from->tag == RSQ_OP_SCAN && indent == 1 && pairCond.empty() && !compacted) { pairSplit = body.size(); pairCond = cond; }
                 openScope("if (" + cond + ") {");
@@ -349,7 +401,9 @@ void Walker::consume(OpNode* o, OpNode* from) {
             for (Expr* e : o->exprs) {
                 q.pool.addId(e);
                 std::string var = "p" + std::to_string((int)(size_t)o->exprs.size()) + "_" + std::to_string(k++) + "_" + std::to_string(indent);
+                dictTablesWithin(e);
                 line("const " + ExprGen::ctype(e->type) + " " + var + " = " + eg.emit(e) + ";");
+                eg.tabled.clear();
                 defs.push_back({expressionName(e), Sym{var, e->type}});
                 s.push_back({expressionName(e), e->type});
             }

@@ -14,6 +14,7 @@ void Walker::collectAccumulators(OpNode* o) {
     q.accums.push_back(Accum{RSQ_E_MIN, "#firstrow", "row", Type(RSQ_BIGINT), 2});
     for (Expr* s : o->splitAgg) {
         Accum ac; ac.kind = s->tag; ac.type = s->type;
+        dictTablesWithin(s);          // (CASE conditions over one dictionary-coded column of the scan: truth tables, codegen.cpp)
         switch (s->tag) {
             case RSQ_E_COUNT: ac.key = "COUNT"; ac.input = eg.emit(s); ac.merge = 0; ac.inputExpr = nullptr; break;
             case RSQ_E_SUM:
@@ -27,6 +28,7 @@ void Walker::collectAccumulators(OpNode* o) {
                 ac.input = "((i64)(" + eg.emit(s) + "))"; ac.merge = s->tag == RSQ_E_MIN ? 2 : 3; ac.inputExpr = s->child; break;
             default: failType("Aggregation type not implemented in updateAggregates(..).");
         }
+        eg.tabled.clear();
         int found = -1;
         for (size_t i = 1; i < q.accums.size(); i++) if (q.accums[i].key == ac.key) found = (int)i;
         if (found < 0) { q.accums.push_back(ac); found = (int)q.accums.size() - 1; }

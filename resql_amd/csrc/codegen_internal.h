@@ -32,6 +32,7 @@ struct ExprGen {
     std::map<std::string, Sym> symbols;     // JitContextFlounder::symbolTable of the current pipeline
     std::map<std::string, int> strWordVars; // string columns whose first words arrive as row-function parameters <var>_w0, _w1 (loaded with the tile): how many
     bool int16Cast = false;                 // rsq_config.compat_flags & RSQ_COMPAT_JIT_INT16_CAST
+    std::map<const Expr*, std::string> tabled;      // sub-expressions answered by a truth table over a dictionary-coded column (Walker::dictTablesWithin): their text
 
     static std::string ctype(const Type& t) {
         switch (t.tag) {
@@ -76,6 +77,7 @@ struct ExprGen {
         if (e->type.tag == RSQ_NT) failType("Expression type undefined in emitExpression(..). Have you derived the expression types?");
         auto it = symbols.find(expressionName(e));
         if (it != symbols.end()) return it->second.var;          // value already available under this name
+        if (!tabled.empty()) { auto tb = tabled.find(e); if (tb != tabled.end()) return tb->second; }
         switch (e->structure) {
             case LITERAL:
                 if (e->tag == RSQ_E_ATTRIBUTE) failType("attribute " + e->symbol + " is not available in this pipeline");
@@ -272,6 +274,21 @@ struct Walker {
         if (k < (int)colNarrow.size() && colNarrow[(size_t)k]) return "rsq::ld2n(a.c" + K + " + b, a.fb" + K + ", " + dst + ");";
         return "rsq::ld2(a.c" + K + " + b, " + dst + ");";
     }
+    // Dictionary-coded string columns (engine.h TableColumn::dict): per scanned column the width W of its values, 0 = not coded.  The scan
+    // treats such a column as a one-byte tile column (colIsString 0, colTypes "u8") whose row-function parameter is the code, vc_<k>;
+    // the row function's first lines turn it into the rsq::Str v_<k> that points into the dictionary (a.d<k>, a kernel argument).
+    std::vector<int> colDict;
+    bool coded(int k) const { return k >= 0 && k < (int)colDict.size() && colDict[(size_t)k] != 0; }
+    std::string paramName(int k) const { return (coded(k) ? "vc_" : "v_") + std::to_string(k); }
+    std::string dictDecode(int k, const std::string& code) const {
+        const std::string K = std::to_string(k), W = std::to_string(colDict[(size_t)k]);
+        return "rsq::str(a.d" + K + " + (u32)(" + code + ") * " + W + "u, " + W + ")";
+    }
+    // Truth tables: a boolean expression whose only non-constant leaf is ONE coded column is evaluated once per dictionary entry in the kernel's
+    // prologue - by the expression text the row function would have run - and a row tests bit `code` of the 256-bit result (LDS, s_dt).
+    int nDictTables = 0;
+    int dictTableColumn(const Expr* e, int col = -1);       // the coded column e depends on alone (-1: none, -2: does not qualify)
+    void dictTablesWithin(Expr* e);                         // registers them in eg.tabled; the caller clears it behind its emit
     int storedWidth(int k) const {            // bytes per row the scan fetches of column k (non-string)
         if (k < (int)colNarrow.size() && colNarrow[(size_t)k]) return colNarrow[(size_t)k];
         return colTypes[(size_t)k] == "i64" ? 8 : colTypes[(size_t)k] == "i32" ? 4 : 1;

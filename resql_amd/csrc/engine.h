@@ -55,6 +55,16 @@ struct TableColumn {
     int64_t nbase = 0;
     void* nptr = nullptr;
     size_t nbytes = 0;
+    // Dictionary image: an owned CHAR(n > 1) / VARCHAR(n) column with at most 256 distinct values (all n stored bytes, compared bytewise)
+    // keeps those values - `dict`, dictN x n bytes as stored, in memcmp order - and one u8 per row, the value's rank in that order.  Built
+    // and rebuilt with the narrow images (aot_kernels.hip buildDictImages); a compile-only context has dictN and dict and no device copies.
+    // dictPtr holds 256 entries (the ones past dictN are zero), so a code never addresses memory outside it.  Read by the generated
+    // scans only, like nptr.
+    int dictN = 0;
+    std::vector<uint8_t> dict;
+    void* dictPtr = nullptr;
+    void* codePtr = nullptr;
+    size_t codeBytes = 0;
 };
 
 // the width of a column's narrow image: a pure function of its type, ownership and statistics (0 = none)
@@ -62,6 +72,10 @@ int narrowWidth(const TableColumn& c);
 // RSQ_NARROW_SCANS=0: no narrow images are built and no scan reads one - the kernels and their text are what they are without them
 // (read where the images are built and where the code generator picks them; flipped by tests/test_gpu_narrow_scan.py)
 inline bool narrowScansEnabled() { const char* e = getenv("RSQ_NARROW_SCANS"); return !e || atoi(e) != 0; }
+// RSQ_DICT_SCANS=1 builds the dictionary images and lets the scans read them; unset or 0: string columns are scanned at their width, the
+// kernels and their text are what they are without the images.  Off by default until the SF10 comparison (tools/dict_scan_bench.py) is on
+// record in docs/KERNELS.md.  RSQ_NARROW_SCANS=0 turns them off as well.
+inline bool dictScansEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return narrowScansEnabled() && e && atoi(e) != 0; }
 
 struct Context;
 
@@ -202,6 +216,7 @@ struct Context {
     std::map<KeyIndexKey, KeyIndex> keyIndexes;
     void retireKeyIndexes(uint64_t uid);
     void releaseKeyIndex(KeyIndex* k);
+    uint64_t columnImageBytes = 0;             // device memory of the tables' narrow and dictionary images (rsq_ctx_memory_stats)
     uint64_t planMemoClock = 0, planMemoHits = 0;
     bool planMemoOff = false;
 };

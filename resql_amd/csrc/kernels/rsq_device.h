@@ -80,6 +80,10 @@ template <typename T> RSQ_DEV void ld2n(const u8* p, i64 base, T (&v)[2]) { cons
 template <typename T> RSQ_DEV void ld2n(const u16* p, i64 base, T (&v)[2]) { const u32 t = RSQ_LD_NARROW(u32, p); v[0] = dec<T>(t & 0xffffu, base); v[1] = dec<T>(t >> 16, base); }
 template <typename T> RSQ_DEV void ld2n(const u32* p, i64 base, T (&v)[2]) { const u32v2 t = RSQ_LD_NARROW(u32v2, p); v[0] = dec<T>(t.x, base); v[1] = dec<T>(t.y, base); }
 
+// Dictionary-coded string columns: the scan loads one u8 per row, the value's rank among the column's (at most 256) distinct values, and the
+// row's rsq::Str points at that entry of the dictionary.  A predicate over one such column is a 256-bit table in LDS: bit `code`.
+RSQ_DEV u8 dict_bit(const u64* table, u8 code) { return (u8)((table[code >> 6] >> (code & 63u)) & 1ull); }
+
 // One 128-row tile of a W-byte string column = 8 * W chunks of 16 bytes; chunk 64 * R + lane is the lane's load number R (the lanes past the
 // last chunk repeat it: an unconditional load, which the compiler's wait counting needs of every load of the tile).  Tiles start at
 // multiples of 128 rows, so the chunks are 16-byte aligned wherever the column base is.

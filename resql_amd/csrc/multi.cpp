@@ -305,6 +305,7 @@ std::unique_ptr<Table> sliceOf(const Table& t, int64_t start, int64_t rows) {
     for (TableColumn& c : v->cols) {
         c.owned = false;
         c.nw = 0; c.nbase = 0; c.nptr = nullptr; c.nbytes = 0;      // (a borrowed view reads the wide column)
+        c.dictN = 0; c.dict.clear(); c.dictPtr = nullptr; c.codePtr = nullptr; c.codeBytes = 0;
         if (c.dptr) c.dptr = (char*)c.dptr + (size_t)start * (size_t)columnWidth(c.type);
     }
     return v;

@@ -263,7 +263,12 @@ void Context::releaseKeyIndex(KeyIndex* k) {
 Table::~Table() {
     if (ctx) ctx->retireKeyIndexes(uid);
     if (ctx && ctx->device >= 0) {
-        for (auto& c : cols) { if (c.owned && c.dptr) ctx->freeRaw(c.dptr); if (c.owned && c.nptr) ctx->freeRaw(c.nptr); }
+        for (auto& c : cols) {
+            if (c.owned && c.dptr) ctx->freeRaw(c.dptr);
+            if (c.owned && c.nptr) { ctx->freeRaw(c.nptr); ctx->columnImageBytes -= c.nbytes; }
+            if (c.owned && c.dictPtr) { ctx->freeRaw(c.dictPtr); ctx->columnImageBytes -= 256ull * (uint64_t)columnWidth(c.type) + 16; }
+            if (c.owned && c.codePtr) { ctx->freeRaw(c.codePtr); ctx->columnImageBytes -= c.codeBytes; }
+        }
     } else {
         for (auto& c : cols) if (c.owned && c.dptr) ::free(c.dptr);
     }
