@@ -142,7 +142,8 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     pipe.blockThreads = 256;
     // workgroups (of 256 threads) per launch; 0 = 2 per CU.  Measured on MI355X (Q1 SF10): 512 workgroups 0.348 ms,
     // 768: 0.367, 1024: 0.374, 2048: 0.395, 4096: 0.448 - a streaming kernel wants exactly 2 resident workgroups per CU
-    pipe.maxGrid = (unsigned)0;
+    // (RSQ_MAX_GRID, as the statement's compile read it, overrides that: a launch parameter, not part of the text)
+    pipe.maxGrid = q.maxGrid;
     colTypes.clear(); colIsString.clear(); colNarrow.clear(); colDict.clear(); nDictTables = 0; rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
     body.clear(); stateDecl.clear(); stateInit.clear(); prologue.clear(); epilogue.clear(); fileScope.clear(); helperFns.clear();
     explainSteps.clear(); indent = 1; matchSlotTable = -1; slotVar.clear(); symbolOrigin.clear(); symbolWord.clear();

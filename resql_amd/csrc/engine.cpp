@@ -298,6 +298,7 @@ static std::string planMemoKey(const Query& q) {
     uint64_t h = 1469598103934665603ull;
     for (auto& p : q.pipelines) h = fnv1a64(p.source, h) * 0x9E3779B97F4A7C15ull;
     std::string k = std::to_string(h);
+    if (q.maxGrid) k += "|g" + std::to_string(q.maxGrid);      // (RSQ_MAX_GRID: what a query learnt under one grid - staged regions per workgroup - is not another's)
     for (Table* t : q.tables) k += "|" + std::to_string(t->uid) + "." + std::to_string(t->version) + "." + std::to_string(t->nRows) + "." + std::to_string(t->row0) + "." + std::to_string(t->nRowsTotal);
     return k;
 }
@@ -524,6 +525,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     double t0 = nowMs();
     std::unique_ptr<Query> q(new Query(ctx));
     int hits0 = ctx.jitCacheHits, comp0 = ctx.jitCompiles;
+    q->maxGrid = maxGridSetting();
     for (int i = 0; i < nTables; i++) {
         Table* t = reinterpret_cast<Table*>(tables[i]);
         if (!t) failInvalid("null table");

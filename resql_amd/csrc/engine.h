@@ -76,6 +76,12 @@ inline bool narrowScansEnabled() { const char* e = getenv("RSQ_NARROW_SCANS"); r
 // kernels and their text are what they are without the images.  Off by default until the SF10 comparison (tools/dict_scan_bench.py) is on
 // record in docs/KERNELS.md.  RSQ_NARROW_SCANS=0 turns them off as well.
 inline bool dictScansEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return narrowScansEnabled() && e && atoi(e) != 0; }
+// RSQ_MAX_GRID=n (1..65535): the tile loops of a statement compiled under it launch at most n 256-thread workgroups' worth of threads
+// (Pipeline::maxGrid: n * 256 / block size workgroups, at least one); unset, 0 or out of range: the grid the pipeline asks for.  Read ONCE per statement, when it is compiled
+// (compileQuery): buffers sized from the grid then (engine_pipelines.cpp sizeJoinTable) fit every later launch.  A launch parameter only -
+// kernel text and code-object cache keys do not know it; the plan memo's key does.  For tests that need many tiles per wave from a small
+// table (tests/test_gpu_narrow_edges.py: the fold of the 32-bit partial sums).
+inline unsigned maxGridSetting() { const char* e = getenv("RSQ_MAX_GRID"); const long v = e ? atol(e) : 0; return v >= 1 && v <= 65535 ? (unsigned)v : 0u; }
 
 struct Context;
 

@@ -509,6 +509,7 @@ struct Query {
     std::string allSource, explainText;
     std::string memoKey;                   // the context's plan memo entry of this query (empty: none)
     bool memoApplied = false;              // ... and an earlier query's entry was found when this one was compiled
+    unsigned maxGrid = 0;                  // RSQ_MAX_GRID as it stood when this query was compiled (engine.h maxGridSetting): every pipeline's maxGrid
 
     explicit Query(Context& c) : ctx(c) {}
     ~Query();

@@ -204,6 +204,7 @@ unsigned fewGroupsGrid(Query& q, Pipeline& p, Kernel* k) {
     const int64_t tiles = p.src->nRows >> 7;
     const int wavesPerBlock = p.blockThreads / 64;
     const int64_t want = std::max<int64_t>(1, (tiles + (int64_t)wavesPerBlock * p.unroll - 1) / ((int64_t)wavesPerBlock * p.unroll));
+    if (p.maxGrid) return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)p.maxGrid * 256 / p.blockThreads));
     return (unsigned)std::min<int64_t>(want, (int64_t)std::min(p.unroll >= 3 ? 6 : 8, residentWorkgroupsPerCU(k, p.blockThreads)) * q.ctx.numCUs);
 }
 
