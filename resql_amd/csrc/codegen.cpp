@@ -446,6 +446,16 @@ bool Walker::downstreamMaterializes(OpNode* o) {
     return true;
 }
 
+// The code of dictionary-coded scan column k, for stage 2: it joins the values the queue carries (one word, like a one-byte column),
+// under the name q_<its place in cqLive>.  compactThen entered it there before stage 2 was generated; the dense group id
+// (codegen_agg.cpp groupIdExpr) asks for the name, and only a name that stage 2 mentions gets a queue slot.
+std::string Walker::stage2Code(int k) {
+    const std::string var = "vc_" + std::to_string(k);
+    for (size_t i = 0; i < cqLive.size(); i++) if (cqLive[i].first.empty() && cqLive[i].second.var == var) return "q_" + std::to_string(i);
+    failUnsupported("internal: the code of scanned column " + std::to_string(k) + " is not among the carried values");
+    return "";
+}
+
 bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
     if (compacted || !selective || !envInt("RSQ_COMPACT", 1, 0, 1) || downstreamMaterializes(o)) return false;
     // not inside the match loop of a join probed for all matches: the queue takes ONE entry per row function call, and a row
@@ -454,6 +464,10 @@ bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
     compacted = true;
     pipe.compact = true;
     cqLive.assign(eg.symbols.begin(), eg.symbols.end());
+    // The codes of this scan's dictionary-coded columns follow the symbols, nameless (no symbol is the empty string): one u8 word
+    // each, never loaded late, read in stage 2 through stage2Code alone.  One that stage 2 does not mention gets no slot below.
+    const size_t nSymbols = cqLive.size();
+    for (size_t p = 0; p < pipe.cols.size(); p++) if (coded((int)p)) cqLive.push_back({"", Sym{"vc_" + std::to_string(p), Type(RSQ_BOOL)}});
     // Late column loads: a scanned (non-string) column that stage 1 never looked at is needed only by the rows that reach
     // stage 2.  The kernel exists in two forms from one source: RSQ_LAZY 0 loads it with the tile and carries it in the
     // queue; RSQ_LAZY 1 leaves it out of the tile loads and stage 2 reads it by row index.  The engine picks the lazy
@@ -481,7 +495,7 @@ bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
     const std::string stage1 = body; const int stage1Indent = indent;
     body.clear(); indent = 1;
     stage2Prefix.clear(); compFilters.clear(); inStage2 = true;
-    for (size_t k = 0; k < cqLive.size(); k++) eg.symbols[cqLive[k].first] = Sym{"q_" + std::to_string(k), cqLive[k].second.type};
+    for (size_t k = 0; k < nSymbols; k++) eg.symbols[cqLive[k].first] = Sym{"q_" + std::to_string(k), cqLive[k].second.type};
     explainSteps.push_back("wave compaction");
     downstream();
     while (indent > 1) closeScope();

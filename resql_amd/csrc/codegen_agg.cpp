@@ -45,32 +45,62 @@ void Walker::collectAccumulators(OpNode* o) {
     q.nSumBlocks = (int64_t)q.accums.size() - q.nMinBlocks - q.nMaxBlocks;
 }
 
+// Dense group ids: every group-by value is a column of this pipeline's scan whose domain is known and small - a numeric column by its
+// statistics' [min, max] (rank = value - min), a one-byte column by its sorted distinct values (rank = position in the set), a
+// dictionary-coded string column (RSQ_DICT_SCANS=1, codegen.cpp colDict) by its dictionary (rank = the row's code, card = the entry
+// count).  The group id is the mixed-radix number of the ranks, at most 2^24 groups.  card and the strides go into the kernel text; a
+// dictionary's values and address do not.  The statement keeps the dictionary's bytes for its tail (DenseKey::dict): a dictionary that
+// changes is rebuilt, which bumps the table's layoutVersion and refuses the statements compiled before (executeQuery).
 bool Walker::tryDenseKeys(OpNode* o) {
     Table* t = pipe.src;
     q.denseKeys.clear();
+    auto no = [&] { q.denseKeys.clear(); return false; };      // (a statement that is not dense holds no dense keys)
     int64_t total = 1;
     for (Expr* g : o->exprs2) {
-        if (g->tag != RSQ_E_ATTRIBUTE) return false;
+        if (g->tag != RSQ_E_ATTRIBUTE) return no();
         auto org = symbolOrigin.find(g->symbol);
-        if (org == symbolOrigin.end() || org->second != -1) return false;      // not a column of this pipeline's scan
+        if (org == symbolOrigin.end() || org->second != -1) return no();      // not a column of this pipeline's scan
         int ci = t->findCol(g->symbol);
-        if (ci < 0 || !t->cols[(size_t)ci].dptr) return false;
+        if (ci < 0 || !t->cols[(size_t)ci].dptr) return no();
         const TableColumn& c = t->cols[(size_t)ci];
-        if (c.type.isString()) return false;               // string keys: generic hash aggregation (bytes as key words)
         DenseKey k; k.expr = g; k.type = c.type;
+        if (c.type.isString()) {
+            // a string key is dense only as a dictionary code of THIS table's own dictionary: not for a shard or a slice view, whose siblings
+            // hold other dictionaries (their dense layouts would not line up), and not in any compile of a statement that runs on several
+            // shards (Context::shardCompile: a table every shard holds alike has no nRowsTotal, and the shards' results are merged group by
+            // group, which wants hash aggregations).  Every other string key: generic hash aggregation (bytes as key words)
+            int sc = -1;
+            for (size_t p = 0; p < pipe.cols.size(); p++) if (pipe.cols[p] == ci) sc = (int)p;
+            if (!coded(sc) || t->nRowsTotal >= 0 || q.ctx.shardCompile || c.dictN <= 0 || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no();
+            k.coded = true; k.scanCol = sc; k.card = c.dictN; k.dict = c.dict;
+            if (c.type.tag == RSQ_CHAR) {
+                std::set<std::string> seen;
+                const size_t w = (size_t)c.type.len;
+                for (int e = 0; e < c.dictN; e++) {
+                    const char* v = (const char*)k.dict.data() + (size_t)e * w;
+                    size_t n = strnlen(v, w);
+                    while (n > 0 && v[n - 1] == ' ') n--;
+                    if (!seen.insert(std::string(v, n)).second) k.spaceEquivalent = true;
+                }
+            }
+            if (total > (int64_t)(1 << 24) / k.card) return no();
+            total *= k.card;
+            q.denseKeys.push_back(k);
+            continue;
+        }
         // (an empty SHARD of a table plans with the statistics of the whole table, like every other shard: Table::nRowsTotal)
         if (t->nRows == 0 && !c.stats.valid && !t->derived) { k.card = 1; k.min = 0; }      // empty input: no row reaches the aggregation
                                                                                         // (a derived table's rows are known only at execution)
-        else if (!c.stats.valid) return false;
+        else if (!c.stats.valid) return no();
         else if (!c.stats.distinctBytes.empty()) { k.byteSet = true; k.values = c.stats.distinctBytes; k.card = (int64_t)k.values.size(); }
         else {
-            if (c.type.isString()) return false;
+            if (c.type.isString()) return no();
             k.min = c.stats.min;
             unsigned __int128 range = (unsigned __int128)((__int128)c.stats.max - (__int128)c.stats.min) + 1;
-            if (range > (unsigned __int128)(1u << 24)) return false;
+            if (range > (unsigned __int128)(1u << 24)) return no();
             k.card = (int64_t)range;
         }
-        if (total > (int64_t)(1 << 24) / k.card) return false;
+        if (total > (int64_t)(1 << 24) / k.card) return no();
         total *= k.card;
         q.denseKeys.push_back(k);
     }
@@ -113,7 +143,15 @@ void Walker::consumeAggregation(OpNode* o, OpNode* from) {
     if (!(forced == 5 && !o->exprs2.empty()) && tryDenseKeys(o)) {
         const int64_t D = q.denseGroups, cells = D * W;
         // measured on MI355X (Q1 SF10, 42 cells): registers 0.47 ms, lane-private LDS 0.71 ms
-        if ((cells <= 64 && forced == 0) || forced == 1) { q.aggMode = AggMode::DENSE_REG; if (cells > 64) failUnsupported("too many groups for register accumulators"); }
+        // A coded key behind a wave compaction (TPC-H Q12: GROUP BY l_shipmode behind the probe of orders) was a hash aggregation in a
+        // 256-thread workgroup before the codes became ranks, bound by the latency of the random probe.  The register form would double
+        // the workgroup and the queues' LDS with it, and hold two VGPRs per cell: Q12's kernel 133 VGPRs, 35.5 KB, 3 waves per SIMD
+        // against the hash form's 107, 15.1 KB and 4.  The workgroup's LDS table keeps 256 threads - 84 VGPRs, 18.6 KB, 5 waves - and
+        // merges into the same few LDS words the hash form's front table did, without the hash walk in front of them.
+        bool codedBehindCompaction = inStage2 && forced == 0 && cells <= 64;
+        if (codedBehindCompaction) { codedBehindCompaction = false; for (auto& k : q.denseKeys) codedBehindCompaction = codedBehindCompaction || k.coded; }
+        if (codedBehindCompaction) q.aggMode = AggMode::DENSE_LDS_SHARED;
+        else if ((cells <= 64 && forced == 0) || forced == 1) { q.aggMode = AggMode::DENSE_REG; if (cells > 64) failUnsupported("too many groups for register accumulators"); }
         else if ((cells <= 56 && forced == 0) || forced == 2) { q.aggMode = AggMode::DENSE_LDS_PRIVATE; if (cells > 56) failUnsupported("too many groups for lane-private LDS accumulators"); }
         else if ((cells <= 6144 && forced == 0) || forced == 3) { q.aggMode = AggMode::DENSE_LDS_SHARED; if (cells > 6144) failUnsupported("too many groups for an LDS table"); }
         else q.aggMode = AggMode::DENSE_GLOBAL;
@@ -546,8 +584,20 @@ std::string Walker::groupIdExpr() {
     std::string gid = "0";
     for (size_t ki = 0; ki < q.denseKeys.size(); ki++) {
         DenseKey& k = q.denseKeys[ki];
-        std::string v = eg.emit(k.expr), rank;
         const std::string rv = "gk" + std::to_string(ki);
+        if (k.coded) {
+            // the rank IS the code the scan loaded: no decode, no dictionary access.  Behind a wave compaction the code travels in the
+            // queue (codegen.cpp compactThen), not the rsq::Str it would decode to.
+            const std::string code = inStage2 ? stage2Code(k.scanCol) : "vc_" + std::to_string(k.scanCol);
+            if (!envInt("RSQ_CHECK_STATS", 0, 0, 1)) line("const int " + rv + " = (int)(" + code + ");");
+            else {
+                line("int " + rv + " = (int)(" + code + ");");
+                line("if ((u32)" + rv + " >= " + std::to_string((long long)k.card) + "u) { atomicOr(a.err, (u32)rsq::ERR_GROUP_OVERFLOW); " + rv + " = 0; }");
+            }
+            gid += " + " + rv + " * " + std::to_string((long long)k.stride);
+            continue;
+        }
+        std::string v = eg.emit(k.expr), rank;
         // (columns the engine owns — uploaded, generated, loaded from '.tbl' — cannot change after their statistics were
         // taken: only adopted columns pay for the checks; TPC-H Q1's kernel is 6 % slower with them)
         bool check = true;
@@ -1055,11 +1105,14 @@ void Walker::emitDenseAggregation(OpNode* o) {
     }
     epilogue += ep.str();
     static const char* names[] = {"none", "registers", "lane-private LDS", "workgroup LDS table", "HBM table", "join entry", "hash"};
+    std::string codedNote;      // (nothing without a dictionary-coded key: the text of every other statement stays what it was)
+    for (auto& k : q.denseKeys)
+        if (k.coded) codedNote += ", key " + k.expr->symbol + " by dictionary code (" + std::to_string((long long)k.card) + (k.card == 1 ? " entry)" : " entries)");
     explainSteps.push_back("aggregation dense groups=" + std::to_string((long long)D) + " accumulators=" + std::to_string(W - 1) +
                            " (of " + std::to_string(o->splitAgg.size()) + " in the reference) in " + names[(int)q.aggMode] +
                            (pipe.partitioned ? " (atomics, or " + std::to_string(pipe.partCount) + " partitions x " + std::to_string(pipe.partGroups) +
                                                " groups aggregated in LDS when many rows pass)" : "") +
-                           (foldTile.empty() ? "" : ", 32-bit partial sums folded every 32 tiles"));
+                           (foldTile.empty() ? "" : ", 32-bit partial sums folded every 32 tiles") + codedNote);
 }
 
 void Walker::emitJoinEntryAggregation(OpNode* o) {

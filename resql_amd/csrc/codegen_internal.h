@@ -415,6 +415,7 @@ struct Walker {
     void collectAccumulators(OpNode* o);
 
     bool tryDenseKeys(OpNode* o);
+    std::string stage2Code(int k);          // stage-2 name of the code of dictionary-coded scan column k (codegen.cpp)
 
     bool tryJoinEntry(OpNode* o);
 

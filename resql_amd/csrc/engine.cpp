@@ -198,6 +198,11 @@ bool denseMode(const Query& q) {
            q.aggMode == AggMode::DENSE_LDS_SHARED || q.aggMode == AggMode::DENSE_GLOBAL;
 }
 
+// A dense table that other ranks' tables may be merged into: not one keyed by a dictionary code.  The dictionary is this process's own
+// (another rank's holds other values under the same codes), so the partial entry points - execute_partial*, partial_layout, bind_partial,
+// merge_gathered, finalize* - answer such a statement as they answer the hash aggregation it was before the codes became ranks.
+static bool partialCapable(const Query& q) { return denseMode(q) && !anyCodedKey(q.denseKeys); }
+
 // Device-resident identity image of the dense aggregate table (0 for sums, +/-inf for min/max) and a pinned
 // host buffer for the read-back: one execute is then {D2D init, kernel(s), D2H} on one stream with a single
 // host synchronisation at the end.
@@ -634,7 +639,8 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
         for (size_t i = 0; i < q->denseKeys.size(); i++) {
             const DenseKey& k = q->denseKeys[i];
             d << (i ? " x " : "") << k.expr->symbol;
-            if (k.byteSet) { d << "{"; for (size_t v = 0; v < k.values.size(); v++) d << (v ? "," : "") << (int)k.values[v]; d << "}"; }
+            if (k.coded) d << "{dictionary code, " << k.card << (k.card == 1 ? " entry}" : " entries}");
+            else if (k.byteSet) { d << "{"; for (size_t v = 0; v < k.values.size(); v++) d << (v ? "," : "") << (int)k.values[v]; d << "}"; }
             else d << "[" << k.min << ".." << (k.min + k.card - 1) << "]";
         }
         d << "] blocks=[";
@@ -907,7 +913,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     const uint64_t epochAtEntry = ctx.execEpoch++;
     q.hRowsView = nullptr;          // (set around a candidate run of the tail only; an execution that did not come back must not leave it)
     if (async) {
-        if (!partialOnly || !denseMode(q)) failUnsupported("asynchronous execution is available for dense partial aggregation only");
+        if (!partialOnly || !partialCapable(q)) failUnsupported("asynchronous execution is available for dense partial aggregation only");
         for (auto& p : q.pipelines)
             if (p.sink != SinkKind::AGGREGATE) failUnsupported("asynchronous execution needs a plan without join / materialize pipelines");
     }
@@ -1710,7 +1716,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
 void finalizeQuery(Query& q) {
     Context& ctx = q.ctx;
     if (!q.derived.empty() && !derivedExternal(q)) refuseDerived(q, "finalize");
-    if (!denseMode(q)) failUnsupported("partial execution / finalize is available for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("partial execution / finalize is available for dense aggregations only");
     RSQ_HIP(hipSetDevice(ctx.device));
     double t1 = nowMs();
     const bool devTail = !q.mergePublishedSeq && denseDeviceTailWanted(q);
@@ -1819,7 +1825,7 @@ void mergeShardResults(Query& into, const std::vector<Query*>& parts) {
 void setHoldTail(Query& q, bool hold) { q.holdTail = hold; }
 bool queryOrderedWithLimit(const Query& q) { return q.root && q.root->tag == RSQ_OP_ORDERBY && q.root->hasLimit; }
 bool queryAsyncCapable(const Query& q) {
-    if (!denseMode(q)) return false;
+    if (!partialCapable(q)) return false;
     for (auto& p : q.pipelines) if (p.sink != SinkKind::AGGREGATE) return false;
     return true;
 }
@@ -1866,7 +1872,7 @@ bool shardGroupsDisjoint(const std::vector<Query*>& parts, std::string& why) {
 
 void finalizeQueryHost(Query& q, const int64_t* words, size_t nWords) {
     if (!q.derived.empty()) refuseDerived(q, "finalize");
-    if (!denseMode(q)) failUnsupported("host finalize is available for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("host finalize is available for dense aggregations only");
     size_t need = q.accums.size() * (size_t)q.denseGroups;
     if (nWords != need) failInvalid("partial table has " + std::to_string(nWords) + " words, expected " + std::to_string(need));
     q.hAgg.assign((const uint64_t*)words, (const uint64_t*)words + nWords);
@@ -1875,7 +1881,7 @@ void finalizeQueryHost(Query& q, const int64_t* words, size_t nWords) {
 }
 
 void bindPartial(Query& q, void* dptr, size_t bytes) {
-    if (!denseMode(q)) failUnsupported("partial tables exist for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("partial tables exist for dense aggregations only");
     size_t need = q.accums.size() * (size_t)q.denseGroups * 8;
     if (!dptr || bytes < need) failInvalid("partial buffer too small: need " + std::to_string(need) + " bytes");
     if (q.dAgg && q.dAggOwned) q.ctx.free(q.dAgg);
@@ -1887,7 +1893,7 @@ void bindPartial(Query& q, void* dptr, size_t bytes) {
 // the kernel behind the merge collective: `gathered` = every rank's partial table back to back (one all-gather), reduced by
 // segment into this query's own partial table; enqueued on the context's stream, no synchronisation
 void mergeGathered(Query& q, const void* gathered, int nRanks) {
-    if (!denseMode(q)) failUnsupported("partial tables exist for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("partial tables exist for dense aggregations only");
     if (!gathered || nRanks < 1) failInvalid("merge needs the gathered tables of at least one rank");
     if (q.ctx.device < 0) throw Error(RSQ_ERR_DEVICE, "this context has no device (compile-only)");
     RSQ_HIP(hipSetDevice(q.ctx.device));
@@ -1902,7 +1908,7 @@ void mergeGathered(Query& q, const void* gathered, int nRanks) {
 }
 
 void partialBuffer(Query& q, void** dptr, int64_t* nMin, int64_t* nMax, int64_t* nSum) {
-    if (!denseMode(q)) failUnsupported("partial tables exist for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("partial tables exist for dense aggregations only");
     *dptr = q.dAgg;
     *nMin = q.nMinBlocks * q.denseGroups;
     *nMax = q.nMaxBlocks * q.denseGroups;
@@ -1939,9 +1945,9 @@ void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool re
     if (executions) *executions = q.kernelTimeLaunches;
     if (reset) { q.kernelTimeSumMs = 0; q.kernelTimeLaunches = 0; }
 }
-bool queryIsDense(const Query& q) { return denseMode(q); }
+bool queryIsDense(const Query& q) { return partialCapable(q); }
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr) {
-    if (!denseMode(q)) failUnsupported("partial tables exist for dense aggregations only");
+    if (!partialCapable(q)) failUnsupported("partial tables exist for dense aggregations only");
     *dptr = q.dAgg;
     *nMin = q.nMinBlocks * q.denseGroups; *nMax = q.nMaxBlocks * q.denseGroups; *nSum = q.nSumBlocks * q.denseGroups;
 }

@@ -225,6 +225,10 @@ struct Context {
     uint64_t columnImageBytes = 0;             // device memory of the tables' narrow and dictionary images (rsq_ctx_memory_stats)
     uint64_t planMemoClock = 0, planMemoHits = 0;
     bool planMemoOff = false;
+    // set by rsq_multi_query_compile around the compiles of a statement that runs on more than one shard: no dense group ids from dictionary
+    // codes there (codegen_agg.cpp tryDenseKeys) - a table the shards hold alike is not unified (nRowsTotal stays -1), and the group-level
+    // merge of the shards' results takes hash aggregations, not dense tables keyed by one context's dictionary
+    bool shardCompile = false;
 };
 
 rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // api.cpp: the host's struct (struct_size bytes), validated

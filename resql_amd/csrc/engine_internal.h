@@ -12,6 +12,7 @@
 
 #include "engine.h"
 #include "hostref.h"
+#include "dense_groups.h"
 
 namespace rsq {
 
@@ -127,15 +128,7 @@ struct Accum {
     Expr* inputExpr = nullptr;   // the input expression itself (null: the row index / a count), for the pre-compiled generic pipeline
 };
 
-struct DenseKey {
-    Expr* expr = nullptr;
-    Type type;
-    bool byteSet = false;
-    std::vector<uint8_t> values;     // byteSet: sorted distinct values
-    int64_t min = 0;
-    int64_t card = 1;
-    int64_t stride = 1;
-};
+// (DenseKey: dense_groups.h)
 
 enum class AggMode { NONE, DENSE_REG, DENSE_LDS_PRIVATE, DENSE_LDS_SHARED, DENSE_GLOBAL, AT_JOIN_ENTRY, HASH };
 enum class SinkKind { AGGREGATE, BUILD, MATERIALIZE };

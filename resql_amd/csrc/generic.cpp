@@ -177,6 +177,7 @@ bool buildGenericProgram(Query& q, GenericProgram& out, std::string& why) {
     // library — 80 ms with the ROCm stack loaded, which a cold TPC-H Q3 then paid on its way to the whole-pipeline interpreter)
     if (!q.nljs.empty()) { why = "a nested-loops join (the interpreters have no pair loop)"; return false; }
     if (!q.derived.empty()) { why = "a derived table (its columns are bound per execution)"; return false; }
+    if (q.agg && denseMode(q) && anyCodedKey(q.denseKeys)) { why = "a group key ranked by its dictionary code (the interpreters read the wide column and cannot rank a string)"; return false; }
     if (q.pipelines.size() != 1 || q.pipelines[0].sink != SinkKind::AGGREGATE || !q.agg) { why = "not a single scan -> aggregation pipeline"; return false; }
     if (!(q.aggMode == AggMode::DENSE_REG || q.aggMode == AggMode::DENSE_LDS_PRIVATE || q.aggMode == AggMode::DENSE_LDS_SHARED || q.aggMode == AggMode::DENSE_GLOBAL)) {
         why = "not a dense aggregation"; return false;

@@ -373,6 +373,7 @@ bool buildGenericPlan(Query& q, std::vector<GenericProgram2>& out, std::string& 
     out.clear();
     if (!q.nljs.empty()) { why = "a nested-loops join (the interpreters have no pair loop)"; return false; }
     if (!q.derived.empty()) { why = "a derived table (the programs hold column addresses; a derived table's are bound per execution)"; return false; }
+    if (q.agg && denseMode(q) && anyCodedKey(q.denseKeys)) { why = "a group key ranked by its dictionary code (the interpreters read the wide column and cannot rank a string)"; return false; }
     try {
         if (q.hashTables.size() > G2_MAX_TABLES) throw Error(RSQ_ERR_UNSUPPORTED, "too many hash tables");
         std::vector<OpNode*> scans;

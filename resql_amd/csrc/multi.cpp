@@ -571,6 +571,12 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 if (blobBytes[(size_t)t])
                     for (int i = 0; i < n; i++) unifyShardStats(*tab(i, t), allBlobs[(size_t)t].data(), n, blobBytes[(size_t)t]);
         }
+        // (more than one shard: every compile below keeps string group keys on the hash form - Context::shardCompile)
+        struct ShardCompile {
+            rsq_multi* m; bool on;
+            ShardCompile(rsq_multi* m_, bool on_) : m(m_), on(on_) { for (Context* c : m->ctxs) c->shardCompile = on; }
+            ~ShardCompile() { for (Context* c : m->ctxs) c->shardCompile = false; }
+        } shardCompile(m, n > 1);
         if (!mq->nlj) {
             for (int i = 0; i < n; i++) mq->qs.push_back(compileQuery(*m->ctxs[(size_t)i], *plan, tables + (size_t)i * (size_t)n_tables, n_tables));
         } else {

@@ -186,17 +186,6 @@ Val evalHost(const HostExpr& h, const std::vector<Val>& sym) {
     return r;
 }
 
-// ---- the groups the device produced ---------------------------------------------------------------
-struct Groups {
-    size_t n = 0, nKeys = 0, nAcc = 0;
-    std::vector<int64_t> firstRow;                 // [n]
-    std::vector<Val> keyData;                      // [n][nKeys], flat
-    std::vector<int64_t> accData;                  // [n][nAcc], flat (index = accums index)
-    std::vector<char> strings;                     // NUL-terminated bytes of string key values (Val::s points in here)
-    const Val* keys(size_t i) const { return keyData.data() + i * nKeys; }
-    const int64_t* acc(size_t i) const { return accData.data() + i * nAcc; }
-};
-
 }  // namespace
 
 // What a query's tail keeps between executions: the group arrays and the scratch of the emission order.  A million groups are
@@ -216,62 +205,14 @@ ReplayScratch& tailReplayScratch(Query& q) { return tailState(q).replay; }
 namespace {
 
 void groupsFromDense(Query& q, Groups& G) {
-    const int64_t D = q.denseGroups;
-    const size_t W = q.accums.size();
-    const uint64_t* table = q.hAggView ? q.hAggView : q.hAgg.data();
-    auto word = [&](size_t w, int64_t g) { return (int64_t)table[(size_t)(q.accumSlot[w] * D + g)]; };
-    G.nKeys = q.denseKeys.size(); G.nAcc = W;
-    // two passes over the dense table, both split over the host threads: count the groups present per part, then
-    // fill each part's slice (group order = dense id order, as before)
-    const int parts = tailThreads((size_t)D);
-    std::vector<size_t> cnt((size_t)parts + 1, 0);
-    parallelFor((size_t)D, parts, [&](size_t b, size_t e, int p) {
-        size_t c = 0;
-        for (size_t g = b; g < e; g++) if (word(0, (int64_t)g) != INT64_MAX) c++;
-        cnt[(size_t)p + 1] = c;
-    });
-    for (int p = 0; p < parts; p++) cnt[(size_t)p + 1] += cnt[(size_t)p];
-    const size_t present = cnt[(size_t)parts];
-    G.n = present;
-    G.firstRow.resize(present); G.keyData.resize(present * G.nKeys); G.accData.resize(present * W);
-    parallelFor((size_t)D, parts, [&](size_t b, size_t e, int p) {
-        size_t o = cnt[(size_t)p];
-        for (size_t gi = b; gi < e; gi++) {
-            const int64_t g = (int64_t)gi;
-            if (word(0, g) == INT64_MAX) continue;
-            G.firstRow[o] = word(0, g);
-            size_t k = 0;
-            for (auto& dk : q.denseKeys) {
-                int64_t rank = (g / dk.stride) % dk.card;
-                Val v; v.i = dk.byteSet ? (int64_t)dk.values[(size_t)rank] : dk.min + rank;
-                G.keyData[o * G.nKeys + k++] = v;
-            }
-            for (size_t w = 0; w < W; w++) G.accData[o * W + w] = word(w, g);
-            o++;
-        }
-    });
+    groupsFromDense(q.denseKeys, q.denseGroups, q.accumSlot, q.hAggView ? q.hAggView : q.hAgg.data(), G);
 }
 
 // candidate rows of a dense aggregate table (engine.cpp: ORDER BY ... LIMIT over a large dense table):
 // [first row | group id | accumulator blocks]
 Groups groupsFromDenseRows(Query& q) {
-    const size_t W = q.accums.size();
-    const size_t stride = (size_t)q.groupRowWords;
     Groups G;
-    G.n = (size_t)q.nGroupRows; G.nKeys = q.denseKeys.size(); G.nAcc = W;
-    G.firstRow.resize(G.n); G.keyData.resize(G.n * G.nKeys); G.accData.resize(G.n * W);
-    for (size_t i = 0; i < G.n; i++) {
-        const int64_t* r = &(q.hRowsView ? q.hRowsView : q.hGroupRows)[i * stride];
-        const int64_t g = r[1];
-        G.firstRow[i] = r[0];
-        size_t k = 0;
-        for (auto& dk : q.denseKeys) {
-            const int64_t rank = (g / dk.stride) % dk.card;
-            Val v; v.i = dk.byteSet ? (int64_t)dk.values[(size_t)rank] : dk.min + rank;
-            G.keyData[i * G.nKeys + k++] = v;
-        }
-        for (size_t w = 0; w < W; w++) G.accData[i * W + w] = r[2 + (size_t)q.accumSlot[w]];
-    }
+    groupsFromDenseRows(q.denseKeys, q.accumSlot, q.hRowsView ? q.hRowsView : q.hGroupRows, (size_t)q.nGroupRows, (size_t)q.groupRowWords, G);
     return G;
 }
 
@@ -462,6 +403,7 @@ void planDeviceTopK(Query& q) {
     OpNode* agg = q.agg;
     const bool dense = q.aggMode == AggMode::DENSE_GLOBAL;         // candidate rows [first row | group id | accumulator blocks]
     if (!agg || (q.aggMode != AggMode::AT_JOIN_ENTRY && q.aggMode != AggMode::HASH && !dense)) return;
+    if (dense) for (auto& dk : q.denseKeys) if (dk.coded && dk.spaceEquivalent) return;      // (candidates are chosen before the host merges such groups)
     OpNode* mat = nullptr; OpNode* orderBy = nullptr;
     std::vector<OpNode*> projections;
     for (OpNode* o = agg->parent; o; o = o->parent) {
@@ -536,6 +478,8 @@ void runTail(Query& q) {
     else if (q.candidateRun) G = groupsFromDenseRows(q);
     else groupsFromDense(q, G);
     if (q.aggMode == AggMode::HASH) mergeSpaceEquivalentGroups(q, G);
+    else if (q.aggMode != AggMode::AT_JOIN_ENTRY)      // (dense: two dictionary entries of a coded CHAR(n) key that differ in trailing spaces only are two ranks)
+        for (auto& dk : q.denseKeys) if (dk.coded && dk.spaceEquivalent) { mergeEqualGroups(q, G); break; }
     if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     tail: %.3f ms  groups from the device tables\n", nowMs() - t0);
     runTailOn(q, G);
 }
@@ -714,6 +658,9 @@ static TailShape buildTailShape(Query& q) {
 // and key descriptions the kernels take.
 bool planDenseDeviceTail(Query& q, DenseTailKeys& keys, DenseTailCols& cols, int& tupleSize, int64_t& limitRows) {
     if (!q.agg || q.denseKeys.empty() || q.denseKeys.size() > 4) return false;
+    // a dictionary-coded key: declined, the host tail runs (groupsFromDense decodes the rank into the entry's bytes; the device tail's keys
+    // are integers - DenseTailKey - and it neither knows the dictionary nor merges space-equivalent CHAR groups)
+    if (anyCodedKey(q.denseKeys)) return false;
     TailShape sh = buildTailShape(q);
     if (!sh.directRows || sh.orderBy || sh.cur.size() > 24) return false;
     keys.n = (int32_t)q.denseKeys.size();
