@@ -294,6 +294,32 @@ int   rsq_ref_emission_order(const uint64_t* hashes, int64_t n, uint64_t min_siz
  * memory.  RSQ_ERR_UNSUPPORTED for tables beyond the device path's range (2^31 slots). */
 int   rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t n, uint64_t min_size, uint32_t* out);
 
+/* ---- device primitives exposed for tests ---------------------------------------------------
+ * The engine's exact integer kernels (aot_kernels.hip) run on the caller's data, so that a test reaches their chunk, sub-block, wave and
+ * word boundaries with a few megabytes instead of the tables that reach them through a query.  Every pointer is host memory.  A call takes
+ * its device buffers from the context's allocator, runs on the context's stream, waits for it, copies the result back and frees the
+ * buffers.  *notes receives the bits of the device error word the call raised (64: the placement's record count is not the number of
+ * distinct keys or exceeds the capacity; 128 / 512: a look-back of the one-launch rank index / scan gave up and the result is void); the
+ * call clears them again, so the context stays usable.  RSQ_ERR_UNSUPPORTED on a context without a device, RSQ_ERR_INVALID for null
+ * pointers, negative sizes and shapes the kernels would read or write out of bounds with. */
+/* offsets[i] = counts[0] + ... + counts[i - 1] in 64 bits.  form 0: exclusiveScanCounts (three launches), 1: exclusiveScanCountsChained
+ * (one launch, decoupled look-back). */
+int   rsq_prim_exclusive_scan(rsq_ctx* ctx, const uint32_t* counts, int64_t n, int32_t form, uint64_t* offsets /* [n] */, uint32_t* notes);
+/* The rank index of a key bitmap of n_blocks 32-byte blocks [rank word | 7 bitmap words]: word 0 of every block comes back as the number
+ * of bits set in the bitmap words of the blocks before it, words 1..7 as they were; chunk_base[c] is the rank at block
+ * c * 1024 and chunk_base[n_chunks] the number of bits set.  form 0: rankTableIndex (two launches), 1: rankTableIndexChained (one
+ * launch; at most 1171 chunks). */
+int   rsq_prim_rank_index(rsq_ctx* ctx, uint32_t* blocks /* [n_blocks * 8], in and out */, int64_t n_blocks, int32_t form,
+                          uint32_t* chunk_base /* [ceil(n_blocks / 1024) + 1] */, uint32_t* notes);
+/* rankTablePlace: the blocks are indexed (form 0), the record counter is the sum of used[], and every record - n_words words, word 0 its
+ * key, used[w] of them at records[w * region * n_words] - is written to words_out at the rank of its key: the number of bits set below
+ * bit (key - bm_min), which lives in bit d & 31 of word 1 + (d >> 5) % 7 of block (d >> 5) / 7.  words_out is filled with 0xff bytes
+ * before the launch.  A record whose key lies outside [bm_min, bm_min + bm_bits) is skipped.  Requires bm_bits <= n_blocks * 224 and
+ * used[w] <= region. */
+int   rsq_prim_rank_place(rsq_ctx* ctx, const uint32_t* blocks /* [n_blocks * 8] */, int64_t n_blocks, int64_t bm_min, int64_t bm_bits,
+                          const int64_t* records /* [n_waves * region * n_words] */, const uint32_t* used /* [n_waves] */, int32_t n_waves,
+                          int32_t region, int32_t n_words, int64_t capacity, int64_t* words_out /* [capacity * n_words] */, uint32_t* notes);
+
 /* ---- SQL text in front of the path --------------------------------------
  * The reference turns SQL text into an operator tree with parseSql (src/parser/parseSql.h:130-166:
  * tokens of src/parser/lexer.y, grammar of src/parser/parser.y) and buildQuery (src/planner.h:409-497),

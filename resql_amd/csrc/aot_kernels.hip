@@ -764,7 +764,7 @@ template <int COMPACT_PER_THREAD>
 __global__ void __launch_bounds__(256) k_compact_entries(const i64* __restrict__ first, i64 cap, const i64* __restrict__ words, int nWords,
                                                          int wordsAos, const i64* __restrict__ acc, int nAcc, i64* __restrict__ out,
                                                          unsigned maxRows, unsigned* count, int unmix, int keyWord, int keyIs32, int keyDesc,
-                                                         u64* __restrict__ imageRange, u64* __restrict__ chain, unsigned launchNo, int narrow,
+                                                         u64* __restrict__ imageRange, int narrow,
                                                          const int* __restrict__ deref, int tabStride) {
     const int stride = 1 + nWords + nAcc;
     u64 imgMax = 0, imgMaxInv = 0;      // range of the sort-key images of the rows written (keyWord >= 0): max(u), max(~u)
@@ -791,52 +791,7 @@ __global__ void __launch_bounds__(256) k_compact_entries(const i64* __restrict__
         unsigned before = 0, total = 0;
 #pragma unroll
         for (int w = 0; w < 4; w++) { const unsigned c = s_wave[w]; if (w < wave) before += c; total += c; }
-        // where the chunk's rows go.  With a chain (RSQ_COMPACT_CHAINED=1, one chunk per workgroup): the rows of the chunks in front, by
-        // decoupled look-back (a wave reads 64 predecessors per round trip; see k_rank_blocks_chained); the rows then come out in slot
-        // order, whatever the workgroups' timing.  Default: one returning atomic per chunk on the row counter.
-        if (chain) {
-            if (t < 64) {
-                const u64 tag = ((u64)(launchNo & 0x3fffffffu)) << 2;
-                auto stateOf = [&](u64 v) -> unsigned { return ((v >> 2) & 0x3fffffffull) == (u64)(launchNo & 0x3fffffffu) ? (unsigned)(v & 3ull) : 0u; };
-                const int ln = t;
-                const i64 me = lo / chunkSlots;
-                unsigned base = 0;
-                if (me == 0) { if (ln == 0) __hip_atomic_store(&chain[0], ((u64)total << 32) | tag | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-                else {
-                    if (ln == 0) __hip_atomic_store(&chain[me], ((u64)total << 32) | tag | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const long long t0 = wall_clock64();
-                    i64 hi = me - 1;
-                    for (;;) {
-                        const i64 idx = hi - ln;
-                        const u64 v = idx >= 0 ? __hip_atomic_load(&chain[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (tag | 2ull);      // (in front of chunk 0: nothing, inclusive)
-                        const unsigned st = stateOf(v);
-                        const u64 ready = __ballot(st != 0u), incl = __ballot(st == 2u);
-                        unsigned take = 0; bool done = false, moved = false;
-                        if (incl) {
-                            const int f = __ffsll((long long)incl) - 1;
-                            const u64 below = (1ull << f) - 1ull;
-                            if ((ready & below) == below) { take = ln <= f ? (unsigned)(v >> 32) : 0u; done = true; }
-                        } else if (ready == ~0ull) { take = (unsigned)(v >> 32); moved = true; }
-                        if (done || moved) {
-#pragma unroll
-                            for (int m = 32; m >= 1; m >>= 1) take += (unsigned)__shfl_xor((int)take, m, 64);
-                            base += take;
-                            if (done) break;
-                            hi -= 64;
-                            continue;
-                        }
-                        // (not reachable - workgroups start in index order; the rows would overlap, so the count is made to say so: the host fails the execution)
-                        if (wall_clock64() - t0 > 2000000ll) { base = 0; if (ln == 0) atomicMax(count, 0xffffffffu); break; }      // 20 ms
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    if (ln == 0) __hip_atomic_store(&chain[me], ((u64)(base + total) << 32) | tag | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (ln == 0) {
-                    s_base = base;
-                    if (lo + chunkSlots >= cap) atomicMax(count, base + total);          // the last chunk knows the number of rows (0xffffffff: a look-back gave up)
-                }
-            }
-        } else
+        // where the chunk's rows go: one returning atomic per chunk on the row counter
         if (t == 0) s_base = total ? atomicAdd(count, total) : 0u;
         __syncthreads();
         if (total) {
@@ -976,10 +931,8 @@ void compactEntries(Context& ctx, const int64_t* firstRow, int64_t capacity, con
     const int64_t chunkSlots = 256 * (int64_t)perThread;
     const int64_t nChunks = std::max<int64_t>(1, (capacity + chunkSlots - 1) / chunkSlots);
     unsigned grid = (unsigned)std::min<int64_t>(8 * (int64_t)ctx.numCUs, nChunks);
-    u64* chain = nullptr;
-    unsigned launchNo = 0;
 #define RSQ_LAUNCH_COMPACT(PT) hipLaunchKernelGGL(k_compact_entries<PT>, dim3(grid), dim3(256), 0, ctx.stream, (const i64*)firstRow, (i64)capacity, \
-                       (const i64*)words, nWords, wordsAos ? 1 : 0, (const i64*)acc, nAcc, (i64*)outRows, (unsigned)maxRows, count, unmix ? 1 : 0, imageRange ? keyWord : -1, keyIs32 ? 1 : 0, keyDesc ? 1 : 0, (u64*)imageRange, chain, launchNo, narrow ? 1 : 0, deref, tabStride)
+                       (const i64*)words, nWords, wordsAos ? 1 : 0, (const i64*)acc, nAcc, (i64*)outRows, (unsigned)maxRows, count, unmix ? 1 : 0, imageRange ? keyWord : -1, keyIs32 ? 1 : 0, keyDesc ? 1 : 0, (u64*)imageRange, narrow ? 1 : 0, deref, tabStride)
     if (perThread >= 64) RSQ_LAUNCH_COMPACT(64); else if (perThread >= 32) RSQ_LAUNCH_COMPACT(32); else RSQ_LAUNCH_COMPACT(16);
 #undef RSQ_LAUNCH_COMPACT
     RSQ_HIP(hipGetLastError());

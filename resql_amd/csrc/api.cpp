@@ -150,6 +150,42 @@ void unifyShardStats(Table& t, const void* blobs, int nShards, size_t blobBytes)
 }
 }  // namespace rsq
 
+// helpers of the device primitives exposed for tests (rsq_prim_*, below)
+namespace {
+// device buffers of one call: given back when it ends, also by an exception, once the stream has drained
+struct PrimBuffers {
+    Context& c;
+    std::vector<void*> held;
+    explicit PrimBuffers(Context& ctx) : c(ctx) {}
+    ~PrimBuffers() { (void)hipStreamSynchronize(c.stream); for (void* p : held) c.free(p); }
+    template <typename E> E* take(size_t n) { void* p = c.alloc(std::max<size_t>(n * sizeof(E), 16)); held.push_back(p); return (E*)p; }
+};
+void primSync(Context& c) { RSQ_HIP(hipStreamSynchronize(c.stream)); c.streamDrained(); }
+uint32_t primErrWord(Context& c) {
+    uint32_t e = 0;
+    RSQ_HIP(hipMemcpyAsync(&e, c.dErr, 4, hipMemcpyDeviceToHost, c.stream));
+    primSync(c);
+    return e;
+}
+// the bits the call raised, and the error word as it was before the call
+void primNotes(Context& c, uint32_t before, uint32_t* notes) {
+    const uint32_t after = primErrWord(c), raised = after & ~before;
+    if (raised) {
+        const uint32_t keep = after & ~raised;
+        RSQ_HIP(hipMemcpyAsync(c.dErr, &keep, 4, hipMemcpyHostToDevice, c.stream));
+        primSync(c);
+    }
+    *notes = raised;
+}
+Context& primContext(rsq_ctx* ctx) {
+    Context& c = *C(ctx);
+    if (c.device < 0) failUnsupported("this context has no device (compile-only)");
+    RSQ_HIP(hipSetDevice(c.device));
+    return c;
+}
+const int64_t kPrimMaxRankBlocks = (int64_t)1171 * RSQ_RANK_CHUNK_BLOCKS;      // a key domain of 2^28 bits (k_rank_blocks_chained)
+}  // namespace
+
 extern "C" {
 
 int64_t rsq_table_stats_bytes(const rsq_table* t) { return t ? (int64_t)tableStatsBytes(*reinterpret_cast<const Table*>(t)) : -1; }
@@ -446,6 +482,92 @@ int rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t 
         RSQ_HIP(hipStreamSynchronize(c.stream));
         RSQ_HIP(hipMemcpy(out, dO, (size_t)n * 4, hipMemcpyDeviceToHost));
         c.free(dH); c.free(dO); c.free(work);
+    });
+}
+
+// ---- device primitives exposed for tests ----
+int rsq_prim_exclusive_scan(rsq_ctx* ctx, const uint32_t* counts, int64_t n, int32_t form, uint64_t* offsets, uint32_t* notes) {
+    if (!ctx || !notes || n < 0 || (n > 0 && (!counts || !offsets)) || (form != 0 && form != 1)) return RSQ_ERR_INVALID;
+    *notes = 0;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        if (n == 0) return;
+        const uint32_t before = primErrWord(c);
+        PrimBuffers b(c);
+        uint32_t* dCnt = b.take<uint32_t>((size_t)n);
+        uint64_t* dOff = b.take<uint64_t>((size_t)n);
+        const size_t tempBytes = scanTempBytes(n);
+        void* temp = b.take<char>(tempBytes);
+        RSQ_HIP(hipMemcpyAsync(dCnt, counts, (size_t)n * 4, hipMemcpyHostToDevice, c.stream));
+        if (form == 1) exclusiveScanCountsChained(c, dCnt, dOff, n, temp, tempBytes);
+        else exclusiveScanCounts(c, dCnt, dOff, n, temp, tempBytes);
+        RSQ_HIP(hipMemcpyAsync(offsets, dOff, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_rank_index(rsq_ctx* ctx, uint32_t* blocks, int64_t n_blocks, int32_t form, uint32_t* chunk_base, uint32_t* notes) {
+    if (!ctx || !notes || !chunk_base || n_blocks < 0 || (n_blocks > 0 && !blocks) || (form != 0 && form != 1)) return RSQ_ERR_INVALID;
+    *notes = 0;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        if (n_blocks > kPrimMaxRankBlocks) failUnsupported("a key bitmap of more than 2^28 bits");
+        if (n_blocks == 0) { chunk_base[0] = 0; return; }
+        const uint32_t before = primErrWord(c);
+        const size_t nChunks = (size_t)((n_blocks + RSQ_RANK_CHUNK_BLOCKS - 1) / RSQ_RANK_CHUNK_BLOCKS);
+        PrimBuffers b(c);
+        uint32_t* dBm = b.take<uint32_t>((size_t)n_blocks * 8);
+        uint32_t* dTotal = b.take<uint32_t>(nChunks);
+        uint32_t* dBase = b.take<uint32_t>(nChunks + 1);
+        RSQ_HIP(hipMemcpyAsync(dBm, blocks, (size_t)n_blocks * 32, hipMemcpyHostToDevice, c.stream));
+        if (form == 1) {
+            RSQ_HIP(hipMemsetAsync(dTotal, 0, nChunks * 4, c.stream));          // the chain words: zero before the launch
+            rankTableIndexChained(c, dBm, n_blocks, dTotal, dBase);
+        } else rankTableIndex(c, dBm, n_blocks, dTotal, dBase);
+        RSQ_HIP(hipMemcpyAsync(blocks, dBm, (size_t)n_blocks * 32, hipMemcpyDeviceToHost, c.stream));
+        RSQ_HIP(hipMemcpyAsync(chunk_base, dBase, (nChunks + 1) * 4, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_rank_place(rsq_ctx* ctx, const uint32_t* blocks, int64_t n_blocks, int64_t bm_min, int64_t bm_bits, const int64_t* records,
+                        const uint32_t* used, int32_t n_waves, int32_t region, int32_t n_words, int64_t capacity, int64_t* words_out,
+                        uint32_t* notes) {
+    if (!ctx || !notes || !blocks || !records || !used || !words_out) return RSQ_ERR_INVALID;
+    *notes = 0;
+    // (the kernels trust these: a block index comes from bm_bits, a record address from used[] and region)
+    if (n_blocks < 1 || n_blocks > kPrimMaxRankBlocks || bm_bits < 1 || bm_bits > n_blocks * 224 || n_waves < 1 || n_waves > (1 << 20) || region < 1 ||
+        n_words < 1 || n_words > 64 || capacity < 1 || capacity > ((int64_t)1 << 31))
+        return RSQ_ERR_INVALID;
+    uint64_t nRecords = 0;
+    for (int32_t w = 0; w < n_waves; w++) { if (used[w] > (uint32_t)region) return RSQ_ERR_INVALID; nRecords += used[w]; }
+    if (nRecords > 0xffffffffull) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        const uint32_t before = primErrWord(c);
+        const size_t nChunks = (size_t)((n_blocks + RSQ_RANK_CHUNK_BLOCKS - 1) / RSQ_RANK_CHUNK_BLOCKS);
+        const size_t recWords = (size_t)n_waves * (size_t)region * (size_t)n_words, outWords = (size_t)capacity * (size_t)n_words;
+        PrimBuffers b(c);
+        uint32_t* dBm = b.take<uint32_t>((size_t)n_blocks * 8);
+        uint32_t* dTotal = b.take<uint32_t>(nChunks);
+        uint32_t* dBase = b.take<uint32_t>(nChunks + 1);
+        int64_t* dRec = b.take<int64_t>(recWords);
+        uint32_t* dUsed = b.take<uint32_t>((size_t)n_waves);
+        uint32_t* dCount = b.take<uint32_t>(1);
+        int64_t* dWords = b.take<int64_t>(outWords);
+        const uint32_t count = (uint32_t)nRecords;
+        RSQ_HIP(hipMemcpyAsync(dBm, blocks, (size_t)n_blocks * 32, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemcpyAsync(dRec, records, recWords * 8, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemcpyAsync(dUsed, used, (size_t)n_waves * 4, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemcpyAsync(dCount, &count, 4, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemsetAsync(dWords, 0xff, outWords * 8, c.stream));
+        rankTableIndex(c, dBm, n_blocks, dTotal, dBase);
+        rankTablePlace(c, dRec, dUsed, (uint32_t)n_waves, (uint32_t)region, dCount, n_words, dBm, bm_min, bm_bits, dBase, n_blocks, dWords, capacity);
+        RSQ_HIP(hipMemcpyAsync(words_out, dWords, outWords * 8, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
     });
 }
 

@@ -500,9 +500,12 @@ void materializePipeline(Query& q, Pipeline& p) {
     RSQ_HIP(hipMemsetAsync(q.dMatTileCnt + (tiles - 2), 0, 3 * 4, ctx.stream));
     q.matLimit = 0;
     launchPipeline(q, p, -1, true);
-    const bool chainedOk = !(getenv("RSQ_SCAN_CHAINED") && atoi(getenv("RSQ_SCAN_CHAINED")) == 0);
+    // RSQ_SCAN_CHAINED: 0 never the one-launch scan, 2 at every size (tests: the form is otherwise out of a small table's reach), else by size
+    const int chainedWhen = getenv("RSQ_SCAN_CHAINED") ? atoi(getenv("RSQ_SCAN_CHAINED")) : 1;
+    const bool chainedOk = chainedWhen != 0;
     // (the one-launch scan pays from ~8 M counts on; one count per 128 rows means tables beyond a billion rows)
-    const bool chained = chainedOk && !q.scanChainedOff && tiles + 1 >= (8ll << 20);
+    const bool chained = chainedOk && !q.scanChainedOff && (chainedWhen == 2 || tiles + 1 >= (8ll << 20));
+    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     %s: offset scan of %lld counts in %s\n", p.entry.c_str(), (long long)(tiles + 1), chained ? "one launch" : "three launches");
     if (chained) exclusiveScanCountsChained(ctx, q.dMatTileCnt, q.dMatOffs, tiles + 1, q.dScanTemp, q.scanTempBytes);
     else exclusiveScanCounts(ctx, q.dMatTileCnt, q.dMatOffs, tiles + 1, q.dScanTemp, q.scanTempBytes);
     q.report.num_kernels++;

@@ -93,7 +93,6 @@ Context::~Context() {
         (void)hipSetDevice(device);
         for (auto& kv : kernels) if (kv.second.module) (void)hipModuleUnload(kv.second.module);
         (void)hipDeviceSynchronize();
-        if (dCompactChain) free(dCompactChain);
         if (spareTailArena.dev) free(spareTailArena.dev);
         if (spareTailArena.pinned) freePinned(spareTailArena.pinned);
         for (auto& e : scratchFreeList) free(e.first);

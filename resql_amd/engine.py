@@ -140,6 +140,9 @@ def lib():
         L.rsq_free.argtypes = [vp]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
+        L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.rsq_prim_rank_index.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.rsq_prim_rank_place.argtypes = [vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, i64, vp, vp]
         L.rsq_measure_read_bandwidth.argtypes = [vp, C.c_size_t, i32, C.POINTER(C.c_double)]
         L.rsq_sql_plan_select.argtypes = [vp, C.c_char_p, C.POINTER(vp), i32, C.POINTER(vp)]
         L.rsq_sql_plan_desc.restype = C.POINTER(P.rsq_plan_desc)
@@ -192,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_source", "rsq_query_explain",
     "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
+    "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_destroy",
@@ -201,6 +205,7 @@ EXPORTED_SYMBOLS = [
 ]
 
 GEN_LINEITEM, GEN_ORDERS, GEN_CUSTOMER, GEN_SYNTHETIC = 0, 1, 2, 3
+RANK_CHUNK_BLOCKS = 1024      # csrc/engine.h RSQ_RANK_CHUNK_BLOCKS: 32-byte bitmap blocks per entry of the rank index's chunk_base
 
 
 class Context:
@@ -244,6 +249,37 @@ class Context:
         m.struct_size = C.sizeof(rsq_memory_stats)
         self._check(self._L.rsq_ctx_memory_stats(self.h, C.byref(m)))
         return {k: getattr(m, k) for k, _ in rsq_memory_stats._fields_ if k not in ("struct_size", "reserved0")}
+
+    # ---- device primitives exposed for tests (resql_hip.h rsq_prim_*): numpy arrays in, (results..., notes) out ----
+    def prim_scan(self, counts: np.ndarray, form: int):
+        """exclusive scan of uint32 counts into uint64 offsets; form 0: three launches, 1: one launch"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        offsets = np.empty(len(counts), dtype=np.uint64)
+        notes = C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_exclusive_scan(self.h, counts.ctypes.data, len(counts), form, offsets.ctypes.data, C.addressof(notes)))
+        return offsets, notes.value
+
+    def prim_rank_index(self, blocks: np.ndarray, form: int):
+        """rank index of a key bitmap [n_blocks, 8] of uint32 (word 0: rank, 1..7: bits); form 0: two launches, 1: one launch"""
+        out = np.array(blocks, dtype=np.uint32, order="C").reshape(-1, 8)
+        chunk_base = np.full((len(out) + RANK_CHUNK_BLOCKS - 1) // RANK_CHUNK_BLOCKS + 1, 0xffffffff, dtype=np.uint32)
+        notes = C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_rank_index(self.h, out.ctypes.data, len(out), form, chunk_base.ctypes.data, C.addressof(notes)))
+        return out, chunk_base, notes.value
+
+    def prim_rank_place(self, blocks: np.ndarray, bm_min: int, bm_bits: int, records: np.ndarray, used: np.ndarray, region: int, n_words: int,
+                        capacity: int):
+        """records [n_waves * region * n_words] of int64 (word 0 of a record: its key) placed at the rank of their keys: [capacity, n_words]"""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint32).reshape(-1, 8)
+        records = np.ascontiguousarray(records, dtype=np.int64)
+        used = np.ascontiguousarray(used, dtype=np.uint32)
+        if records.size != len(used) * region * n_words:
+            raise ValueError("records must hold n_waves * region * n_words words")
+        out = np.zeros((capacity, n_words), dtype=np.int64)
+        notes = C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_rank_place(self.h, blocks.ctypes.data, len(blocks), bm_min, bm_bits, records.ctypes.data, used.ctypes.data,
+                                                len(used), region, n_words, capacity, out.ctypes.data, C.addressof(notes)))
+        return out, notes.value
 
     def set_stream(self, hip_stream: Optional[int]):
         """launch on the caller's HIP stream (an integer handle, 0 = the null stream; e.g.

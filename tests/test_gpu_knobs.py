@@ -23,6 +23,7 @@ KNOBS = [
     ("RSQ_FUSED_STEP", "0", ("tpch", "fuzz")),           # the one-launch step as separate launches (its fallback after an exception)
     ("RSQ_FUSED_SELECT", "0", ("topk",)),                # candidate selection as separate launches (fallback of a timed-out meeting point)
     ("RSQ_SCAN_CHAINED", "0", ("rows", "joins")),        # offset scan in three launches (fallback of a timed-out look-back)
+    ("RSQ_SCAN_CHAINED", "2", ("rows", "joins")),        # ... in one launch at every size (by itself only beyond a billion rows; tests/test_gpu_materialize_passes.py proves the form)
     ("RSQ_RANK_CHAINED", "0", ("joins", "q3")),          # rank index in two launches (fallback of a timed-out look-back)
     ("RSQ_PUBLISH_STATUS", "0", ("joins", "q3", "topk")),  # status words by copies (hosts without a device view of pinned memory)
     ("RSQ_COMPACT", "0", ("joins", "fuzz", "q3")),       # no wave compaction (pipelines that are not selective take this form anyway)

@@ -6,7 +6,7 @@ lanes), when nearly none does (few live tiles), and under LIMIT."""
 import numpy as np
 import pytest
 
-from resql_amd import plan as P
+from resql_amd import engine, plan as P
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
@@ -78,3 +78,28 @@ def test_limit_takes_the_first_tuples_in_scan_order(gpu_ctx, limit):
         q.close()
         for t in tabs:
             t.close()
+
+
+@pytest.mark.parametrize("pass_fraction", [0.0005, 0.97])
+def test_offsets_from_the_one_launch_scan(monkeypatch, capfd, pass_fraction):
+    """RSQ_SCAN_CHAINED=2: the offsets of the write pass come from k_scan_chained, which the engine takes by itself only beyond a billion
+    rows.  1 200 000 rows are 9378 tile counts - three chunks of the scan, so two of them look back.  Which form ran is read from the
+    trace (RSQ_TRACE: "offset scan of N counts in one launch"); with the switch ignored that line says "three launches" and this fails."""
+    monkeypatch.setenv("RSQ_SCAN_CHAINED", "2")
+    monkeypatch.setenv("RSQ_TRACE", "1")
+    dim, fact = _tables(1_200_000, 3_000, pass_fraction, seed=int(pass_fraction * 10_000) + 7)
+    plan = _plan(dim, fact, False)
+    want = orc.execute(plan)
+    ctx = engine.Context(device=0)
+    try:
+        tabs = [ctx.table(t) for t in plan.tables]
+        q = ctx.compile(plan, tabs)
+        for _ in range(3):
+            capfd.readouterr()
+            q.execute()
+            trace = capfd.readouterr().err
+            assert "offset scan of 9378 counts in one launch" in trace and "three launches" not in trace, trace
+            got = q.result()
+            assert got.n_rows == want.n_rows and got.text == want.text
+    finally:
+        ctx.close()
