@@ -6,6 +6,8 @@
 
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <string>
 #include <vector>
 
 #include "expr.h"
@@ -60,6 +62,54 @@ inline Val denseKeyValue(const DenseKey& dk, int64_t rank, char* strings, size_t
         sp += w + 1;
     } else v.i = dk.byteSet ? (int64_t)dk.values[(size_t)rank] : dk.min + rank;
     return v;
+}
+
+// ---- a coded key in the device tail (devtail.hip) -------------------------------------------------
+// Values::hash adds a string value's contribution to the running sum (hostref.cpp refHashValue, the CHAR(n > 1) and VARCHAR cases), so a
+// coded key's part of a group's hash depends on its rank alone: term[rank] = refHashValue(0, entry, type).  The two loops are restated
+// here (this header does not see hostref.h) with the same character arithmetic: a signed char, a 32-bit multiply, sign extension.
+inline uint64_t codedEntryHashTerm(const uint8_t* entry, const Type& t) {
+    const char* s = (const char*)entry;
+    uint64_t h = 0;
+    if (t.tag == RSQ_CHAR) {       // hashChar: the declared length, missing characters count as ' '
+        bool ended = false;
+        for (int i = 0; i < t.len; i++) {
+            char c;
+            if (!ended && s[i] != '\0') c = s[i]; else { ended = true; c = ' '; }
+            const int32_t m = (int32_t)((uint32_t)(int)c * 31636373u);
+            h = h + (uint64_t)(int64_t)m + (uint64_t)(int64_t)c;
+        }
+        return h;
+    }
+    for (int i = 0; i < t.len && s[i] != '\0'; i++) {      // hashVarchar: the characters up to the first NUL
+        const int c = s[i];
+        const int32_t m = (int32_t)((uint32_t)c * 31636373u);
+        h = h + (uint64_t)(int64_t)m + (uint64_t)(int64_t)c;
+    }
+    return h;
+}
+inline void codedKeyHashTerms(const DenseKey& dk, std::vector<uint64_t>& terms) {
+    const size_t w = (size_t)dk.type.len;
+    terms.resize((size_t)dk.card);
+    for (size_t e = 0; e < (size_t)dk.card; e++) terms[e] = codedEntryHashTerm(dk.dict.data() + e * w, dk.type);
+}
+// rank -> the smallest rank whose entry is the same value to the reference: CHAR(n) entries are equal up to trailing spaces (the rule of
+// codegen_agg.cpp tryDenseKeys and tail.cpp mergeEqualGroups), VARCHAR entries only when they are the same entry.  true: some rank moved.
+inline bool codedKeyClasses(const DenseKey& dk, std::vector<uint32_t>& cls) {
+    const size_t w = (size_t)dk.type.len;
+    cls.resize((size_t)dk.card);
+    bool any = false;
+    std::map<std::string, uint32_t> first;
+    for (size_t e = 0; e < (size_t)dk.card; e++) {
+        cls[e] = (uint32_t)e;
+        if (dk.type.tag != RSQ_CHAR) continue;
+        const char* v = (const char*)dk.dict.data() + e * w;
+        size_t n = strnlen(v, w);
+        while (n > 0 && v[n - 1] == ' ') n--;
+        auto at = first.emplace(std::string(v, n), (uint32_t)e);
+        if (!at.second) { cls[e] = at.first->second; any = true; }
+    }
+    return any;
 }
 
 // table: [block][group] words, accumulator w in block accumSlot[w]; a group is present when its first-row word is not INT64_MAX

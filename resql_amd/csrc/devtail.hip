@@ -5,6 +5,8 @@
 // groups that was 85 ms of host work behind 8 ms of kernels (round 2): reading 32 MB of table back, building group arrays,
 // sorting them by first row, hashing, replaying the reference's table, writing a million packed tuples.  Here the per-group
 // work stays on the GPU:
+//   k_dense_fold / k_dense_spell          (a dictionary-coded CHAR(n) key with entries equal up to trailing spaces only) those
+//                                         groups merged into one, in place, and the member whose spelling the group shows
 //   k_present_flags / k_present_scatter   the groups that occur (first-row word != +inf), compacted in group-id order
 //   radixSortPairs                        those groups ordered by their first input row (LSD radix sort, 8-bit digits,
 //                                         stable: wave-level digit matching + per-wave digit counts in LDS)
@@ -15,6 +17,9 @@
 // The host keeps the one step that is a chain of data-dependent decisions: the slot order of the reference's table
 // (hostref.cpp refEmissionOrderParallel, itself cut into independent probe clusters).  8 bytes per group go up, 4 come
 // back, the finished tuples go up once.
+// A dictionary-coded string key (RSQ_DICT_SCANS=1) is a rank like every other dense key: its part of the hash is a table look-up
+// (the term of an entry does not depend on the other keys), its bytes in the tuple are the entry's, from the statement's own copy
+// of the dictionary.
 #include <algorithm>
 #include <utility>
 #include <vector>
@@ -140,6 +145,7 @@ __global__ void __launch_bounds__(256) k_dense_hashes(const u32* __restrict__ gi
         const u32 g = gids[i];
         u64 h = 0;
         for (int k = 0; k < keys.n; k++) {
+            if (keys.k[k].len > 0) { h += keys.k[k].terms[((i64)g / keys.k[k].stride) % keys.k[k].card]; continue; }      // coded: the entry's term
             const i64 v = dense_key_value(keys.k[k], g);
             switch (keys.k[k].typeTag) {
                 case RSQ_BIGINT: case RSQ_DECIMAL: h += (u64)v * A + B; break;
@@ -154,12 +160,28 @@ __global__ void __launch_bounds__(256) k_dense_hashes(const u32* __restrict__ gi
 
 // ---- the result relation's packed tuples --------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dense_rows(const u64* __restrict__ table, i64 D, const u32* __restrict__ gids, const u32* __restrict__ order,
-                                                    i64 nRows, DenseTailKeys keys, DenseTailCols cols, int tupleSize, u8* __restrict__ out, u32* err) {
+                                                    i64 nRows, DenseTailKeys keys, DenseTailCols cols, int tupleSize, const u32* __restrict__ spell,
+                                                    u8* __restrict__ out, u32* err) {
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < nRows; i += (i64)gridDim.x * blockDim.x) {
         const u32 g = gids[order ? order[i] : (u32)i];
         u8* dst = out + (size_t)i * (size_t)tupleSize;
         for (int c = 0; c < cols.n; c++) {
             const DenseTailCol& col = cols.c[c];
+            if (col.kind == 0 && keys.k[col.a].len > 0) {
+                // a coded key: the entry's bytes up to the first NUL, zeros to len + 1 (as k_row_result_rows writes a string by value);
+                // of a merged group, the entry of the member that spells it
+                const DenseTailKey& key = keys.k[col.a];
+                const i64 rank = ((i64)(spell ? spell[g] : g) / key.stride) % key.card;
+                const u8* e = key.dict + (size_t)rank * (size_t)key.len;
+                u8* p = dst + col.offset;
+                bool ended = false;
+                for (int b = 0; b < col.width; b++) {
+                    const u8 ch = (ended || b >= key.len) ? (u8)0 : e[b];
+                    if (ch == 0) ended = true;
+                    p[b] = ch;
+                }
+                continue;
+            }
             i64 v;
             if (col.kind == 0) v = dense_key_value(keys.k[col.a], g);
             else if (col.kind == 1) v = (i64)table[(size_t)col.a * (size_t)D + g];
@@ -172,6 +194,61 @@ __global__ void __launch_bounds__(256) k_dense_rows(const u64* __restrict__ tabl
             for (int b = 0; b < col.width; b++) p[b] = (u8)((u64)v >> (8 * b));
         }
     }
+}
+
+// ---- groups of coded CHAR(n) keys that are one group to the reference -------------------------------------------------------
+// Two dictionary entries that differ in trailing spaces only are two ranks, hence two dense groups, and ONE group to the reference
+// (CHAR equality ignores trailing spaces; the group shows the spelling of its first row): the device form of tail.cpp
+// mergeEqualGroups over the [block][group] table.  The host maps every rank to its class's smallest rank (dense_groups.h
+// codedKeyClasses); a group whose id changes under the maps is a member, the id it changes to its representative's.
+//   k_dense_fold    every present member merges its cells into the representative's: wrapping int64 sum, min, max (64-bit
+//                   atomics; several members may reach one representative at once), its first row by min.  A representative is never
+//                   a member, so the cells a thread reads are not written here.  spell[g] = g for every group.
+//   k_dense_spell   the member whose first row is the group's (first rows are row numbers: at most one) leaves its id in
+//                   spell[representative]; every member's first-row word becomes +inf, k_present_flags drops it.
+// The table is folded in place: the execution's start puts the whole table back to its identities (enqueueTableInit).
+__device__ __forceinline__ i64 fold_representative(const DenseFoldSpec& s, i64 g) {
+    i64 r = 0;
+    for (int k = 0; k < s.nKeys; k++) {
+        const i64 rank = (g / s.stride[k]) % s.card[k];
+        r += (s.classOf[k] ? (i64)s.classOf[k][rank] : rank) * s.stride[k];
+    }
+    return r;
+}
+__global__ void __launch_bounds__(256) k_dense_fold(u64* table, i64 D, DenseFoldSpec s, u32* __restrict__ spell) {
+    const size_t firstAt = (size_t)s.accBlock[0] * (size_t)D;
+    for (i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x; g < D; g += (i64)gridDim.x * blockDim.x) {
+        spell[g] = (u32)g;
+        const i64 r = fold_representative(s, g);
+        if (r == g) continue;
+        const i64 first = (i64)table[firstAt + (size_t)g];
+        if (first == 0x7fffffffffffffffll) continue;
+        for (int w = 1; w < s.nAcc; w++) {
+            const size_t at = (size_t)s.accBlock[w] * (size_t)D;
+            const u64 v = table[at + (size_t)g];
+            if (s.accKind[w] == 0) atomicAdd(&table[at + (size_t)r], v);      // (wrapping: the engine's int64 sum)
+            else if (s.accKind[w] == 2) atomicMin(reinterpret_cast<i64*>(&table[at + (size_t)r]), (i64)v);
+            else atomicMax(reinterpret_cast<i64*>(&table[at + (size_t)r]), (i64)v);
+        }
+        atomicMin(reinterpret_cast<i64*>(&table[firstAt + (size_t)r]), first);
+    }
+}
+__global__ void __launch_bounds__(256) k_dense_spell(i64* first, i64 D, DenseFoldSpec s, u32* __restrict__ spell) {
+    for (i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x; g < D; g += (i64)gridDim.x * blockDim.x) {
+        const i64 r = fold_representative(s, g);
+        if (r == g) continue;
+        const i64 f = first[g];
+        if (f == 0x7fffffffffffffffll) continue;
+        if (f == first[r]) spell[r] = (u32)g;      // (first[r] is no member's word: nobody writes it here)
+        first[g] = 0x7fffffffffffffffll;
+    }
+}
+void denseFoldEqualGroups(Context& ctx, uint64_t* table, int64_t D, const DenseFoldSpec& spec, uint32_t* spell) {
+    if (D <= 0) return;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (D + 255) / 256));
+    hipLaunchKernelGGL(k_dense_fold, dim3(grid), dim3(256), 0, ctx.stream, (u64*)table, (i64)D, spec, spell);
+    hipLaunchKernelGGL(k_dense_spell, dim3(grid), dim3(256), 0, ctx.stream, (i64*)table + (size_t)spec.accBlock[0] * (size_t)D, (i64)D, spec, spell);
+    RSQ_HIP(hipGetLastError());
 }
 
 // ---- the same tail over the group rows of a hash / join-entry aggregation -----------------------------------------------------------
@@ -418,10 +495,10 @@ void denseGroupHashes(Context& ctx, const uint32_t* gids, int64_t n, const Dense
 }
 
 void denseResultRows(Context& ctx, const uint64_t* table, int64_t D, const uint32_t* gids, const uint32_t* order, int64_t nRows, const DenseTailKeys& keys,
-                     const DenseTailCols& cols, int tupleSize, uint8_t* out) {
+                     const DenseTailCols& cols, int tupleSize, const uint32_t* spell, uint8_t* out) {
     if (nRows <= 0) return;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (nRows + 255) / 256));
-    hipLaunchKernelGGL(k_dense_rows, dim3(grid), dim3(256), 0, ctx.stream, (const u64*)table, (i64)D, gids, order, (i64)nRows, keys, cols, tupleSize, out, ctx.dErr);
+    hipLaunchKernelGGL(k_dense_rows, dim3(grid), dim3(256), 0, ctx.stream, (const u64*)table, (i64)D, gids, order, (i64)nRows, keys, cols, tupleSize, spell, out, ctx.dErr);
     RSQ_HIP(hipGetLastError());
 }
 

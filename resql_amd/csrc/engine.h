@@ -321,8 +321,14 @@ void selectTopCandidatesRangePublish(Context& ctx, const int64_t* rows, int stri
 
 // devtail.hip: the tail of a large dense aggregation on the device (present groups, order by first row, the reference's hashes,
 // packed result tuples); tail.cpp planDenseDeviceTail says whether a plan qualifies and describes keys and columns
-struct DenseTailKey { int64_t min, card, stride; int32_t byteSet, typeTag; uint8_t values[32]; };
+// A dictionary-coded string key (len > 0; dense_groups.h DenseKey::coded): its rank is the row's code.  dict = the statement's copy of the
+// card x len entry bytes, terms = card 64-bit terms of Values::hash (dense_groups.h codedKeyHashTerms), both in device memory.
+struct DenseTailKey { int64_t min, card, stride; int32_t byteSet, typeTag; uint8_t values[32]; const uint8_t* dict; const uint64_t* terms; int32_t len, pad; };
 struct DenseTailKeys { int32_t n; DenseTailKey k[4]; };
+// groups of coded CHAR(n) keys whose entries are equal up to trailing spaces, merged in place in the [block][group] table:
+// classOf[k] = rank -> representative rank of key k (device memory; null: the key has no such entries), accumulator w in block accBlock[w]
+// with merge kind accKind[w] (0 wrapping sum, 2 min, 3 max; w = 0 is the first-row word)
+struct DenseFoldSpec { int32_t nKeys, nAcc; int64_t card[4], stride[4]; const uint32_t* classOf[4]; int32_t accBlock[32], accKind[32]; };
 struct DenseTailCol { int32_t kind, a, b, width, offset; };      // kind 0: group value of key a; 1: table block a; 2: AVG = block a * 100 / block b
 struct DenseTailCols { int32_t n; DenseTailCol c[24]; };
 void densePresentGroups(Context& ctx, const int64_t* firstBlock, int64_t D, uint32_t* flags /* [D + 1] */, uint64_t* offs /* [D + 1], offs[D] = count */,
@@ -330,8 +336,12 @@ void densePresentGroups(Context& ctx, const int64_t* firstBlock, int64_t D, uint
 size_t radixSortTempBytes(int64_t n);
 bool radixSortPairs(Context& ctx, uint64_t* keysA, uint32_t* valsA, uint64_t* keysB, uint32_t* valsB, int64_t n, int keyBits, void* temp, size_t tempBytes);
 void denseGroupHashes(Context& ctx, const uint32_t* gids, int64_t n, const DenseTailKeys& keys, uint64_t* hashes);
+// spell (null: every group spells itself): the group id whose dictionary entries a group's coded key columns show (denseFoldEqualGroups)
 void denseResultRows(Context& ctx, const uint64_t* table, int64_t D, const uint32_t* gids, const uint32_t* order, int64_t nRows, const DenseTailKeys& keys,
-                     const DenseTailCols& cols, int tupleSize, uint8_t* out);
+                     const DenseTailCols& cols, int tupleSize, const uint32_t* spell, uint8_t* out);
+// in front of densePresentGroups: every present group whose id changes under the class maps is merged into its representative's cells and
+// dropped (first-row word = INT64_MAX); spell[representative] = the member with the smallest first row, spell[g] = g for every other group
+void denseFoldEqualGroups(Context& ctx, uint64_t* table, int64_t D, const DenseFoldSpec& spec, uint32_t* spell /* [D] */);
 
 // ... and the same tail for the GROUP ROWS of a hash / join-entry aggregation ([first row | table words | accumulator blocks], as
 // compactEntries leaves them): order by first row, the reference's hashes from the group values, the replay, packed tuples.

@@ -15,6 +15,9 @@ namespace rsq {
 // reference's hash of every group -> [8 bytes per group to the host] -> host: slot order of the reference's table (the cluster-
 // parallel replay, hostref.cpp) -> [4 bytes per group back] -> device: packed result tuples in that order -> [the tuples to the
 // host].  rsq_config.emission_order = RSQ_EMIT_ANY skips everything between "present" and "tuples".
+// A dictionary-coded key (dense_groups.h DenseKey::coded): the statement's copy of its entries and the hash terms of the entries are
+// uploaded once, into the tail's arena; where two CHAR(n) entries are equal up to trailing spaces their groups are merged on the device
+// first (devtail.hip k_dense_fold / k_dense_spell), in place in q.dAgg, which every execution's start puts back to its identities.
 bool denseDeviceTailWanted(Query& q) {
     const bool off = getenv("RSQ_DEVICE_TAIL") && atoi(getenv("RSQ_DEVICE_TAIL")) == 0;      // (read per execution: tests switch it)
     const int64_t minGroups = getenv("RSQ_DEVICE_TAIL_MIN") ? atoll(getenv("RSQ_DEVICE_TAIL_MIN")) : 65536;
@@ -41,8 +44,16 @@ double runDenseDeviceTail(Query& q) {
         std::vector<std::pair<uint64_t, uint64_t>> lv;
         q.dtReplayBytes = replayLevels((uint64_t)D, opSize(q.agg), lv) ? replayDeviceBytes((uint64_t)D, lv.back().first) : 0;
         q.dtSortTempBytes = radixSortTempBytes(D);
+        // coded keys: per key [entries | hash terms | class map (only where entries are equal up to trailing spaces)], and the spelling array
+        q.dtFolds = false;
+        size_t codedBytes = 0;
+        for (auto& dk : q.denseKeys) if (dk.coded) {
+            codedBytes += up(dk.dict.size()) + up((size_t)dk.card * 8) + (dk.spaceEquivalent ? up((size_t)dk.card * 4) : 0);
+            q.dtFolds = q.dtFolds || dk.spaceEquivalent;
+        }
         const size_t sz[] = {up((size_t)(D + 1) * 4), up((size_t)(D + 1) * 8), up(scanTempBytes(D + 1)), up((size_t)D * 8), up((size_t)D * 8), up((size_t)D * 4), up((size_t)D * 4),
-                             up(q.dtSortTempBytes), up((size_t)D * 8), up((size_t)D * 4), up((size_t)D * (size_t)q.dtTupleSize)};
+                             up(q.dtSortTempBytes), up((size_t)D * 8), up((size_t)D * 4), up((size_t)D * (size_t)q.dtTupleSize),
+                             q.dtFolds ? up((size_t)D * 4) : 0, codedBytes};
         size_t devBytes = up(q.dtReplayBytes); for (size_t b : sz) devBytes += b;
         const size_t psz[] = {up((size_t)D * 8), up((size_t)D * 4), up(std::max<size_t>((size_t)D * (size_t)q.dtTupleSize, 8))};
         size_t pinBytes = 0; for (size_t b : psz) pinBytes += b;
@@ -57,9 +68,37 @@ double runDenseDeviceTail(Query& q) {
         q.dtFlags = (uint32_t*)take(); q.dtOffs = (uint64_t*)take(); q.dtScanTemp = take();
         q.dtFirst[0] = (uint64_t*)take(); q.dtFirst[1] = (uint64_t*)take(); q.dtGid[0] = (uint32_t*)take(); q.dtGid[1] = (uint32_t*)take();
         q.dtSortTemp = take(); q.dtHashes = (uint64_t*)take(); q.dtOrder = (uint32_t*)take(); q.dtRows = (uint8_t*)take();
+        q.dtSpell = q.dtFolds ? (uint32_t*)take() : (take(), nullptr);
+        char* coded = (char*)take();
         q.dtReplayWork = q.dtReplayBytes ? (void*)(d + at) : nullptr;
+        // (from DenseKey::dict, never from the table: a dictionary that changes refuses the statement - layoutVersion)
+        DenseFoldSpec& fs = q.dtFold;
+        fs = DenseFoldSpec{};
+        fs.nKeys = (int32_t)q.denseKeys.size(); fs.nAcc = (int32_t)q.accums.size();
+        for (size_t w = 0; w < q.accums.size() && w < 32; w++) { fs.accBlock[w] = q.accumSlot[w]; fs.accKind[w] = q.accums[w].merge; }
+        for (size_t k = 0; k < q.denseKeys.size(); k++) {
+            const DenseKey& dk = q.denseKeys[k];
+            fs.card[k] = dk.card; fs.stride[k] = dk.stride; fs.classOf[k] = nullptr;
+            if (!dk.coded) continue;
+            std::vector<uint64_t> terms;
+            codedKeyHashTerms(dk, terms);
+            RSQ_HIP(hipMemcpy(coded, dk.dict.data(), dk.dict.size(), hipMemcpyHostToDevice));
+            q.dtKeys.k[k].dict = (const uint8_t*)coded; coded += up(dk.dict.size());
+            RSQ_HIP(hipMemcpy(coded, terms.data(), terms.size() * 8, hipMemcpyHostToDevice));
+            q.dtKeys.k[k].terms = (const uint64_t*)coded; coded += up(terms.size() * 8);
+            if (!dk.spaceEquivalent) continue;
+            std::vector<uint32_t> cls;
+            codedKeyClasses(dk, cls);
+            RSQ_HIP(hipMemcpy(coded, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
+            fs.classOf[k] = (const uint32_t*)coded; coded += up(cls.size() * 4);
+        }
         char* h = (char*)q.dtArena.pinned;
         q.hDtHashes = (uint64_t*)h; q.hDtOrder = (uint32_t*)(h + psz[0]); q.resultPinned = (uint8_t*)(h + psz[0] + psz[1]);
+    }
+    if (q.dtFolds) {
+        denseFoldEqualGroups(ctx, q.dAgg, D, q.dtFold, q.dtSpell);
+        q.report.num_kernels += 2;
+        if (trace) { waitForStream(ctx); phase("pipelines done; groups equal up to trailing spaces merged"); }
     }
     densePresentGroups(ctx, (const int64_t*)(q.dAgg + (size_t)q.accumSlot[0] * (size_t)D), D, q.dtFlags, q.dtOffs, q.dtScanTemp, q.dtFirst[0], q.dtGid[0]);
     uint64_t nPresent = 0;
@@ -106,7 +145,7 @@ double runDenseDeviceTail(Query& q) {
         dOrder = q.dtOrder;
         }
     }
-    denseResultRows(ctx, q.dAgg, D, dGids, dOrder, emit, q.dtKeys, q.dtCols, q.dtTupleSize, q.dtRows);
+    denseResultRows(ctx, q.dAgg, D, dGids, dOrder, emit, q.dtKeys, q.dtCols, q.dtTupleSize, q.dtSpell, q.dtRows);
     if (emit > 0) RSQ_HIP(hipMemcpyAsync(q.resultPinned, q.dtRows, (size_t)emit * (size_t)q.dtTupleSize, hipMemcpyDeviceToHost, ctx.stream));
     RSQ_HIP(hipMemcpyAsync(q.hPinned + q.pinnedWords, ctx.dErr, 4, hipMemcpyDeviceToHost, ctx.stream));
     waitForStream(ctx);

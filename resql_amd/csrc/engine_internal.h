@@ -428,6 +428,7 @@ struct Query {
     void* dtSortTemp = nullptr; size_t dtSortTempBytes = 0;
     uint64_t* dtHashes = nullptr; uint32_t* dtOrder = nullptr; uint8_t* dtRows = nullptr;
     void* dtReplayWork = nullptr; size_t dtReplayBytes = 0;           // work area of the replay on the device (0: host replay)
+    bool dtFolds = false; DenseFoldSpec dtFold{}; uint32_t* dtSpell = nullptr;      // a coded CHAR(n) key with entries equal up to trailing spaces (devtail.hip k_dense_fold)
     uint64_t* hDtHashes = nullptr; uint32_t* hDtOrder = nullptr;      // pinned
     uint8_t* resultPinned = nullptr;       // pinned copy of the result tuples (device tail)
     const uint8_t* resultDev = nullptr;    // ... and the device buffer they were written to (null: the host tail made the tuples)

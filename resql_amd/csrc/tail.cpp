@@ -654,30 +654,43 @@ static TailShape buildTailShape(Query& q) {
 }
 
 // Can the rows of this dense aggregation be produced on the device (devtail.hip)?  Yes when every output column is a group
-// value, an accumulator or an AVG (no computed projection, no strings) and nothing sorts the rows afterwards.  Fills the column
-// and key descriptions the kernels take.
+// value, an accumulator or an AVG (no computed projection; a string only as the value of a dictionary-coded key) and nothing
+// sorts the rows afterwards.  Fills the column and key descriptions the kernels take; a coded key's device pointers (dictionary copy, hash
+// terms) are set where the tail's buffers are made (engine_devtail.cpp).
 bool planDenseDeviceTail(Query& q, DenseTailKeys& keys, DenseTailCols& cols, int& tupleSize, int64_t& limitRows) {
     if (!q.agg || q.denseKeys.empty() || q.denseKeys.size() > 4) return false;
-    // a dictionary-coded key: declined, the host tail runs (groupsFromDense decodes the rank into the entry's bytes; the device tail's keys
-    // are integers - DenseTailKey - and it neither knows the dictionary nor merges space-equivalent CHAR groups)
-    if (anyCodedKey(q.denseKeys)) return false;
     TailShape sh = buildTailShape(q);
-    if (!sh.directRows || sh.orderBy || sh.cur.size() > 24) return false;
+    if (sh.orderBy || sh.cur.size() > 24) return false;
     keys.n = (int32_t)q.denseKeys.size();
+    bool folds = false;
     for (size_t k = 0; k < q.denseKeys.size(); k++) {
         const DenseKey& dk = q.denseKeys[k];
         DenseTailKey& o = keys.k[k];
         o.min = dk.min; o.card = dk.card; o.stride = dk.stride; o.byteSet = dk.byteSet ? 1 : 0; o.typeTag = dk.type.tag;
-        if (dk.type.isString()) return false;
+        o.dict = nullptr; o.terms = nullptr; o.len = 0; o.pad = 0;
+        if (dk.type.isString() && !dk.coded) return false;      // (a string key that is not coded is not dense in the first place)
+        if (dk.coded) {
+            if (dk.type.len <= 0 || dk.dict.size() != (size_t)dk.card * (size_t)dk.type.len) return false;
+            o.len = dk.type.len;
+            folds = folds || dk.spaceEquivalent;
+        }
         if (dk.byteSet) { if (dk.values.size() > sizeof o.values) return false; memset(o.values, 0, sizeof o.values); memcpy(o.values, dk.values.data(), dk.values.size()); }
     }
+    if (folds && q.accums.size() > 32) return false;      // (DenseFoldSpec names 32 accumulator blocks)
     cols.n = (int32_t)sh.cur.size();
     for (size_t c = 0; c < sh.cur.size(); c++) {
         const Src& s = sh.colSrc[c];
         DenseTailCol& o = cols.c[c];
+        if (s.kind == 3) return false;                                    // a computed projection: the host's expression interpreter
         o.kind = s.kind; o.offset = sh.offs[c]; o.width = sizeInTuple(sh.cur[c].type, true);
         if (s.kind == 0) { o.a = s.a; o.b = 0; }
         else { o.a = q.accumSlot[(size_t)s.a]; o.b = s.kind == 2 ? q.accumSlot[(size_t)s.b] : 0; }      // accumulator index -> block of the [block][group] table
+        if (sh.cur[c].type.isString()) {
+            // a string: the entry of a coded key by value, len bytes and a NUL
+            if (s.kind != 0 || s.a < 0 || (size_t)s.a >= q.denseKeys.size() || keys.k[s.a].len <= 0 || o.width != keys.k[s.a].len + 1) return false;
+            continue;
+        }
+        if (s.kind == 0 && (s.a < 0 || (size_t)s.a >= q.denseKeys.size() || keys.k[s.a].len > 0)) return false;
         if (o.width != 8 && o.width != 4 && o.width != 2 && o.width != 1) return false;      // (CHAR(1) takes two bytes of a tuple: the character and a NUL)
     }
     tupleSize = (int)sh.ts;

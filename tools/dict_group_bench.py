@@ -7,7 +7,13 @@ and `select l_shipmode, sum(l_quantity), count(*) from lineitem group by l_shipm
 between them, so that clocks and neighbours change under both alike.  A run is `repeat` executions of each statement; per build and
 statement the file gets every run's median and the median, minimum and maximum over the runs' medians (whole execution and kernels),
 the aggregation's explain step, and whether both builds gave one answer.  One JSON line per figure, stamped with --sha.  --also adds a
-third worker: this tree again with one more environment switch (RSQ_AGG_MODE=1: the register form also behind Q12's compaction)."""
+third worker: this tree again with one more environment switch (RSQ_AGG_MODE=1: the register form also behind Q12's compaction).
+
+usage: python tools/dict_group_bench.py [SF] --tail [--runs N] [--repeat N] [--out FILE] [--sha SHA]
+The device tail of a dense aggregation with a coded key against its host tail (RSQ_DEVICE_TAIL=0, which is the parent commit's tail
+for such a statement): `group by l_shipmode, l_suppkey`, one process, one compiled statement, the switch read at every execution and
+the runs alternating.  Per run and over the runs: whole execution, kernels and tail (rsq_report.finalize_time_ms), as
+tools/hash_tail_bench.py prints them."""
 import json
 import os
 import statistics
@@ -67,6 +73,50 @@ def worker(tree, sf, repeat, also=""):
     ctx.close()
 
 
+TAIL_SQL = "select l_shipmode, l_suppkey, count(*), sum(l_quantity) from lineitem group by l_shipmode, l_suppkey"
+
+
+def tail_rows(sf, runs, repeat, emit):
+    """device tail against RSQ_DEVICE_TAIL=0 over one compiled statement"""
+    sys.path.insert(0, HERE)
+    os.environ["RSQ_DICT_SCANS"] = "1"
+    from resql_amd import engine, tpch_full
+    ctx = engine.Context(device=0)
+    tab = ctx.table(tpch_full.lineitem(sf))
+    q = ctx.sql_compile(TAIL_SQL, [tab])
+    q.await_kernels()
+    answers, series = {}, {"device": [], "host": []}
+    try:
+        for run in range(runs + 1):                                           # (run 0 warms both tails and keeps their answers)
+            for tail in (("device", "host") if run % 2 else ("host", "device")):
+                os.environ["RSQ_DEVICE_TAIL"] = "1" if tail == "device" else "0"
+                ex, ke, fi = [], [], []
+                for _ in range(repeat if run else 3):
+                    q.execute()
+                    r = q.report()
+                    ex.append(r.execution_time_ms)
+                    fi.append(r.finalize_time_ms)
+                    if r.kernel_time_ms > 0:
+                        ke.append(r.kernel_time_ms)
+                if not run:
+                    answers[tail] = q.result().text
+                    continue
+                v = {"exec_ms_median": statistics.median(ex), "kernel_ms_median": statistics.median(ke) if ke else None, "tail_ms_median": statistics.median(fi)}
+                series[tail].append(v)
+                emit(dict(v, statement=TAIL_SQL, tail=tail, run=run))
+        agg = [s for l in q.explain.splitlines() if l.startswith("pipeline") for s in l.split(" -> ") if "aggregation" in s]
+        emit({"statement": TAIL_SQL, "sf": sf, "RSQ_DICT_SCANS": "1", "same_answer": answers["device"] == answers["host"], "aggregation": agg})
+        for tail, vs in series.items():
+            cols = {k: [v[k + "_ms_median"] for v in vs if v[k + "_ms_median"] is not None] for k in ("exec", "kernel", "tail")}
+            emit(dict({"summary": "group_by_shipmode_suppkey", "tail": tail, "runs": runs, "executions_per_run": repeat},
+                      **{k + "_ms": {"median": round(statistics.median(c), 4), "min": round(min(c), 4), "max": round(max(c), 4)} if c else None for k, c in cols.items()}))
+    finally:
+        os.environ.pop("RSQ_DEVICE_TAIL", None)
+        q.close()
+        tab.close()
+        ctx.close()
+
+
 def main():
     sf = float(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else 10.0
     runs, repeat, out_path, sha = arg("--runs", 7), arg("--repeat", 30), arg("--out", ""), arg("--sha", "")
@@ -83,6 +133,12 @@ def main():
         if out:
             out.write(line + "\n")
             out.flush()
+
+    if "--tail" in sys.argv:
+        tail_rows(sf, runs, repeat, emit)
+        if sha:
+            emit({"head_sha": sha})
+        return
 
     procs = {b: subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", t, str(sf), str(repeat), also[b]], stdin=subprocess.PIPE,
                                  stdout=subprocess.PIPE, text=True) for b, t in trees.items()}
