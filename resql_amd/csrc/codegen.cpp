@@ -147,7 +147,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     colTypes.clear(); colIsString.clear(); colNarrow.clear(); colDict.clear(); nDictTables = 0; rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
     body.clear(); stateDecl.clear(); stateInit.clear(); prologue.clear(); epilogue.clear(); fileScope.clear(); helperFns.clear();
     explainSteps.clear(); indent = 1; matchSlotTable = -1; slotVar.clear(); symbolOrigin.clear(); symbolWord.clear();
-    multiMatchAbove = false;
+    multiMatchAbove = false; repeatedKeysAbove.clear(); denseRefusal.clear();
     selective = false; compacted = false; stage2Body.clear(); cqLive.clear();
     leadCond.clear(); leadCols.clear(); leadPass = 1.0; leadPassComplete = true;
     pairSplit = std::string::npos; pairCond.clear();

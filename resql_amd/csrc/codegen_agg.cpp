@@ -45,20 +45,70 @@ void Walker::collectAccumulators(OpNode* o) {
     q.nSumBlocks = (int64_t)q.accums.size() - q.nMinBlocks - q.nMaxBlocks;
 }
 
+// two entries of a CHAR(n) column's dictionary are equal up to trailing spaces: one group to the reference (tail.cpp mergeEqualGroups)
+static bool dictSpaceEquivalent(const TableColumn& c) {
+    if (c.type.tag != RSQ_CHAR) return false;
+    std::set<std::string> seen;
+    const size_t w = (size_t)c.type.len;
+    for (int e = 0; e < c.dictN; e++) {
+        const char* v = (const char*)c.dict.data() + (size_t)e * w;
+        size_t n = strnlen(v, w);
+        while (n > 0 && v[n - 1] == ' ') n--;
+        if (!seen.insert(std::string(v, n)).second) return true;
+    }
+    return false;
+}
+
 // Dense group ids: every group-by value is a column of this pipeline's scan whose domain is known and small - a numeric column by its
 // statistics' [min, max] (rank = value - min), a one-byte column by its sorted distinct values (rank = position in the set), a
 // dictionary-coded string column (RSQ_DICT_SCANS=1, codegen.cpp colDict) by its dictionary (rank = the row's code, card = the entry
 // count).  The group id is the mixed-radix number of the ranks, at most 2^24 groups.  card and the strides go into the kernel text; a
 // dictionary's values and address do not.  The statement keeps the dictionary's bytes for its tail (DenseKey::dict): a dictionary that
 // changes is rebuilt, which bumps the table's layoutVersion and refuses the statements compiled before (executeQuery).
+// RSQ_DICT_SCANS=2 adds one kind of key that is NOT a column of the scan: a string that a join's build side carries by address, where that
+// address points into a dictionary image (rank = (address - dictionary) / width; see the key's own note below).
 bool Walker::tryDenseKeys(OpNode* o) {
     Table* t = pipe.src;
     q.denseKeys.clear();
-    auto no = [&] { q.denseKeys.clear(); return false; };      // (a statement that is not dense holds no dense keys)
+    denseRefusal.clear();
+    // (a statement that is not dense holds no dense keys; why: said in explain under RSQ_DICT_SCANS=2, where a string key was the obstacle)
+    auto no = [&](const std::string& why = std::string()) { q.denseKeys.clear(); if (dictJoinKeysEnabled()) denseRefusal = why; return false; };
     int64_t total = 1;
     for (Expr* g : o->exprs2) {
-        if (g->tag != RSQ_E_ATTRIBUTE) return no();
+        if (g->tag != RSQ_E_ATTRIBUTE) return no(g->type.isString() ? "key " + expressionName(g) + " not by dictionary code: a computed value" : std::string());
         auto org = symbolOrigin.find(g->symbol);
+        if (g->type.isString() && org != symbolOrigin.end() && org->second < -1) return no("key " + g->symbol + " not by dictionary code: a computed value");
+        if (g->type.isString() && org != symbolOrigin.end() && org->second == -1 && t->derived) return no("key " + g->symbol + " not by dictionary code: a derived table holds it by value");
+        if (org != symbolOrigin.end() && org->second >= 0 && g->type.isString() && dictJoinKeysEnabled()) {
+            // A string from a join's build side (RSQ_DICT_SCANS=2): dense by the dictionary its address points into (HashTable::DictOrigin),
+            // where it has one - under the conditions of a scan-own coded key below, for this scan's table and the origin's alike.  The
+            // origin table must be one of the statement's, so that a rebuilt dictionary refuses it (executeQuery).
+            // The first row of a group is the SCAN's row.  A probe for all matches may hand one row several entries, whose groups then
+            // share their first row: the hash form emits such groups in the order of their slots, a dense table in the order of their
+            // ranks, the reference in the order of its chain.  Where the statistics say that a probed table's keys repeat
+            // (HashTable::dupKeysKnown) the statement keeps the form it had; where they cannot tell - the planner calls every join over
+            // a key that is not one of five TPC-H primary keys a join for all matches, TPC-H Q5's probe of the supplier table among
+            // them - unique build keys give one entry per row and nothing ties.  Not under a nested-loops join: every pair is a row there.
+            const HashTable& from = *q.hashTables[(size_t)org->second];
+            auto sw = symbolWord.find(g->symbol);
+            const HashTable::DictOrigin* og = sw != symbolWord.end() && sw->second >= (int)from.keys.size() ? from.originOf((size_t)sw->second - from.keys.size()) : nullptr;
+            const std::string key = "key " + g->symbol + " not by dictionary code: ";
+            if (!og) return no(key + "its bytes do not stand in a dictionary image");
+            if (!repeatedKeysAbove.empty()) return no(key + "the build keys of " + repeatedKeysAbove + " repeat, and a row with several matches has no first group");
+            if (underNestedLoops()) return no(key + "under a nested-loops join");
+            if (q.ctx.shardCompile) return no(key + "the statement runs on several shards");
+            if (t->nRowsTotal >= 0 || og->table->nRowsTotal >= 0) return no(key + (t->nRowsTotal >= 0 ? t->name : og->table->name) + " is a shard of a larger table");
+            if (std::find(q.tables.begin(), q.tables.end(), og->table) == q.tables.end()) return no(key + og->table->name + " is not a table of this statement");
+            const TableColumn& c = og->table->cols[(size_t)og->col];
+            if (c.dictN <= 0 || c.type.len != og->len || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no(key + "its bytes do not stand in a dictionary image");
+            DenseKey k; k.expr = g; k.type = c.type;
+            k.coded = true; k.scanCol = -1; k.originTable = og->table; k.originCol = og->col; k.card = c.dictN; k.dict = c.dict;
+            k.spaceEquivalent = dictSpaceEquivalent(c);
+            if (total > (int64_t)(1 << 24) / k.card) return no(key + "more than 2^24 groups");
+            total *= k.card;
+            q.denseKeys.push_back(k);
+            continue;
+        }
         if (org == symbolOrigin.end() || org->second != -1) return no();      // not a column of this pipeline's scan
         int ci = t->findCol(g->symbol);
         if (ci < 0 || !t->cols[(size_t)ci].dptr) return no();
@@ -73,16 +123,7 @@ bool Walker::tryDenseKeys(OpNode* o) {
             for (size_t p = 0; p < pipe.cols.size(); p++) if (pipe.cols[p] == ci) sc = (int)p;
             if (!coded(sc) || t->nRowsTotal >= 0 || q.ctx.shardCompile || c.dictN <= 0 || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no();
             k.coded = true; k.scanCol = sc; k.card = c.dictN; k.dict = c.dict;
-            if (c.type.tag == RSQ_CHAR) {
-                std::set<std::string> seen;
-                const size_t w = (size_t)c.type.len;
-                for (int e = 0; e < c.dictN; e++) {
-                    const char* v = (const char*)k.dict.data() + (size_t)e * w;
-                    size_t n = strnlen(v, w);
-                    while (n > 0 && v[n - 1] == ' ') n--;
-                    if (!seen.insert(std::string(v, n)).second) k.spaceEquivalent = true;
-                }
-            }
+            k.spaceEquivalent = dictSpaceEquivalent(c);
             if (total > (int64_t)(1 << 24) / k.card) return no();
             total *= k.card;
             q.denseKeys.push_back(k);
@@ -140,6 +181,8 @@ void Walker::consumeAggregation(OpNode* o, OpNode* from) {
     const int W = (int)q.accums.size();
     std::string mode;
     const int forced = envInt("RSQ_AGG_MODE", 0, 0, 5);     // 5 = generic hash aggregation even where a dense id exists (tests)
+    denseRefusal.clear();
+    if (forced == 5 && dictJoinKeysEnabled()) for (Expr* g : o->exprs2) if (g->type.isString()) denseRefusal = "no dense ids: RSQ_AGG_MODE=5";
     if (!(forced == 5 && !o->exprs2.empty()) && tryDenseKeys(o)) {
         const int64_t D = q.denseGroups, cells = D * W;
         // measured on MI355X (Q1 SF10, 42 cells): registers 0.47 ms, lane-private LDS 0.71 ms
@@ -572,7 +615,8 @@ void Walker::emitHashAggregation(OpNode* o) {
     q.aggTable = ht->id;
     explainSteps.push_back("hash aggregation in " + T + " (" + std::to_string(ht->keys.size()) + " key word(s)" +
                            (anyCarried ? " + " + std::to_string(ht->payload.size()) + " carried word(s) of group values that depend on them" : "") + (lds ? ", LDS front table" : "") +
-                           ") accumulators=" + std::to_string(W - 1) + " (of " + std::to_string(o->splitAgg.size()) + " in the reference)");
+                           ") accumulators=" + std::to_string(W - 1) + " (of " + std::to_string(o->splitAgg.size()) + " in the reference)" +
+                           (denseRefusal.empty() ? std::string() : ", " + denseRefusal));
     q.hashTables.push_back(std::move(ht));
 }
 
@@ -585,6 +629,22 @@ std::string Walker::groupIdExpr() {
     for (size_t ki = 0; ki < q.denseKeys.size(); ki++) {
         DenseKey& k = q.denseKeys[ki];
         const std::string rv = "gk" + std::to_string(ki);
+        if (k.coded && k.scanCol < 0) {
+            // a string carried from a join's build side: its address points into the origin column's dictionary image in both forms of the
+            // table (codegen_join.cpp consumeMatch), so the rank is a subtract and a divide by the width - no load.  The dictionary's
+            // address is an argument, bound when the statement is compiled like a.d<k>; the text holds the width and card.  The rank
+            // indexes the aggregation's table, so it is always checked: one at or above card is counted into group 0 and fails the
+            // execution, like a key outside its statistics.  Behind a wave compaction the address travels under the symbol's name.
+            const std::string an = "gd" + std::to_string(ki);
+            addArg(an, "const char*", (uint64_t)(uintptr_t)k.originTable->cols[(size_t)k.originCol].dictPtr);
+            if (helperFns.find("dict_rank(") == std::string::npos)
+                helperFns += "template <int W> static RSQ_DEV u64 dict_rank(const rsq::Str v, const char* dict) { return (u64)(v.p - dict) / (u64)W; }\n";
+            line("int " + rv + " = 0;");
+            line("{ const u64 r = dict_rank<" + std::to_string(k.type.len) + ">(" + eg.emit(k.expr) + ", a." + an + "); if (r < " + std::to_string((long long)k.card) +
+                 "ull) " + rv + " = (int)r; else atomicOr(a.err, (u32)rsq::ERR_GROUP_OVERFLOW); }");
+            gid += " + " + rv + " * " + std::to_string((long long)k.stride);
+            continue;
+        }
         if (k.coded) {
             // the rank IS the code the scan loaded: no decode, no dictionary access.  Behind a wave compaction the code travels in the
             // queue (codegen.cpp compactThen), not the rsq::Str it would decode to.
@@ -1107,7 +1167,9 @@ void Walker::emitDenseAggregation(OpNode* o) {
     static const char* names[] = {"none", "registers", "lane-private LDS", "workgroup LDS table", "HBM table", "join entry", "hash"};
     std::string codedNote;      // (nothing without a dictionary-coded key: the text of every other statement stays what it was)
     for (auto& k : q.denseKeys)
-        if (k.coded) codedNote += ", key " + k.expr->symbol + " by dictionary code (" + std::to_string((long long)k.card) + (k.card == 1 ? " entry)" : " entries)");
+        if (k.coded) codedNote += ", key " + k.expr->symbol + " by dictionary code" +
+                                  (k.originTable ? " of " + k.originTable->name + "." + k.originTable->cols[(size_t)k.originCol].name : std::string()) +
+                                  " (" + std::to_string((long long)k.card) + (k.card == 1 ? " entry)" : " entries)");
     explainSteps.push_back("aggregation dense groups=" + std::to_string((long long)D) + " accumulators=" + std::to_string(W - 1) +
                            " (of " + std::to_string(o->splitAgg.size()) + " in the reference) in " + names[(int)q.aggMode] +
                            (pipe.partitioned ? " (atomics, or " + std::to_string(pipe.partCount) + " partitions x " + std::to_string(pipe.partGroups) +

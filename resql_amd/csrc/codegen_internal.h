@@ -309,6 +309,8 @@ struct Walker {
     std::map<std::string, int> symbolOrigin;   // symbol -> hash table id it was read from (or -1: scan column)
     std::map<std::string, int> symbolWord;     // symbol -> word index in that table
     bool multiMatchAbove = false;
+    std::string repeatedKeysAbove;             // a probe for all matches above whose table's build keys repeat for certain (HashTable::dupKeysKnown): which
+    std::string denseRefusal;                  // RSQ_DICT_SCANS=2: why a string group key did not become a dense id (tryDenseKeys), for explain
     bool underNestedLoops() const { return !q.nljs.empty(); }      // the plan pairs rows in a nested-loops join
     // wave-level compaction (see compactThen)
     bool selective = false, compacted = false;
@@ -393,6 +395,12 @@ struct Walker {
     static std::string wordAt(const HashTable& ht, const std::string& T, int w);
 
     std::string slotOf(const HashTable& ht, const std::string& T, const std::vector<std::string>& keyVars);
+
+    // RSQ_DICT_SCANS=2: where a build-side string's bytes stand, if that is a dictionary image (HashTable::DictOrigin) - a coded column of
+    // this pipeline's scan, or a payload of an earlier table that has an origin itself.  Only for a name some aggregation of the statement
+    // groups by: every other statement keeps the text it has under RSQ_DICT_SCANS=1.
+    bool isGroupKey(const std::string& name) const;
+    HashTable::DictOrigin payloadOriginOf(const std::string& name) const;
 
     void consumeBuild(OpNode* o, OpNode* from);
     void consumeBuildBody(OpNode* o, OpNode* from);

@@ -121,6 +121,36 @@ std::string Walker::slotOf(const HashTable& ht, const std::string& T, const std:
     return hashOf(keyVars) + " & " + T + "_mask";
 }
 
+bool Walker::isGroupKey(const std::string& name) const {
+    for (auto& o : q.ops)
+        if (o->tag == RSQ_OP_AGGREGATION)
+            for (Expr* g : o->exprs2) if (g->tag == RSQ_E_ATTRIBUTE && g->symbol == name) return true;
+    return false;
+}
+
+HashTable::DictOrigin Walker::payloadOriginOf(const std::string& name) const {
+    const HashTable::DictOrigin none;
+    if (!dictJoinKeysEnabled() || !isGroupKey(name)) return none;
+    auto org = symbolOrigin.find(name);
+    if (org == symbolOrigin.end()) return none;
+    if (org->second == -1) {
+        // a bare column of this scan, read from its dictionary image: v_<k> is rsq::str(a.d<k> + code * n, n), and that address is stored
+        const int ci = pipe.src->findCol(name);
+        int sc = -1;
+        for (size_t p = 0; p < pipe.cols.size(); p++) if (pipe.cols[p] == ci) sc = (int)p;
+        if (ci < 0 || !coded(sc)) return none;
+        HashTable::DictOrigin o; o.table = pipe.src; o.col = ci; o.len = pipe.src->cols[(size_t)ci].type.len;
+        return o;
+    }
+    if (org->second < 0) return none;      // (computed in this pipeline, or a nested-loops join's column: by value)
+    // a payload of an earlier table: the address it handed out is stored again as it is
+    const HashTable& from = *q.hashTables[(size_t)org->second];
+    auto w = symbolWord.find(name);
+    if (w == symbolWord.end() || w->second < (int)from.keys.size()) return none;
+    const HashTable::DictOrigin* o = from.originOf((size_t)w->second - from.keys.size());
+    return o ? *o : none;
+}
+
 void Walker::consumeBuild(OpNode* o, OpNode* from) {
     if (compactThen(o, [&] { consumeBuildBody(o, from); })) return;
     consumeBuildBody(o, from);
@@ -158,7 +188,7 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
             if (l->tag == RSQ_E_ATTRIBUTE && l->symbol == a.name && !l->type.isString() && keyFirstWord[ki] >= 0) alias = keyFirstWord[ki];
         }
         if (alias >= 0) ht->keyAlias.push_back({{a.name, it->second.type}, alias});
-        else ht->payload.push_back({a.name, it->second.type});
+        else { ht->payload.push_back({a.name, it->second.type}); ht->payloadOrigin.push_back(payloadOriginOf(a.name)); }
     }
     // key-domain bitmap (see HashTable): one integer key that is a column of this pipeline's scan with usable statistics
     if (o->exprs.size() == 1 && keyVars.size() == 1 && envInt("RSQ_JOIN_BITMAP", 1, 0, 1)) {
@@ -223,6 +253,16 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
         ht->identityCapable = ht->rankCapable && !ht->setOnly && from->tag == RSQ_OP_SCAN && ci >= 0 && pipe.src->cols[(size_t)ci].owned &&
                               pipe.src->cols[(size_t)ci].stats.valid && pipe.src->cols[(size_t)ci].stats.ascending;
         ht->uniqueKnown = ht->identityCapable && pipe.src->cols[(size_t)ci].stats.strictlyAscending && pipe.src->nRows < 0xffffffffll;
+    }
+    // ... or that they repeat: a bare scan whose one integer key column is sorted with equal neighbours, or holds more rows than its range has
+    // values.  A probe for all matches of such a table hands one row several entries (codegen_agg.cpp tryDenseKeys).
+    if (o->exprs.size() == 1 && from->tag == RSQ_OP_SCAN && o->exprs[0]->child->tag == RSQ_E_ATTRIBUTE && !o->exprs[0]->child->type.isString()) {
+        const int ci = pipe.src->findCol(o->exprs[0]->child->symbol);
+        if (ci >= 0 && pipe.src->cols[(size_t)ci].stats.valid && pipe.src->nRows > 1) {
+            const ColumnStats& st = pipe.src->cols[(size_t)ci].stats;
+            const unsigned __int128 range = (unsigned __int128)((__int128)st.max - (__int128)st.min) + 1;
+            ht->dupKeysKnown = (st.ascending && !st.strictlyAscending) || (unsigned __int128)pipe.src->nRows > range;
+        }
     }
     // DIRECT (HashTable::directCapable): every payload value is a column of this scan - it is, over a bare scan - and the statistics promise
     // unique keys: if the keys also fill their range (known when the form is decided), the probes read the table's columns themselves
@@ -545,7 +585,13 @@ void Walker::consumeMatch(OpNode* o, HashTable& ht, const std::string& T, const 
             // (the direct form: the value of the build table's column at row T_s - a string's address is base + T_s * width, no load at all)
             const std::string src = "a." + T + "_src" + std::to_string(w);
             addArg(T + "_direct", "u64", 0); addArg(T + "_src" + std::to_string(w), "const char*", 0);
-            const std::string direct = p.type.isString() ? "(i64)(u64)(" + src + " + " + T + "_s * " + std::to_string(p.type.len) + "ull)"
+            // (a payload with a dictionary origin: the row's code and the dictionary instead of the wide column, so that both forms of the
+            // table hand out an address inside the image - the same bytes, and the group id's rank: codegen_agg.cpp groupIdExpr)
+            const bool viaDict = p.type.isString() && ht.originOf((size_t)(w - (int)ht.keys.size())) != nullptr;
+            const std::string codes = "a." + T + "_code" + std::to_string(w), dict = "a." + T + "_dict" + std::to_string(w);
+            if (viaDict) { addArg(T + "_code" + std::to_string(w), "const u8*", 0); addArg(T + "_dict" + std::to_string(w), "const char*", 0); }
+            const std::string direct = viaDict ? "(i64)(u64)(" + dict + " + (u32)" + codes + "[" + T + "_s] * " + std::to_string(p.type.len) + "u)" :
+                                       p.type.isString() ? "(i64)(u64)(" + src + " + " + T + "_s * " + std::to_string(p.type.len) + "ull)"
                                                          : "(i64)(reinterpret_cast<const " + ExprGen::ctype(p.type) + "*>(" + src + ")[" + T + "_s])";
             line("const i64 " + T + "_w" + std::to_string(w) + " = a." + T + "_direct ? " + direct + " : " + word + ";");
             word = T + "_w" + std::to_string(w);
@@ -567,8 +613,9 @@ void Walker::consumeMatch(OpNode* o, HashTable& ht, const std::string& T, const 
     for (size_t i = 0; i < probeKeyNames.size(); i++)
         if (!probeKeyNames[i].empty() && symbolOrigin.count(probeKeyNames[i]) && symbolOrigin[probeKeyNames[i]] == -1) probeKeyOf[probeKeyNames[i]] = {ht.id, (int)i};
     int prevMatch = matchSlotTable; bool prevMulti = multiMatchAbove;
+    const std::string prevRepeated = repeatedKeysAbove;
     slotVar[ht.id] = T + "_s";
-    if (o->singleMatch) matchSlotTable = ht.id; else { multiMatchAbove = true; }
+    if (o->singleMatch) matchSlotTable = ht.id; else { multiMatchAbove = true; if (ht.dupKeysKnown) repeatedKeysAbove = T; }
     explainSteps.push_back(std::string("probe ") + T + (o->singleMatch ? " (single match)" : " (all matches)"));
     selective = true;                       // whatever follows a join probe sees only the matching rows
     {
@@ -578,7 +625,7 @@ void Walker::consumeMatch(OpNode* o, HashTable& ht, const std::string& T, const 
     }
     consume(o->parent, o);
     probesInScope.pop_back();
-    matchSlotTable = prevMatch; multiMatchAbove = prevMulti;
+    matchSlotTable = prevMatch; multiMatchAbove = prevMulti; repeatedKeysAbove = prevRepeated;
 }
 
 void Walker::probeTable(OpNode* o, HashTable& ht, const std::string& T, const std::vector<std::string>& keyVars,

@@ -15,6 +15,8 @@
 
 namespace rsq {
 
+struct Table;
+
 struct DenseKey {
     Expr* expr = nullptr;
     Type type;
@@ -26,8 +28,13 @@ struct DenseKey {
     // coded: a dictionary-coded string column of the pipeline's scan (engine.h TableColumn::dict) - the rank is the row's u8 code, card
     // the dictionary's entry count.  `dict` is the statement's own copy of the card x width entry bytes, for its tail; scanCol is the
     // column's place among the pipeline's scanned columns (the code is the row-function parameter vc_<scanCol>).
+    // ... or, with scanCol -1, a string carried from a join's build side whose address points into the dictionary of column originCol of
+    // originTable (engine_internal.h HashTable::DictOrigin): the rank is (address - dictionary) / width, card and dict are that column's.
+    // The tails read card, dict and type alone and do not tell the two apart.
     bool coded = false;
     int scanCol = -1;
+    const Table* originTable = nullptr;
+    int originCol = -1;
     std::vector<uint8_t> dict;
     bool spaceEquivalent = false;    // coded CHAR(n): two entries are equal up to trailing spaces - one group to the reference (tail.cpp mergeEqualGroups)
 };

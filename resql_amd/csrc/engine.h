@@ -76,6 +76,10 @@ inline bool narrowScansEnabled() { const char* e = getenv("RSQ_NARROW_SCANS"); r
 // kernels and their text are what they are without the images.  Off by default until the SF10 comparison (tools/dict_scan_bench.py) is on
 // record in docs/KERNELS.md.  RSQ_NARROW_SCANS=0 turns them off as well.
 inline bool dictScansEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return narrowScansEnabled() && e && atoi(e) != 0; }
+// RSQ_DICT_SCANS=2: everything 1 means, and a string that reaches an aggregation as a join's build-side payload is a dense group key by
+// the dictionary of the column it came from (codegen_join.cpp payloadOrigin, codegen_agg.cpp tryDenseKeys).  Read where a statement is
+// compiled; under 0 and 1 no text, explain line or cache key knows of it.
+inline bool dictJoinKeysEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return dictScansEnabled() && atoi(e) >= 2; }
 // RSQ_MAX_GRID=n (1..65535): the tile loops of a statement compiled under it launch at most n 256-thread workgroups' worth of threads
 // (Pipeline::maxGrid: n * 256 / block size workgroups, at least one); unset, 0 or out of range: the grid the pipeline asks for.  Read ONCE per statement, when it is compiled
 // (compileQuery): buffers sized from the grid then (engine_pipelines.cpp sizeJoinTable) fit every later launch.  A launch parameter only -

@@ -47,6 +47,14 @@ struct HashTable {
     int id = 0;
     std::vector<Attr> keys;          // build-side key values (names of the build key expressions)
     std::vector<Attr> payload;       // build-side attributes carried to the probe side
+    // Dictionary origin of a string payload (RSQ_DICT_SCANS=2, codegen_join.cpp): the address the payload word holds points into the
+    // dictionary image of column `col` of `table` (entries `len` bytes apart) in BOTH forms of the table, so its rank there is
+    // (address - dictionary) / len.  One per payload entry when any is set (table null: none); carried from table to table with the value.
+    struct DictOrigin { const Table* table = nullptr; int col = -1; int len = 0; };
+    std::vector<DictOrigin> payloadOrigin;
+    const DictOrigin* originOf(size_t payloadIndex) const {
+        return payloadIndex < payloadOrigin.size() && payloadOrigin[payloadIndex].table ? &payloadOrigin[payloadIndex] : nullptr;
+    }
     std::vector<std::pair<Attr, int>> keyAlias;   // build-side attributes that ARE a key value: (attribute, key word) — not stored twice
     int64_t capacity = 0;
     bool unique = false;             // probed single-match
@@ -82,6 +90,7 @@ struct HashTable {
     uint32_t* dCompBitmap = nullptr;
     bool identityCapable = false;    // rank dictionary over a bare scan in key order: entry number == row number when every row is inserted (codegen.cpp consumeBuild)
     bool uniqueKnown = false;        // ... and the column statistics say its values are unique (strictly ascending): every row is inserted under its own key, no sizing pass
+    bool dupKeysKnown = false;       // the opposite: the statistics of its one key column say that some value repeats (ascending, not strictly; or more rows than values)
     bool identity = false;           // ... and this is so in this query
     bool dense = false;              // ... and the keys fill their whole range: entry number = key - min, probes skip bit and rank block (the sizing pass saw unique keys and as many entries as rows)
     // DIRECT: such a table whose key statistics are known beforehand (uniqueKnown) and whose payload values are all plain columns of the scanned

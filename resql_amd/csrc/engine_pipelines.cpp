@@ -80,6 +80,13 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
             const size_t w = (size_t)atoi(f.c_str() + 3) - h.keys.size();
             return h.direct && h.directSrc && w < h.directCols.size() ? (uint64_t)(uintptr_t)h.directSrc->cols[(size_t)h.directCols[w]].dptr : 0ull;
         }
+        if ((f.compare(0, 4, "code") == 0 || f.compare(0, 4, "dict") == 0) && f.size() > 4 && isdigit((unsigned char)f[4])) {
+            // ... of a payload with a dictionary origin: the build table's codes and dictionary (codegen_join.cpp consumeMatch)
+            const size_t w = (size_t)atoi(f.c_str() + 4) - h.keys.size();
+            if (!h.direct || !h.directSrc || w >= h.directCols.size()) return 0ull;
+            const TableColumn& c = h.directSrc->cols[(size_t)h.directCols[w]];
+            return (uint64_t)(uintptr_t)(f[0] == 'c' ? c.codePtr : c.dictPtr);
+        }
         if (f == "temp") return (uint64_t)(uintptr_t)h.dTemp;
         if (f == "treg") return (uint64_t)h.tempRegion;
         if (f == "tused") return (uint64_t)(uintptr_t)h.dTempUsed;
@@ -580,6 +587,9 @@ void sizeJoinTable(Query& q, Pipeline& p, HashTable& h, uint32_t n, bool dupKeys
     // accumulators beside the entries and makes its group rows from them
     h.direct = h.identity && h.directCapable && h.uniqueKnown && q.aggTable != h.id && h.directSrc == p.src;
     for (int c : h.directCols) h.direct = h.direct && p.src->cols[(size_t)c].dptr != nullptr;
+    // (a payload with a dictionary origin is read from the column's codes and dictionary: codegen_join.cpp consumeMatch)
+    for (size_t w = 0; w < h.directCols.size(); w++)
+        if (h.originOf(w)) h.direct = h.direct && p.src->cols[(size_t)h.directCols[w]].codePtr != nullptr && p.src->cols[(size_t)h.directCols[w]].dictPtr != nullptr;
     if (h.direct && !h.dense && !h.keyIndex && !ctx.planMemoOff && h.directKeyCol >= 0) {
         // the context may hold this column's key index already (another query built it, or this statement's previous query did)
         auto it = ctx.keyIndexes.find(Context::KeyIndexKey{p.src->uid, p.src->version, p.src->nRows, p.src->row0, h.directKeyCol});

@@ -13,7 +13,13 @@ usage: python tools/dict_group_bench.py [SF] --tail [--runs N] [--repeat N] [--o
 The device tail of a dense aggregation with a coded key against its host tail (RSQ_DEVICE_TAIL=0, which is the parent commit's tail
 for such a statement): `group by l_shipmode, l_suppkey`, one process, one compiled statement, the switch read at every execution and
 the runs alternating.  Per run and over the runs: whole execution, kernels and tail (rsq_report.finalize_time_ms), as
-tools/hash_tail_bench.py prints them."""
+tools/hash_tail_bench.py prints them.
+
+usage: python tools/dict_group_bench.py [SF] --join-keys --parent-tree DIR [--runs N] [--repeat N] [--out FILE] [--sha SHA]
+Dense group ids for a string from a join's build side (RSQ_DICT_SCANS=2): TPC-H Q5, whose n_name reaches lineitem's aggregation through
+the supplier's table, and Q12 as the control (its key is lineitem's own column: 1 and 2 give it one kernel).  One worker per build
+loads the six tables Q5 reads with the images on and compiles both statements under RSQ_DICT_SCANS = 0, 1 and 2 (the parent: 0 and 1);
+all stay resident and the runs alternate between builds and switches.  Every answer is compared with tests/golden/ref_full_<q>_sf<SF>.tbl."""
 import json
 import os
 import statistics
@@ -71,6 +77,96 @@ def worker(tree, sf, repeat, also=""):
     for t in tabs:
         t.close()
     ctx.close()
+
+
+def join_worker(tree, sf, repeat, switches):
+    """one build: the tables with the images on, Q5 and Q12 compiled under every switch, then a run per line read from the orchestrator"""
+    sys.path.insert(0, tree)
+    os.environ["RSQ_DICT_SCANS"] = max(switches)                          # (the images are built when a table is created)
+    from resql_amd import engine, tpch_full
+    db = tpch_full.database(sf, fill_unused=False)
+    names = sorted(db)
+    print(f"[{tree}] tables generated", file=sys.stderr, flush=True)
+    ctx = engine.Context(device=0)
+    tabs = [ctx.table(db[k]) for k in names]
+    print(f"[{tree}] tables loaded", file=sys.stderr, flush=True)
+    qs, ready = {}, {"ready": True, "aggregation": {}, "equals_reference_answer": {}, "answers": {}}
+    for name in ("q5", "q12"):
+        gold = os.path.join(HERE, "tests", "golden", f"ref_full_{name}_sf{sf:g}.tbl")
+        want = open(gold, encoding="latin1").read() if os.path.exists(gold) else None
+        for sw in switches:
+            os.environ["RSQ_DICT_SCANS"] = sw                             # (read when a statement is compiled)
+            q = ctx.sql_compile(tpch_full.QUERIES[name], tabs)
+            q.await_kernels()
+            for _ in range(3):
+                q.execute()
+            key = f"{name}@{sw}"
+            qs[key] = q
+            ready["aggregation"][key] = [s for l in q.explain.splitlines() if l.startswith("pipeline") for s in l.split(" -> ") if "aggregation" in s]
+            ready["answers"][key] = q.result().text
+            ready["equals_reference_answer"][key] = None if want is None else q.result().text == want
+    print(json.dumps(ready), flush=True)
+    flip = False
+    for line in sys.stdin:
+        if line.strip() != "run":
+            break
+        out = {}
+        for key in (sorted(qs, reverse=flip)):
+            q, ex, ke = qs[key], [], []
+            for _ in range(repeat):
+                q.execute()
+                r = q.report()
+                ex.append(r.execution_time_ms)
+                if r.kernel_time_ms > 0:
+                    ke.append(r.kernel_time_ms)
+            out[key] = {"exec_ms_median": statistics.median(ex), "exec_ms_min": min(ex), "kernel_ms_median": statistics.median(ke) if ke else None}
+        flip = not flip
+        print(json.dumps(out), flush=True)
+    for q in qs.values():
+        q.close()
+    for t in tabs:
+        t.close()
+    ctx.close()
+
+
+def join_keys(sf, runs, repeat, emit, parent_tree):
+    trees = {"this": (HERE, "0,1,2")}
+    if parent_tree:
+        trees = {"parent": (os.path.abspath(parent_tree), "0,1"), "this": (HERE, "0,1,2")}
+    procs = {b: subprocess.Popen([sys.executable, os.path.abspath(__file__), "--join-worker", t, str(sf), str(repeat), sw], stdin=subprocess.PIPE,
+                                 stdout=subprocess.PIPE, text=True) for b, (t, sw) in trees.items()}
+    try:
+        ready = {b: json.loads(p.stdout.readline()) for b, p in procs.items()}
+        first = ready["this"]["answers"]
+        for b in trees:
+            for key, agg in ready[b]["aggregation"].items():
+                emit({"statement": key.split("@")[0], "sf": sf, "RSQ_DICT_SCANS": key.split("@")[1], "build": b, "aggregation": agg,
+                      "equals_reference_answer": ready[b]["equals_reference_answer"][key],
+                      "same_answer_as_this_at_0": ready[b]["answers"][key] == first[key.split("@")[0] + "@0"]})
+        series = {b: {} for b in trees}
+        for run in range(1, runs + 1):
+            for b in (list(trees) if run % 2 else list(trees)[::-1]):             # (alternating, and alternating who goes first)
+                procs[b].stdin.write("run\n")
+                procs[b].stdin.flush()
+                for key, v in json.loads(procs[b].stdout.readline()).items():
+                    series[b].setdefault(key, []).append(v)
+                    emit(dict(v, statement=key.split("@")[0], RSQ_DICT_SCANS=key.split("@")[1], build=b, run=run))
+        for b in trees:
+            for key, vs in sorted(series[b].items()):
+                ex = [v["exec_ms_median"] for v in vs]
+                ke = [v["kernel_ms_median"] for v in vs if v["kernel_ms_median"] is not None]
+                emit({"summary": key.split("@")[0], "RSQ_DICT_SCANS": key.split("@")[1], "build": b, "runs": runs, "executions_per_run": repeat,
+                      "exec_ms": {"median": round(statistics.median(ex), 4), "min": round(min(ex), 4), "max": round(max(ex), 4)},
+                      "kernel_ms": {"median": round(statistics.median(ke), 4), "min": round(min(ke), 4), "max": round(max(ke), 4)} if ke else None})
+    finally:
+        for p in procs.values():
+            try:
+                p.stdin.write("quit\n")
+                p.stdin.close()
+            except OSError:
+                pass
+        for p in procs.values():
+            p.wait()
 
 
 TAIL_SQL = "select l_shipmode, l_suppkey, count(*), sum(l_quantity) from lineitem group by l_shipmode, l_suppkey"
@@ -134,6 +230,12 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if "--join-keys" in sys.argv:
+        join_keys(sf, runs, repeat, emit, arg("--parent-tree", ""))
+        if sha:
+            emit({"head_sha": sha})
+        return
+
     if "--tail" in sys.argv:
         tail_rows(sf, runs, repeat, emit)
         if sha:
@@ -177,7 +279,9 @@ def main():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--worker":
+    if len(sys.argv) > 1 and sys.argv[1] == "--join-worker":
+        join_worker(sys.argv[2], float(sys.argv[3]), int(sys.argv[4]), sys.argv[5].split(","))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--worker":
         worker(sys.argv[2], float(sys.argv[3]), int(sys.argv[4]), sys.argv[5] if len(sys.argv) > 5 else "")
     else:
         main()
