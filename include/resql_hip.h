@@ -319,6 +319,35 @@ int   rsq_prim_rank_index(rsq_ctx* ctx, uint32_t* blocks /* [n_blocks * 8], in a
 int   rsq_prim_rank_place(rsq_ctx* ctx, const uint32_t* blocks /* [n_blocks * 8] */, int64_t n_blocks, int64_t bm_min, int64_t bm_bits,
                           const int64_t* records /* [n_waves * region * n_words] */, const uint32_t* used /* [n_waves] */, int32_t n_waves,
                           int32_t region, int32_t n_words, int64_t capacity, int64_t* words_out /* [capacity * n_words] */, uint32_t* notes);
+/* The kernels that finish an aggregation (devtail.hip, aot_kernels.hip), under the same conventions.  None of them raises a bit of the error
+ * word on the inputs these entry points accept, except the merge's 2 ("Hash table full"), which its table of >= 2 n slots does not reach. */
+/* radixSortPairs: the pairs sorted, stably, by the low 8 * ceil(key_bits / 8) bits of their keys (whole 8-bit digits); key_bits 1..64.  The
+ * result is copied from whichever of the two buffer pairs holds it; with n <= 1 nothing runs and the input is the answer. */
+int   rsq_prim_radix_sort_pairs(rsq_ctx* ctx, const uint64_t* keys /* [n] */, const uint32_t* vals /* [n] */, int64_t n, int32_t key_bits,
+                                uint64_t* keys_out /* [n] */, uint32_t* vals_out /* [n] */, uint32_t* notes);
+/* out[i] = min(in[0..i]): the running minimum of the device replay of the reference's hash table (k_scanmin_chunks / _totals / _apply). */
+int   rsq_prim_running_min(rsq_ctx* ctx, const int64_t* in /* [n] */, int64_t n, int64_t* out /* [n] */, uint32_t* notes);
+/* mergeGroupRows: n group rows [first row | n_tab table words | accumulators] of `stride` words merged by key.  Key k is row word
+ * key_word[k] of type key_type[k] (rsq_type_tag); key_len[k] is 0 for a number, 1 for CHAR(1), the declared length for CHAR(n) /
+ * VARCHAR(n), whose bytes fill ceil(len / 8) consecutive words.  INT / DATE compare by their low 32 bits, BOOL / CHAR(1) by their low byte,
+ * CHAR(n) without trailing spaces, VARCHAR up to its NUL.  Accumulator w is row word acc_word[w], merged by acc_kind[w]: 0 wrapping int64 sum,
+ * 2 min, 3 max.  out_rows receives one row per group - first row: the members' minimum; table words: those of the member with that
+ * first row; accumulators merged - in the order of the groups' owners (the member that claimed the group's slot), *out_count the number
+ * of groups; the rows behind them are 0xff bytes.  Requires n < 2^31, n_keys <= 16, n_acc <= 32, every key inside words 1..n_tab, every
+ * accumulator word inside n_tab + 1..stride - 1. */
+int   rsq_prim_merge_group_rows(rsq_ctx* ctx, const int64_t* rows /* [n * stride] */, int64_t n, int32_t stride, int32_t n_tab,
+                                const int32_t* key_word, const int32_t* key_type, const int32_t* key_len, int32_t n_keys, const int32_t* acc_word,
+                                const int32_t* acc_kind, int32_t n_acc, int64_t* out_rows /* [n * stride] */, uint64_t* out_count, uint32_t* notes);
+/* The ORDER BY ... LIMIT pre-selection over rows of `stride` words with the sort key in word key_word (is32: its low 32 bits, signed; desc:
+ * larger first).  A key's image is (key ^ 2^63), complemented for ascending order, so "earlier in the order" is "larger".  n_rows goes
+ * into a device word, as the engine's row count does; the kernels take min(n_rows, rows_upper_bound) rows.  form 0: selectTopCandidates,
+ * the rows whose image is at or above the want-th largest.  form 1: prepareTopCandidatesRange, image_range = {largest image, ~smallest
+ * image} copied into the scratch (the caller supplies it: nothing is computed here), selectTopCandidatesRange: the rows of the 11-bit bin
+ * of the want-th largest image and of every bin above.  *cand_count is the number of such rows, cand_out - 0xff bytes before the launch -
+ * holds the first `capacity` of them in no particular order.  Requires want >= 1, capacity >= 1, stride 1..64, key_word < stride. */
+int   rsq_prim_topk_select(rsq_ctx* ctx, const int64_t* rows /* [n_rows * stride] */, int64_t n_rows, int64_t rows_upper_bound, int32_t stride,
+                           int32_t key_word, int32_t is32, int32_t desc, int64_t want, int32_t form, const uint64_t* image_range /* [2], form 1 */,
+                           int64_t capacity, int64_t* cand_out /* [capacity * stride] */, uint32_t* cand_count, uint32_t* notes);
 
 /* ---- SQL text in front of the path --------------------------------------
  * The reference turns SQL text into an operator tree with parseSql (src/parser/parseSql.h:130-166:

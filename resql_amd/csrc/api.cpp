@@ -184,6 +184,8 @@ Context& primContext(rsq_ctx* ctx) {
     return c;
 }
 const int64_t kPrimMaxRankBlocks = (int64_t)1171 * RSQ_RANK_CHUNK_BLOCKS;      // a key domain of 2^28 bits (k_rank_blocks_chained)
+const int64_t kPrimMaxItems = (int64_t)1 << 31;      // pairs, values, rows of one call: the kernels' tile and row indices are 32 bits
+const int32_t kPrimMaxStride = 4096;                 // words of a group row (a merge)
 }  // namespace
 
 extern "C" {
@@ -566,6 +568,133 @@ int rsq_prim_rank_place(rsq_ctx* ctx, const uint32_t* blocks, int64_t n_blocks, 
         rankTableIndex(c, dBm, n_blocks, dTotal, dBase);
         rankTablePlace(c, dRec, dUsed, (uint32_t)n_waves, (uint32_t)region, dCount, n_words, dBm, bm_min, bm_bits, dBase, n_blocks, dWords, capacity);
         RSQ_HIP(hipMemcpyAsync(words_out, dWords, outWords * 8, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_radix_sort_pairs(rsq_ctx* ctx, const uint64_t* keys, const uint32_t* vals, int64_t n, int32_t key_bits, uint64_t* keys_out,
+                              uint32_t* vals_out, uint32_t* notes) {
+    if (!ctx || !notes || n < 0 || n > kPrimMaxItems || (n > 0 && (!keys || !vals || !keys_out || !vals_out)) || key_bits < 1 || key_bits > 64)
+        return RSQ_ERR_INVALID;
+    *notes = 0;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        if (n == 0) return;
+        const uint32_t before = primErrWord(c);
+        PrimBuffers b(c);
+        uint64_t* dKeys[2] = {b.take<uint64_t>((size_t)n), b.take<uint64_t>((size_t)n)};
+        uint32_t* dVals[2] = {b.take<uint32_t>((size_t)n), b.take<uint32_t>((size_t)n)};
+        const size_t tempBytes = radixSortTempBytes(n);
+        void* temp = b.take<char>(tempBytes);
+        RSQ_HIP(hipMemcpyAsync(dKeys[0], keys, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemcpyAsync(dVals[0], vals, (size_t)n * 4, hipMemcpyHostToDevice, c.stream));
+        // (n <= 1: nothing runs and the A buffers, the input, are the answer)
+        const int in = radixSortPairs(c, dKeys[0], dVals[0], dKeys[1], dVals[1], n, key_bits, temp, tempBytes) ? 1 : 0;
+        RSQ_HIP(hipMemcpyAsync(keys_out, dKeys[in], (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
+        RSQ_HIP(hipMemcpyAsync(vals_out, dVals[in], (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_running_min(rsq_ctx* ctx, const int64_t* in, int64_t n, int64_t* out, uint32_t* notes) {
+    if (!ctx || !notes || n < 0 || n > kPrimMaxItems || (n > 0 && (!in || !out))) return RSQ_ERR_INVALID;
+    *notes = 0;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        if (n == 0) return;
+        const uint32_t before = primErrWord(c);
+        PrimBuffers b(c);
+        int64_t* dV = b.take<int64_t>((size_t)n);
+        int64_t* dChunkMin = b.take<int64_t>(runningMinTempBytes(n) / 8);
+        RSQ_HIP(hipMemcpyAsync(dV, in, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
+        runningMinInPlace(c, dV, n, dChunkMin);
+        RSQ_HIP(hipGetLastError());
+        RSQ_HIP(hipMemcpyAsync(out, dV, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_merge_group_rows(rsq_ctx* ctx, const int64_t* rows, int64_t n, int32_t stride, int32_t n_tab, const int32_t* key_word,
+                              const int32_t* key_type, const int32_t* key_len, int32_t n_keys, const int32_t* acc_word, const int32_t* acc_kind,
+                              int32_t n_acc, int64_t* out_rows, uint64_t* out_count, uint32_t* notes) {
+    if (!ctx || !notes || !out_count || n < 0 || (n > 0 && (!rows || !out_rows))) return RSQ_ERR_INVALID;
+    *notes = 0;
+    // (the kernels trust the spec: a key's words and an accumulator's word are row offsets)
+    if (n >= ((int64_t)1 << 31) || stride < 1 || stride > kPrimMaxStride || n_tab < 0 || n_tab > stride - 1 || n_keys < 0 || n_keys > 16 || n_acc < 0 ||
+        n_acc > 32 || (n_keys > 0 && (!key_word || !key_type || !key_len)) || (n_acc > 0 && (!acc_word || !acc_kind)))
+        return RSQ_ERR_INVALID;
+    GroupMergeSpec spec{};
+    spec.stride = stride; spec.nTab = n_tab; spec.nAcc = n_acc;
+    spec.keys.n = n_keys;
+    for (int32_t k = 0; k < n_keys; k++) {
+        const int32_t t = key_type[k], len = key_len[k];
+        if (t != RSQ_VARCHAR && t != RSQ_CHAR && t != RSQ_BOOL && t != RSQ_INT && t != RSQ_BIGINT && t != RSQ_DECIMAL && t != RSQ_DATE) return RSQ_ERR_INVALID;
+        const bool string = t == RSQ_VARCHAR || t == RSQ_CHAR;
+        if (len < 0 || (string && len < 1) || (!string && len > 1)) return RSQ_ERR_INVALID;
+        const int64_t words = len > 1 ? ((int64_t)len + 7) / 8 : 1;          // (len <= 1: one word, compared by the type's rule)
+        if (key_word[k] < 1 || (int64_t)key_word[k] + words - 1 > n_tab) return RSQ_ERR_INVALID;
+        spec.keys.k[k] = RowTailKey{key_word[k], t, len, 0};
+    }
+    for (int32_t w = 0; w < n_acc; w++) {
+        if (acc_word[w] < n_tab + 1 || acc_word[w] > stride - 1 || (acc_kind[w] != 0 && acc_kind[w] != 2 && acc_kind[w] != 3)) return RSQ_ERR_INVALID;
+        spec.accWord[w] = acc_word[w]; spec.accKind[w] = acc_kind[w];
+    }
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        const uint32_t before = primErrWord(c);
+        const size_t words = (size_t)n * (size_t)stride;
+        PrimBuffers b(c);
+        int64_t* dRows = b.take<int64_t>(words);
+        int64_t* dOut = b.take<int64_t>(words);
+        void* temp = b.take<char>(groupMergeTempBytes(n));
+        uint64_t* dCount = b.take<uint64_t>(1);
+        if (words) RSQ_HIP(hipMemcpyAsync(dRows, rows, words * 8, hipMemcpyHostToDevice, c.stream));
+        if (words) RSQ_HIP(hipMemsetAsync(dOut, 0xff, words * 8, c.stream));
+        mergeGroupRows(c, dRows, n, spec, temp, dOut, dCount);
+        if (words) RSQ_HIP(hipMemcpyAsync(out_rows, dOut, words * 8, hipMemcpyDeviceToHost, c.stream));
+        RSQ_HIP(hipMemcpyAsync(out_count, dCount, 8, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        primNotes(c, before, notes);
+    });
+}
+
+int rsq_prim_topk_select(rsq_ctx* ctx, const int64_t* rows, int64_t n_rows, int64_t rows_upper_bound, int32_t stride, int32_t key_word, int32_t is32,
+                         int32_t desc, int64_t want, int32_t form, const uint64_t* image_range, int64_t capacity, int64_t* cand_out,
+                         uint32_t* cand_count, uint32_t* notes) {
+    if (!ctx || !notes || !cand_out || !cand_count || n_rows < 0 || (n_rows > 0 && !rows)) return RSQ_ERR_INVALID;
+    *notes = 0;
+    // (the kernels trust these: a row address comes from stride and key_word, a candidate address from capacity; row indices are 32 bits)
+    if (n_rows > kPrimMaxItems || rows_upper_bound < 0 || rows_upper_bound > kPrimMaxItems || stride < 1 || stride > 64 || key_word < 0 ||
+        key_word >= stride || want < 1 || want > 0xffffffffll || capacity < 1 || capacity > kPrimMaxItems || (form != 0 && form != 1) ||
+        (form == 1 && !image_range))
+        return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        const uint32_t before = primErrWord(c);
+        const size_t rowWords = (size_t)n_rows * (size_t)stride, candWords = (size_t)capacity * (size_t)stride;
+        PrimBuffers b(c);
+        int64_t* dRows = b.take<int64_t>(rowWords);
+        uint32_t* dN = b.take<uint32_t>(1);
+        uint64_t* dImages = b.take<uint64_t>((size_t)std::min<int64_t>(n_rows, rows_upper_bound));      // (the kernels take min(*nRows, bound) rows)
+        char* scratch = b.take<char>(topkHistBytes());
+        int64_t* dCand = b.take<int64_t>(candWords);
+        const uint32_t n32 = (uint32_t)n_rows;
+        if (rowWords) RSQ_HIP(hipMemcpyAsync(dRows, rows, rowWords * 8, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemcpyAsync(dN, &n32, 4, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemsetAsync(dCand, 0xff, candWords * 8, c.stream));
+        if (form == 1) {
+            prepareTopCandidatesRange(c, scratch);
+            RSQ_HIP(hipMemcpyAsync(scratch, image_range, 16, hipMemcpyHostToDevice, c.stream));
+            selectTopCandidatesRange(c, dRows, stride, key_word, is32 != 0, desc != 0, dN, (uint32_t)rows_upper_bound, (uint32_t)want, scratch, dCand,
+                                     (uint32_t)capacity);
+        } else
+            selectTopCandidates(c, dRows, stride, key_word, is32 != 0, desc != 0, dN, (uint32_t)rows_upper_bound, (uint32_t)want, dImages, scratch, dCand,
+                                (uint32_t)capacity);
+        RSQ_HIP(hipMemcpyAsync(cand_out, dCand, candWords * 8, hipMemcpyDeviceToHost, c.stream));
+        RSQ_HIP(hipMemcpyAsync(cand_count, scratch + 16, 4, hipMemcpyDeviceToHost, c.stream));
         primSync(c);
         primNotes(c, before, notes);
     });

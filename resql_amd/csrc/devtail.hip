@@ -108,7 +108,8 @@ size_t radixSortTempBytes(int64_t n) {
     return (size_t)cells * 4 + 64 + (size_t)cells * 8 + 64 + scanTempBytes(cells);
 }
 
-// sorts n pairs by the low `keyBits` bits of the keys; the result is in (keysA, valsA) after an even number of passes, in
+// sorts n pairs, stably, by the low 8 * ceil(keyBits / 8) bits of the keys (whole 8-bit digits: a bit above keyBits inside the last
+// digit takes part, the bits above that digit do not); the result is in (keysA, valsA) after an even number of passes, in
 // (keysB, valsB) after an odd one: returns true when it is in the B buffers
 bool radixSortPairs(Context& ctx, uint64_t* keysA, uint32_t* valsA, uint64_t* keysB, uint32_t* valsB, int64_t n, int keyBits, void* temp, size_t tempBytes) {
     if (n <= 1 || keyBits <= 0) return false;
@@ -594,6 +595,16 @@ __global__ void __launch_bounds__(256) k_scanmin_apply(i64* __restrict__ v, i64 
         if (b < v[i]) v[i] = b;
     }
 }
+size_t runningMinTempBytes(int64_t n) { return (size_t)((n + SM_CHUNK - 1) / SM_CHUNK + 1) * 8; }
+// v[i] = min(v[0..i]) in place, on ctx.stream; `chunkMin` holds runningMinTempBytes(n) bytes
+void runningMinInPlace(Context& ctx, int64_t* v, int64_t n, int64_t* chunkMin) {
+    if (n <= 0) return;
+    const i64 nChunks = (n + SM_CHUNK - 1) / SM_CHUNK;
+    const unsigned applyGrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)n + 255) / 256));
+    hipLaunchKernelGGL(k_scanmin_chunks, dim3((unsigned)nChunks), dim3(256), 0, ctx.stream, (i64*)v, (i64)n, (i64*)chunkMin);
+    hipLaunchKernelGGL(k_scanmin_totals, dim3(1), dim3(1024), 0, ctx.stream, (i64*)chunkMin, nChunks);
+    hipLaunchKernelGGL(k_scanmin_apply, dim3(applyGrid), dim3(256), 0, ctx.stream, (i64*)v, (i64)n, (const i64*)chunkMin);
+}
 // one thread per slot; a cluster is replayed by the thread of its first slot
 __global__ void __launch_bounds__(256) k_rp_clusters(const u64* __restrict__ start, const i64* __restrict__ minS, u64 N, i64 cnt, const u32* __restrict__ items,
                                                      const u32* __restrict__ home, const u64* __restrict__ ts /* null: item index */, u32* __restrict__ who) {
@@ -668,7 +679,7 @@ bool replayLevels(uint64_t n, uint64_t minSize, std::vector<std::pair<uint64_t, 
 size_t replayDeviceBytes(uint64_t n, uint64_t nMax) {
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     return up(n * 4) + up(n * 4) + up(n * 8) + up((nMax + 1) * 4) + up((nMax + 1) * 8) + up(2 * nMax * 8) + up(nMax * 4) + up(scanTempBytes((int64_t)nMax + 1)) +
-           up(((2 * nMax + SM_CHUNK - 1) / SM_CHUNK + 1) * 8);
+           up(runningMinTempBytes((int64_t)(2 * nMax)));
 }
 
 // order[k] = index (into hashes) of the group in the k-th occupied slot of the reference's table; everything on ctx.stream, no
@@ -695,10 +706,7 @@ void replayEmissionOrderDevice(Context& ctx, const uint64_t* hashes, uint64_t n,
         exclusiveScanCounts(ctx, count, (uint64_t*)start, (int64_t)N + 1, scanTemp, scanTempBytes((int64_t)N + 1));       // (count[N] is 0: the trailing slot)
         hipLaunchKernelGGL(k_rp_scatter, grid((u64)cnt), dim3(256), 0, ctx.stream, (const u32*)home, cnt, (const u64*)start, count, items);
         hipLaunchKernelGGL(k_rp_excess, grid(2 * N), dim3(256), 0, ctx.stream, (const u64*)start, N, cnt, S);
-        const i64 n2 = (i64)(2 * N), nChunks = (n2 + SM_CHUNK - 1) / SM_CHUNK;
-        hipLaunchKernelGGL(k_scanmin_chunks, dim3((unsigned)nChunks), dim3(256), 0, ctx.stream, S, n2, chunkMin);
-        hipLaunchKernelGGL(k_scanmin_totals, dim3(1), dim3(1024), 0, ctx.stream, chunkMin, nChunks);
-        hipLaunchKernelGGL(k_scanmin_apply, grid((u64)n2), dim3(256), 0, ctx.stream, S, n2, (const i64*)chunkMin);
+        runningMinInPlace(ctx, (int64_t*)S, (int64_t)(2 * N), (int64_t*)chunkMin);
         RSQ_HIP(hipMemsetAsync(who, 0xff, (size_t)N * 4, ctx.stream));
         hipLaunchKernelGGL(k_rp_clusters, grid(N), dim3(256), 0, ctx.stream, (const u64*)start, (const i64*)S, N, cnt, (const u32*)items, (const u32*)home,
                            L == 0 ? (const u64*)nullptr : (const u64*)ts, who);

@@ -370,6 +370,9 @@ void rowTailResultRows(Context& ctx, const int64_t* rows, int stride, const uint
 // the replay of the reference's aggregation hash table on the device (devtail.hip): level sizes on the host, everything else enqueued
 bool replayLevels(uint64_t n, uint64_t minSize, std::vector<std::pair<uint64_t, uint64_t>>& levels);
 size_t replayDeviceBytes(uint64_t n, uint64_t nMax);
+// the inclusive running minimum the replay takes its carries from (k_scanmin_*): v[i] = min(v[0..i]) in place, three launches on ctx.stream
+size_t runningMinTempBytes(int64_t n);
+void runningMinInPlace(Context& ctx, int64_t* v, int64_t n, int64_t* chunkMin /* runningMinTempBytes(n) */);
 void replayEmissionOrderDevice(Context& ctx, const uint64_t* hashes, uint64_t n, const std::vector<std::pair<uint64_t, uint64_t>>& levels, void* work, uint32_t* order);
 
 // tbl.cpp: '.tbl' text -> columns with the reference's BULK INSERT semantics (execute.h:332-388)

@@ -143,6 +143,10 @@ def lib():
         L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
         L.rsq_prim_rank_index.argtypes = [vp, vp, i64, i32, vp, vp]
         L.rsq_prim_rank_place.argtypes = [vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, i64, vp, vp]
+        L.rsq_prim_radix_sort_pairs.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
+        L.rsq_prim_running_min.argtypes = [vp, vp, i64, vp, vp]
+        L.rsq_prim_merge_group_rows.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+        L.rsq_prim_topk_select.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp]
         L.rsq_measure_read_bandwidth.argtypes = [vp, C.c_size_t, i32, C.POINTER(C.c_double)]
         L.rsq_sql_plan_select.argtypes = [vp, C.c_char_p, C.POINTER(vp), i32, C.POINTER(vp)]
         L.rsq_sql_plan_desc.restype = C.POINTER(P.rsq_plan_desc)
@@ -196,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_source", "rsq_query_explain",
     "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
+    "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_destroy",
@@ -280,6 +285,55 @@ class Context:
         self._check(self._L.rsq_prim_rank_place(self.h, blocks.ctypes.data, len(blocks), bm_min, bm_bits, records.ctypes.data, used.ctypes.data,
                                                 len(used), region, n_words, capacity, out.ctypes.data, C.addressof(notes)))
         return out, notes.value
+
+    def prim_radix_sort_pairs(self, keys: np.ndarray, vals: np.ndarray, key_bits: int):
+        """(uint64 key, uint32 value) pairs sorted, stably, by the low 8 * ceil(key_bits / 8) bits of the keys: (keys, vals, notes)"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        if len(keys) != len(vals):
+            raise ValueError("as many values as keys")
+        keys_out, vals_out = np.zeros(len(keys), dtype=np.uint64), np.zeros(len(keys), dtype=np.uint32)
+        notes = C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_radix_sort_pairs(self.h, keys.ctypes.data, vals.ctypes.data, len(keys), key_bits, keys_out.ctypes.data,
+                                                      vals_out.ctypes.data, C.addressof(notes)))
+        return keys_out, vals_out, notes.value
+
+    def prim_running_min(self, values: np.ndarray):
+        """out[i] = min(values[0..i]) of int64 values: (out, notes)"""
+        values = np.ascontiguousarray(values, dtype=np.int64)
+        out = np.zeros(len(values), dtype=np.int64)
+        notes = C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_running_min(self.h, values.ctypes.data, len(values), out.ctypes.data, C.addressof(notes)))
+        return out, notes.value
+
+    def prim_merge_group_rows(self, rows: np.ndarray, n_tab: int, keys, accs):
+        """group rows [n, stride] of int64 ([first row | n_tab table words | accumulators]) merged by key; keys: (word, type tag, len)
+        each, accs: (word, kind 0 sum / 2 min / 3 max) each: (the groups' rows [count, stride], notes)"""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        n, stride = rows.shape
+        kw, kt, kl = (np.array([k[j] for k in keys], dtype=np.int32) for j in range(3))
+        aw, ak = (np.array([a[j] for a in accs], dtype=np.int32) for j in range(2))
+        out = np.zeros((n, stride), dtype=np.int64)
+        count, notes = C.c_uint64(0xffffffffffffffff), C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_merge_group_rows(self.h, rows.ctypes.data, n, stride, n_tab, kw.ctypes.data, kt.ctypes.data, kl.ctypes.data, len(keys),
+                                                      aw.ctypes.data, ak.ctypes.data, len(accs), out.ctypes.data, C.addressof(count), C.addressof(notes)))
+        if count.value > n:
+            raise EngineError(5, f"the merge reports {count.value} groups of {n} rows")
+        return out[:count.value], notes.value
+
+    def prim_topk_select(self, rows: np.ndarray, key_word: int, is32: bool, desc: bool, want: int, form: int, capacity: int,
+                         rows_upper_bound: Optional[int] = None, image_range=None):
+        """ORDER BY ... LIMIT pre-selection over rows [n, stride] of int64; form 0: the exact radix select, 1: the one-histogram form over
+        image_range = (largest image, ~smallest image): (cand [capacity, stride], 0xff bytes where nothing was written; count; notes)"""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        n, stride = rows.shape
+        rng = None if image_range is None else np.array([int(x) & 0xffffffffffffffff for x in image_range], dtype=np.uint64)
+        cand = np.zeros((capacity, stride), dtype=np.int64)
+        count, notes = C.c_uint32(0xffffffff), C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_topk_select(self.h, rows.ctypes.data, n, n if rows_upper_bound is None else rows_upper_bound, stride, key_word,
+                                                 1 if is32 else 0, 1 if desc else 0, want, form, None if rng is None else rng.ctypes.data, capacity,
+                                                 cand.ctypes.data, C.addressof(count), C.addressof(notes)))
+        return cand, count.value, notes.value
 
     def set_stream(self, hip_stream: Optional[int]):
         """launch on the caller's HIP stream (an integer handle, 0 = the null stream; e.g.

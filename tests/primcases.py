@@ -228,3 +228,514 @@ def place_cases():
         for n_waves in PLACE_WAVES:
             out.append((f"words{n_words}_waves{n_waves}", PlaceCase(n_words, n_waves, used_shift=i)))
     return out
+
+
+# =====================================================================================================================================
+# The kernels that finish an aggregation: the radix sort of the device tail, the running minimum of the replay, the merge of several
+# shards' group rows (devtail.hip) and the ORDER BY ... LIMIT pre-selection (aot_kernels.hip), through rsq_prim_radix_sort_pairs,
+# rsq_prim_running_min, rsq_prim_merge_group_rows and rsq_prim_topk_select.  Integer operations all four: every reference is exact.
+# =====================================================================================================================================
+RS_TILE = 2048                # pairs per workgroup of a sort pass, taken in rounds of 256:   devtail.hip  #define RS_TILE 2048
+SM_CHUNK = 4096               # values per workgroup of the running minimum, 16 per thread:   devtail.hip  #define SM_CHUNK 4096
+SM_BATCH = 1024               # chunk minima per batch of k_scanmin_totals (base += 1024):    devtail.hip, literal in the kernel
+TOPK_BINS = 2048              # bins of one histogram (an 11-bit digit):                      aot_kernels.hip  enum { TOPK_PASSES = 6, TOPK_BINS = 2048 }
+TOPK_PASSES = 6               # five 11-bit digits and a last one of 9 bits (topk_shift / topk_bits)
+NOTE_MERGE_FULL = 2           # k_gm_insert: "Hash table full" (a table of >= 2 n slots: not reached)
+NOTE_NAMES[NOTE_MERGE_FULL] = "2: the merge's hash table is full"
+NOTE_NAMES[256] = "256: a meeting point of the one-launch top-k selection timed out"
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+U64 = (1 << 64) - 1
+# rsq_type_tag (include/resql_plan.h)
+T_VARCHAR, T_CHAR, T_BOOL, T_INT, T_BIGINT, T_DECIMAL, T_DATE = 0, 1, 2, 3, 4, 5, 7
+
+
+# ---- sort ---------------------------------------------------------------------------------------------------------------------------
+SORT_SIZES = [0, 1, 2, 63, 64, 65, 255, 256, 257, RS_TILE - 1, RS_TILE, RS_TILE + 1, 2 * RS_TILE - 1, 2 * RS_TILE + 1, 3 * RS_TILE + 1, 600_001]
+SORT_KEY_BITS = [1, 8, 9, 16, 17, 24, 32, 33, 41, 63, 64]          # 1, 1, 2, 2, 3, 3, 4, 5, 6, 8, 8 passes
+SORT_PATTERNS = ["equal", "digits_0_255", "lane_digits", "ascending", "descending", "copies50", "top_byte", "above_mask"]
+
+
+def sort_passes(key_bits):
+    return (key_bits + 7) // 8
+
+
+def sort_mask(key_bits):
+    """the bits radixSortPairs sorts by: whole 8-bit digits, 8 * ceil(key_bits / 8) of them"""
+    return (1 << 8 * sort_passes(key_bits)) - 1
+
+
+def sort_keys(n, key_bits, pattern, seed=0):
+    """`n` uint64 keys.  equal: a tile's 2048 pairs share every digit.  digits_0_255: every digit is the first or the last bin.
+    lane_digits: digit d of key i is i % 256 in every pass - the 256 lanes of a round hold 256 different digits.  copies50: about 50
+    copies of every key (stability decides their order).  top_byte: only the last pass sees a difference.  above_mask: copies50 with
+    random bits above the sorted ones, which must travel with the key and not matter."""
+    rng = np.random.default_rng(n * 11 + key_bits * 1000 + seed)
+    passes, mask = sort_passes(key_bits), np.uint64(sort_mask(key_bits))
+    i = np.arange(n, dtype=np.uint64)
+    if pattern == "equal":
+        return np.full(n, 0x5a5a5a5a5a5a5a5a, dtype=np.uint64) & mask
+    if pattern == "digits_0_255":
+        k = np.zeros(n, dtype=np.uint64)
+        for d in range(passes):
+            k |= rng.integers(0, 2, n, dtype=np.uint64) * np.uint64(255) << np.uint64(8 * d)
+        return k
+    if pattern == "lane_digits":
+        return (i % np.uint64(256)) * np.uint64(0x0101010101010101) & mask
+    if pattern in ("ascending", "descending"):
+        up = i * np.uint64(int(mask) // max(n, 1)) if n <= int(mask) else i * (mask + np.uint64(1)) // np.uint64(max(n, 1))      # sorted, over the whole range
+        return up if pattern == "ascending" else up[::-1].copy()
+    distinct = rng.integers(0, 1 << 63, n // 50 + 1, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, n // 50 + 1, dtype=np.uint64) & mask
+    k = distinct[rng.integers(0, len(distinct), n)]
+    if pattern == "copies50":
+        return k
+    if pattern == "top_byte":
+        return (k & np.uint64(0xff)) << np.uint64(8 * (passes - 1)) | np.uint64(0x0123456789abcdef) & (mask >> np.uint64(8))
+    if pattern == "above_mask":
+        above = rng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, n, dtype=np.uint64) & ~mask
+        return k | above
+    raise AssertionError(pattern)
+
+
+def sort_vals(n, kind, seed=0):
+    """arange: the input position, which makes stability visible; random: any 32 bits, 0xffffffff among them"""
+    if kind == "arange":
+        return np.arange(n, dtype=np.uint32)
+    v = np.random.default_rng(n + seed).integers(0, 1 << 32, n, dtype=np.uint32)
+    v[::7] = 0xffffffff
+    return v
+
+
+def sort_reference(keys, vals, key_bits):
+    order = np.argsort(keys & np.uint64(sort_mask(key_bits)), kind="stable")
+    return keys[order], vals[order]
+
+
+def sort_reference_loop(keys, vals, key_bits):
+    mask = sort_mask(key_bits)
+    order = sorted(range(len(keys)), key=lambda i: (int(keys[i]) & mask, i))
+    return [int(keys[i]) for i in order], [int(vals[i]) for i in order]
+
+
+def sort_cases():
+    """(n, key_bits, pattern, vals kind).  Every key_bits with 2049 (every pattern) and 600 001 (copies50 and one more pattern, all of
+    them over the list); every other size with an odd and an even number of passes - the result in either buffer pair - and every
+    pattern; three cases whose values are not the input positions."""
+    out = []
+    odd = [b for b in SORT_KEY_BITS if sort_passes(b) % 2 == 1]
+    even = [b for b in SORT_KEY_BITS if sort_passes(b) % 2 == 0]
+    for j, n in enumerate(SORT_SIZES):
+        for b in SORT_KEY_BITS if n == RS_TILE + 1 else (odd[j % len(odd)], even[j % len(even)]) if n != 600_001 else ():
+            out += [(n, b, p, "arange") for p in SORT_PATTERNS]
+    for j, b in enumerate(SORT_KEY_BITS):
+        out += [(600_001, b, p, "arange") for p in sorted({"copies50", SORT_PATTERNS[j % len(SORT_PATTERNS)]})]
+    out += [(257, 17, "copies50", "random"), (RS_TILE + 1, 16, "copies50", "random"), (3 * RS_TILE + 1, 41, "digits_0_255", "random")]
+    return out
+
+
+# ---- running minimum ------------------------------------------------------------------------------------------------------------------
+RUNMIN_SIZES = [1, 15, 16, 17, 1023, 1024, 1025, SM_CHUNK - 1, SM_CHUNK, SM_CHUNK + 1, 2 * SM_CHUNK + 1,
+                SM_BATCH * SM_CHUNK - 1, SM_BATCH * SM_CHUNK, SM_BATCH * SM_CHUNK + 1, (SM_BATCH + 1) * SM_CHUNK + 17]      # the last four: a second
+#                 batch of k_scanmin_totals, 34 MB each way
+RUNMIN_PATTERNS = ["increasing", "decreasing", "random", "holds_max"]
+# (n, index of the one INT64_MIN among INT64_MAX): both sides of a thread's 16 values, of a wave's 1024, of a chunk, of the first batch
+# of chunk minima, and the very last value
+RUNMIN_SINGLE = [(2 * SM_CHUNK + 1, at) for at in (0, 15, 16, 1023, 1024, SM_CHUNK - 1, SM_CHUNK, 2 * SM_CHUNK)] + \
+                [((SM_BATCH + 1) * SM_CHUNK + 17, at) for at in (SM_CHUNK - 1, SM_CHUNK, (SM_BATCH - 1) * SM_CHUNK + SM_CHUNK - 1, SM_BATCH * SM_CHUNK,
+                                                                 (SM_BATCH + 1) * SM_CHUNK + 16)]
+
+
+def runmin_values(n, pattern, seed=0, at=None):
+    """`n` int64 values.  increasing: the first value is the minimum of every prefix - it must cross every boundary.  decreasing: every
+    value is a new minimum.  holds_max: INT64_MAX - the kernels' padding value - as data, a few other values in between.  single: one
+    INT64_MIN at `at`, INT64_MAX everywhere else."""
+    rng = np.random.default_rng(n * 3 + seed)
+    i = np.arange(n, dtype=np.int64)
+    if pattern == "increasing":
+        return i - 5
+    if pattern == "decreasing":
+        return (1 << 62) - 3 * i
+    if pattern == "random":
+        return rng.integers(INT64_MIN, INT64_MAX, n, dtype=np.int64, endpoint=True)
+    v = np.full(n, INT64_MAX, dtype=np.int64)
+    if pattern == "holds_max":
+        where = rng.random(n) < 0.002
+        where[0] = False
+        v[where] = rng.integers(INT64_MIN, INT64_MAX, int(where.sum()), dtype=np.int64, endpoint=True)
+        return v
+    if pattern == "single":
+        v[at] = INT64_MIN
+        return v
+    raise AssertionError(pattern)
+
+
+def runmin_reference(v):
+    return np.minimum.accumulate(v)
+
+
+def runmin_reference_loop(v):
+    out, m = [], None
+    for x in v:
+        m = int(x) if m is None or int(x) < m else m
+        out.append(m)
+    return out
+
+
+def runmin_cases():
+    return [(n, p, None) for n in RUNMIN_SIZES for p in RUNMIN_PATTERNS] + [(n, "single", at) for n, at in RUNMIN_SINGLE]
+
+
+# ---- merge of group rows ----------------------------------------------------------------------------------------------------------------
+MERGE_SIZES = [1, 2, 255, 256, 257, 100_003]
+MERGE_GROUPINGS = ["one", "distinct", "three", "random"]
+MERGE_KEYSETS = ["bigint", "int_date", "bool_char1", "char12", "varchar12", "char11_varchar20", "composite"]
+MERGE_ACCSETS = ["small", "wrap", "extremes"]
+_MERGE_KEYS = {      # (type tag, len) of every key; a string takes ceil(len / 8) table words
+    "bigint": [(T_BIGINT, 0)], "int_date": [(T_INT, 0), (T_DATE, 0)], "bool_char1": [(T_BOOL, 0), (T_CHAR, 1)], "char12": [(T_CHAR, 12)],
+    "varchar12": [(T_VARCHAR, 12)], "char11_varchar20": [(T_CHAR, 11), (T_VARCHAR, 20)], "composite": [(T_BIGINT, 0), (T_INT, 0), (T_CHAR, 11)]}
+_MERGE_ACCS = {"small": [0], "wrap": [0, 0, 2, 3], "extremes": [2, 3, 0]}      # merge kinds: 0 wrapping sum, 2 min, 3 max
+
+
+def _key_words(length):
+    return (length + 7) // 8 if length > 1 else 1
+
+
+def _string_words(rng, g, length, is_char):
+    """[n, words] int64 holding one spelling per row of group g's string: the group's text, then - row by row - some trailing spaces, a
+    NUL and random bytes behind it (equal for CHAR, different strings for VARCHAR unless the spaces agree), or the text padded with
+    spaces to the full length (CHAR only); every fourth group's text fills the whole length (not group 0: "one group" keeps its spellings).  The bytes behind `length` in the last
+    word are random in every row."""
+    n, words = len(g), _key_words(length)
+    b = rng.integers(0, 256, (n, words * 8), dtype=np.uint8)
+    spaces = rng.integers(0, length + 1, n)
+    for r in range(n):
+        text = b"k%d" % g[r]
+        if g[r] % 4 == 3:
+            text = (text + b"x" * length)[:length]
+        end = min(length, len(text) + int(spaces[r]))
+        b[r, :len(text)] = np.frombuffer(text, dtype=np.uint8)
+        b[r, len(text):end] = 32
+        if end < length and not (is_char and spaces[r] % 3 == 0):
+            b[r, end] = 0
+        elif end < length:
+            b[r, end:length] = 32
+    return b.view(np.int64).reshape(n, words)
+
+
+class MergeCase:
+    """group rows [first row | table words | accumulators] of `n` rows "of several shards, back to back".  grouping: one - all rows one
+    group; distinct - as many groups as the key set has values for; three - every group has exactly three members, one in each third
+    of the rows, the smallest first row in the first, second, third member in turn; random - about four members per group."""
+
+    def __init__(self, n, grouping, keyset, accset, seed=0):
+        rng = np.random.default_rng(n * 17 + MERGE_GROUPINGS.index(grouping) * 5 + MERGE_KEYSETS.index(keyset) + seed * 1000)
+        self.n, self.grouping, self.keyset, self.accset = n, grouping, keyset, accset
+        third = n // 3
+        if grouping == "one":
+            g = np.zeros(n, dtype=np.int64)
+        elif grouping == "distinct" or (grouping == "three" and third == 0):
+            g = rng.permutation(n).astype(np.int64)
+        elif grouping == "three":      # (the n % 3 rows behind the three shards are groups of their own)
+            g = np.concatenate([rng.permutation(third), rng.permutation(third), rng.permutation(third), third + np.arange(n - 3 * third)]).astype(np.int64)
+        else:
+            g = rng.integers(0, n // 4 + 1, n).astype(np.int64)
+        first = rng.permutation(n).astype(np.int64) * 3 + 1          # unique
+        if grouping == "three" and third:      # member (g % 3) of group g gets the smallest of the group's three first rows
+            shard = np.minimum(np.arange(n) // third, 3)
+            members = np.argsort(g[:3 * third], kind="stable").reshape(third, 3)          # row indices of a group's members, shard by shard
+            f = np.sort(first[members], axis=1)
+            for grp in range(third):
+                order = [1, 2, 2]
+                order.insert(grp % 3, 0)
+                first[members[grp]] = f[grp][order[:3]]
+            assert (shard[members] == [0, 1, 2]).all()
+        cols, self.keys, word = [first.reshape(n, 1)], [], 1
+        for tag, length in _MERGE_KEYS[keyset]:
+            self.keys.append((word, tag, length))
+            junk = rng.integers(INT64_MIN, INT64_MAX, n, dtype=np.int64)
+            if length > 1:
+                cols.append(_string_words(rng, g, length, tag == T_CHAR))
+            elif tag == T_BIGINT:
+                cols.append(((g + 1) * np.int64(0x9E3779B97F4A7C15 - (1 << 64))).reshape(n, 1))          # (wraps; odd multiplier: injective)
+            elif tag in (T_INT, T_DATE):      # the low 32 bits are the key, the upper 32 random
+                low = (g * 40503 + (0 if tag == T_INT else g // 7)) & 0xffffffff
+                cols.append(((junk & ~np.int64(0xffffffff)) | low).reshape(n, 1))
+            else:                             # BOOL / CHAR(1): the low byte is the key, the upper seven random
+                low = (g & 1) if tag == T_BOOL else 33 + (g >> 1) % 90
+                cols.append(((junk & ~np.int64(0xff)) | low).reshape(n, 1))
+            word += _key_words(length)
+        self.n_tab = word - 1
+        self.accs = []
+        for kind in _MERGE_ACCS[accset]:
+            self.accs.append((word, kind))
+            if accset == "small":
+                a = rng.integers(-1000, 1000, n, dtype=np.int64)
+            elif accset == "wrap":            # two members are enough to pass INT64_MAX (or INT64_MIN)
+                a = rng.choice(np.array([INT64_MAX, INT64_MAX // 2 + 1, INT64_MIN, INT64_MIN // 2 - 1, 1, -1], dtype=np.int64), n)
+            else:
+                a = rng.integers(INT64_MIN, INT64_MAX, n, dtype=np.int64, endpoint=True)
+                a[rng.random(n) < 0.2] = INT64_MIN
+                a[rng.random(n) < 0.2] = INT64_MAX
+            cols.append(a.reshape(n, 1))
+            word += 1
+        self.stride = word
+        self.rows = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype=np.int64)
+        assert self.rows.shape == (n, 1 + self.n_tab + len(self.accs))
+
+
+def _merge_normalised(rows, keys):
+    """[n, bytes] uint8: the key of every row as mergeGroupRows compares it - INT / DATE 4 bytes, BOOL / CHAR(1) one, other numbers 8; a
+    string cut at its NUL, CHAR(n) without trailing spaces, as (length, bytes zeroed behind the length)"""
+    n, parts = len(rows), []
+    for word, tag, length in keys:
+        if length > 1:
+            b = np.ascontiguousarray(rows[:, word:word + _key_words(length)]).view(np.uint8).reshape(n, -1)[:, :length]
+            nul = b == 0
+            ln = np.where(nul.any(axis=1), nul.argmax(axis=1), length)
+            if tag == T_CHAR:
+                inside = np.arange(length)[None, :] < ln[:, None]
+                keep = inside & (b != 32)
+                ln = np.where(keep.any(axis=1), length - keep[:, ::-1].argmax(axis=1), 0)
+            parts.append(np.where(np.arange(length)[None, :] < ln[:, None], b, 0).astype(np.uint8))
+            parts.append(ln.astype(np.uint8).reshape(n, 1))
+        else:
+            width = 4 if tag in (T_INT, T_DATE) else 1 if tag in (T_BOOL, T_CHAR) else 8
+            parts.append(np.ascontiguousarray(rows[:, word:word + 1]).view(np.uint8).reshape(n, 8)[:, :width])
+    return np.ascontiguousarray(np.concatenate(parts, axis=1)) if parts else np.zeros((n, 1), dtype=np.uint8)
+
+
+def merge_reference(rows, n_tab, keys, accs):
+    """one row per group - [min of the first rows | table words of the member with that first row | accumulators merged] - sorted by
+    word 0"""
+    n, stride = rows.shape
+    if n == 0:
+        return rows.copy()
+    norm = _merge_normalised(rows, keys)
+    _, inv = np.unique(norm.view(np.dtype((np.void, norm.shape[1]))).reshape(n), return_inverse=True)
+    inv = inv.reshape(n)
+    groups = int(inv.max()) + 1
+    first = np.full(groups, INT64_MAX, dtype=np.int64)
+    np.minimum.at(first, inv, rows[:, 0])
+    best = np.flatnonzero(rows[:, 0] == first[inv])
+    assert len(best) == groups, "first rows must be unique"
+    out = np.zeros((groups, stride), dtype=np.int64)
+    out[inv[best], :1 + n_tab] = rows[best, :1 + n_tab]
+    for word, kind in accs:
+        if kind == 0:
+            acc = np.zeros(groups, dtype=np.uint64)
+            np.add.at(acc, inv, rows[:, word].view(np.uint64))          # (uint64: wraps like the engine's int64 sum)
+            out[:, word] = acc.view(np.int64)
+        else:
+            acc = np.full(groups, INT64_MAX if kind == 2 else INT64_MIN, dtype=np.int64)
+            (np.minimum if kind == 2 else np.maximum).at(acc, inv, rows[:, word])
+            out[:, word] = acc
+    return out[np.argsort(out[:, 0], kind="stable")]
+
+
+def merge_reference_loop(rows, n_tab, keys, accs):
+    """the same row by row: a dict from the normalised key tuple to [min first row, table words of that member, accumulators]"""
+    def signed(x):
+        x &= U64
+        return x - (1 << 64) if x >> 63 else x
+    table = {}
+    for r in rows:
+        r = [int(x) for x in r]
+        key = []
+        for word, tag, length in keys:
+            if length > 1:
+                raw = b"".join((r[word + w] & U64).to_bytes(8, "little") for w in range(_key_words(length)))[:length]
+                s = raw.split(b"\0")[0]
+                key.append(s.rstrip(b" ") if tag == T_CHAR else s)
+            else:
+                key.append(r[word] & (0xffffffff if tag in (T_INT, T_DATE) else 0xff if tag in (T_BOOL, T_CHAR) else U64))
+        key = tuple(key)
+        if key not in table:
+            table[key] = list(r)
+            continue
+        g = table[key]
+        if r[0] < g[0]:
+            g[:1 + n_tab] = r[:1 + n_tab]
+        for word, kind in accs:
+            g[word] = signed(g[word] + r[word]) if kind == 0 else min(g[word], r[word]) if kind == 2 else max(g[word], r[word])
+    return sorted(table.values())
+
+
+def merge_cases():
+    """(n, grouping, key set, accumulator set): every small size with every grouping and key set; 100 003 rows with every grouping of
+    BIGINT keys and with three shards of every other key set.  The accumulator sets take turns."""
+    out = []
+    for n in MERGE_SIZES:
+        for grouping in MERGE_GROUPINGS:
+            for keyset in MERGE_KEYSETS:
+                if n == 100_003 and keyset != "bigint" and grouping != "three":
+                    continue
+                out.append((n, grouping, keyset, MERGE_ACCSETS[len(out) % len(MERGE_ACCSETS)]))
+    return out
+
+
+# ---- ORDER BY ... LIMIT pre-selection -----------------------------------------------------------------------------------------------------
+TOPK_SIZES = [1, 255, 256, 257, 2047, 2049, 600_001]          # 600 001: more than one sweep of a 256-workgroup grid (65 536 rows)
+TOPK_KINDS = ["random64", "random32", "equal", "minmax", "low9", "top11", "ties"]
+TOPK_ID_STEP, TOPK_ID_BASE = 7, 13                            # row i carries the id 13 + 7 i in the word behind its key
+
+
+def topk_image(words, is32, desc):
+    """aot_kernels.hip topk_image: the key (is32: its low 32 bits, sign-extended) with the sign bit flipped, complemented for ascending
+    order - "earlier in the requested order" is "larger" """
+    v = np.asarray(words, dtype=np.int64)
+    if is32:
+        v = v.astype(np.int32).astype(np.int64)
+    u = v.view(np.uint64) ^ np.uint64(1 << 63)
+    return u if desc else ~u
+
+
+def topk_image_loop(w, is32, desc):
+    w = int(w)
+    if is32:
+        w &= 0xffffffff
+        w -= (w >> 31) << 32
+    u = (w & U64) ^ (1 << 63)
+    return u if desc else u ^ U64
+
+
+def topk_range_shift(hi, lo):
+    """k_topk_range_hist: hi > lo ? clz(hi - lo) : 0"""
+    return 64 - (int(hi) - int(lo)).bit_length() if int(hi) > int(lo) else 0
+
+
+def topk_range_digit(u, lo, shift):
+    """aot_kernels.hip topk_range_digit: ((u - lo) << shift) >> 53 in 64 bits - below 2048 whatever the range"""
+    with np.errstate(over="ignore"):
+        return ((np.asarray(u, dtype=np.uint64) - np.uint64(lo)) << np.uint64(shift)) >> np.uint64(53)
+
+
+def topk_range_digit_loop(u, lo, shift):
+    return ((((int(u) - int(lo)) & U64) << shift) & U64) >> 53
+
+
+def topk_exact_range(images):
+    """(largest image, ~smallest image): what compactEntries collects into the scratch"""
+    return (int(images.max()), int(images.min()) ^ U64) if len(images) else (0, 0)
+
+
+def topk_wider_range(rng2):
+    """a range that reaches half way to both ends of the 64 bits beyond the data's"""
+    hi, lo = rng2[0], rng2[1] ^ U64
+    return hi + (U64 - hi) // 2, (lo - lo // 2) ^ U64
+
+
+def topk_reference(images, want):
+    """form 0: the indices of the rows whose image is at or above the want-th largest - every row when there are fewer than `want`"""
+    if want > len(images):
+        return np.arange(len(images))
+    t = np.partition(images, len(images) - want)[len(images) - want]
+    return np.flatnonzero(images >= t)
+
+
+def topk_reference_loop(images, want):
+    s = sorted((int(x) for x in images), reverse=True)
+    return [i for i, x in enumerate(images) if want > len(s) or int(x) >= s[want - 1]]
+
+
+def topk_range_reference(images, want, rng2):
+    """form 1: the rows in the bin of the want-th largest image and in every bin above it (bins of topk_range_digit over the range given,
+    rng2 = (hi, ~lo)); every row when there are fewer than `want`"""
+    hi, lo = rng2[0], rng2[1] ^ U64
+    d = topk_range_digit(images, lo, topk_range_shift(hi, lo))
+    at_or_above = np.cumsum(np.bincount(d.astype(np.int64), minlength=TOPK_BINS)[::-1])[::-1]          # rows in bins >= b
+    ok = np.flatnonzero(at_or_above >= want)
+    return np.flatnonzero(d >= (ok[-1] if len(ok) else 0))
+
+
+def topk_range_reference_loop(images, want, rng2):
+    hi, lo = rng2[0], rng2[1] ^ U64
+    shift = topk_range_shift(hi, lo)
+    d = [topk_range_digit_loop(u, lo, shift) for u in images]
+    assert all(0 <= x < TOPK_BINS for x in d)
+    hist = [0] * TOPK_BINS
+    for x in d:
+        hist[x] += 1
+    b, above = 0, 0
+    for cand in range(TOPK_BINS - 1, -1, -1):          # the highest bin with `want` rows in it and above it
+        above += hist[cand]
+        if above >= want:
+            b = cand
+            break
+    return [i for i, x in enumerate(d) if x >= b]
+
+
+class TopkCase:
+    """rows [n, stride] of random words with the sort key in word key_word and the row's id in the word behind it (cyclically).  kinds:
+    random32 - the key is the low 32 bits, negative values among them, the upper 32 random; equal - one image (hi == lo); minmax - only
+    INT64_MIN and INT64_MAX (a full 64-bit span: shift 0); low9 / top11 - keys that differ in their low 9 / top 11 bits only (the
+    threshold is decided by the last / first digit of the radix select); ties - 5 rows above a value that 300 rows share."""
+
+    def __init__(self, n, kind, want, stride=2, key_word=0, desc=True, capacity=None, rows_upper_bound=None, overflow=False, seed=0):
+        rng = np.random.default_rng(n * 19 + TOPK_KINDS.index(kind) * 3 + stride + seed * 1000)
+        self.n, self.kind, self.want, self.stride, self.key_word, self.desc = n, kind, want, stride, key_word, desc
+        self.is32 = kind == "random32"
+        self.capacity = n + 1 if capacity is None else capacity
+        self.rows_upper_bound, self.overflow = rows_upper_bound, overflow
+        if kind == "random64":
+            k = rng.integers(INT64_MIN, INT64_MAX, n, dtype=np.int64, endpoint=True)
+        elif kind == "random32":
+            k = rng.integers(-(1 << 31), 1 << 31, n, dtype=np.int64) & 0xffffffff | rng.integers(INT64_MIN, INT64_MAX, n, dtype=np.int64) & ~np.int64(0xffffffff)
+        elif kind == "equal":
+            k = np.full(n, -123456789, dtype=np.int64)
+        elif kind == "minmax":
+            k = np.where(rng.integers(0, 2, n) == 1, INT64_MAX, INT64_MIN).astype(np.int64)
+        elif kind == "low9":
+            k = np.int64(0x1234567890abc000) + rng.integers(0, 512, n, dtype=np.int64)
+        elif kind == "top11":
+            k = (rng.integers(0, 2048, n, dtype=np.uint64) << np.uint64(53) | np.uint64(0x000fedcba9876543)).view(np.int64)
+        elif kind == "ties":
+            assert n >= 400
+            k = rng.integers(-1000, 1000, n, dtype=np.int64)
+            where = rng.permutation(n)
+            k[where[:300]] = 5000 if desc else -5000
+            k[where[300:305]] = (6000 if desc else -6000) + np.arange(5) * (1 if desc else -1)
+        else:
+            raise AssertionError(kind)
+        self.rows = rng.integers(INT64_MIN, INT64_MAX, (n, stride), dtype=np.int64)
+        self.rows[:, key_word] = k
+        self.rows[:, (key_word + 1) % stride] = TOPK_ID_BASE + TOPK_ID_STEP * np.arange(n, dtype=np.int64)
+
+    @property
+    def id_word(self):
+        return (self.key_word + 1) % self.stride
+
+    def seen(self):
+        """the rows the kernels take: min(n_rows, rows_upper_bound)"""
+        return self.n if self.rows_upper_bound is None else min(self.n, self.rows_upper_bound)
+
+    def images(self):
+        return topk_image(self.rows[:self.seen(), self.key_word], self.is32, self.desc)
+
+    def name(self):
+        return (f"n{self.n}_{self.kind}_want{self.want}_s{self.stride}k{self.key_word}_{'desc' if self.desc else 'asc'}"
+                + (f"_bound{self.rows_upper_bound}" if self.rows_upper_bound is not None else "") + ("_overflow" if self.overflow else ""))
+
+
+def topk_cases():
+    out = []
+    for j, n in enumerate(TOPK_SIZES):          # every size with want = 1, n - 1, n, n + 1, ascending and descending in turn
+        for i, want in enumerate(sorted({1, n - 1, n, n + 1} - {0})):
+            out.append(TopkCase(n, "random64", want, stride=2, key_word=(i + j) % 2, desc=(i + j) % 2 == 0))
+    for n in (257, 2049):                       # every kind of key in both orders, a few, some and all rows wanted
+        for kind in TOPK_KINDS:
+            if kind == "ties":
+                continue
+            for desc in (True, False):
+                for want in (1, 100, n):
+                    out.append(TopkCase(n, kind, want, stride=3, key_word=2, desc=desc))
+    for stride, key_word in [(2, 0), (2, 1), (3, 1), (9, 0), (9, 4), (9, 8)]:          # the key in the first, a middle and the last word
+        for kind in ("random64", "random32"):
+            out.append(TopkCase(2049, kind, 40, stride=stride, key_word=key_word, desc=stride != 3))
+    out.append(TopkCase(600_001, "random32", 1000, stride=3, key_word=1, desc=False))
+    out.append(TopkCase(600_001, "low9", 50_000, stride=2, key_word=1, desc=True))
+    for desc in (True, False):                  # the tie set at the threshold: inside the capacity, and larger than it
+        out.append(TopkCase(2049, "ties", 10, stride=3, key_word=0, desc=desc))
+        out.append(TopkCase(2049, "ties", 10, stride=3, key_word=0, desc=desc, capacity=100, overflow=True))
+    out.append(TopkCase(600_001, "equal", 7, stride=2, key_word=0, capacity=1000, overflow=True))
+    for n, bound in [(2049, 1000), (2049, 2048), (2049, 2050), (2049, 1 << 31), (600_001, 70_000), (257, 0)]:      # below and above n_rows
+        out.append(TopkCase(n, "random64", 33, stride=2, key_word=1, desc=True, rows_upper_bound=bound))
+    return out

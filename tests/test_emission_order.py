@@ -34,6 +34,8 @@ CASES = [
     (50_000, 2, "identical-runs"),      # runs of identical hashes (Values::hash is symmetric in its keys)
     (40_000, 2, "end-heavy"),           # homes near the table's end: clusters wrap around
     (1_300_000, 1_200_000, "random"),   # the 10 B-row shard's shape: 2 M slots, one growth
+    (1_300_000, 2_000_000, "random"),   # 4 026 031 slots at once: 1 966 chunks of the running minimum, a second batch of chunk minima
+    (1_250_000, 2, "random"),           # ... and the same level reached through every growth from 5 slots
 ]
 
 
