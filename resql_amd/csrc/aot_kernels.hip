@@ -89,7 +89,7 @@ static void hostStats(Table& t) {
 // narrow images (frame of reference + byte width): what the generated scans read instead of the wide column
 // ------------------------------------------------------------------------------------------------
 int narrowWidth(const TableColumn& c) {
-    if (!narrowScansEnabled()) return 0;
+    if (!sw::flag<sw::RSQ_NARROW_SCANS>()) return 0;
     if (!c.owned || !c.dptr || !c.stats.valid || c.type.isString()) return 0;
     const int tag = c.type.tag;
     if (tag != RSQ_INT && tag != RSQ_BIGINT && tag != RSQ_DECIMAL && tag != RSQ_DATE) return 0;
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) k_dict_encode(const unsigned char* __rest
 }
 
 static bool dictCandidate(const Table& t, const TableColumn& c) {
-    if (!dictScansEnabled() || t.derived || t.nRows <= 0 || !c.owned || !c.dptr || !c.type.isString()) return false;
+    if (!sw::dictScansEnabled() || t.derived || t.nRows <= 0 || !c.owned || !c.dptr || !c.type.isString()) return false;
     return !(c.type.tag == RSQ_CHAR && c.type.len == 1);          // (CHAR(1) keeps its byte set)
 }
 

@@ -154,7 +154,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     strPrefetch.clear(); strPrefetchWidth.clear(); strStaged.clear(); strStagedBytes = 0; postTile.clear(); foldTile.clear(); eg.strWordVars.clear();
     eg.symbols.clear();
     o->schema.clear();
-    const bool narrowScans = narrowScansEnabled();
+    const bool narrowScans = sw::flag<sw::RSQ_NARROW_SCANS>();
     for (size_t ci = 0; ci < t->cols.size(); ci++) {
         const TableColumn& c = t->cols[ci];
         // Values::dematerialize(..., required): an empty request set means all attributes
@@ -175,7 +175,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
         const int nw = (!t->derived && c.owned && narrowScans && !c.type.isString() && (c.nptr || q.ctx.device < 0)) ? c.nw : 0;
         colNarrow.push_back(nw);
         // ... or its dictionary image (TableColumn::dict): one byte per row, the value an rsq::Str into the dictionary
-        const bool dictCoded = !t->derived && c.owned && c.type.isString() && c.dictN > 0 && dictScansEnabled() && (c.codePtr || q.ctx.device < 0);
+        const bool dictCoded = !t->derived && c.owned && c.type.isString() && c.dictN > 0 && sw::dictScansEnabled() && (c.codePtr || q.ctx.device < 0);
         colDict.push_back(dictCoded ? c.type.len : 0);
         pipe.storedBytesPerRow += dictCoded ? 1 : nw ? nw : columnWidth(c.type);
         if (dictCoded) {
@@ -457,7 +457,7 @@ std::string Walker::stage2Code(int k) {
 }
 
 bool Walker::compactThen(OpNode* o, const std::function<void()>& downstream) {
-    if (compacted || !selective || !envInt("RSQ_COMPACT", 1, 0, 1) || downstreamMaterializes(o)) return false;
+    if (compacted || !selective || !sw::num<sw::RSQ_COMPACT>() || downstreamMaterializes(o)) return false;
     // not inside the match loop of a join probed for all matches: the queue takes ONE entry per row function call, and a row
     // with several matches would keep only its last (found with a constant build key: every build row the same key)
     if (multiMatchAbove) return false;

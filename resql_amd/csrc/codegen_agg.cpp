@@ -72,14 +72,15 @@ bool Walker::tryDenseKeys(OpNode* o) {
     q.denseKeys.clear();
     denseRefusal.clear();
     // (a statement that is not dense holds no dense keys; why: said in explain under RSQ_DICT_SCANS=2, where a string key was the obstacle)
-    auto no = [&](const std::string& why = std::string()) { q.denseKeys.clear(); if (dictJoinKeysEnabled()) denseRefusal = why; return false; };
+    const bool dictJoinKeys = sw::dictJoinKeysEnabled();
+    auto no = [&](const std::string& why = std::string()) { q.denseKeys.clear(); if (dictJoinKeys) denseRefusal = why; return false; };
     int64_t total = 1;
     for (Expr* g : o->exprs2) {
         if (g->tag != RSQ_E_ATTRIBUTE) return no(g->type.isString() ? "key " + expressionName(g) + " not by dictionary code: a computed value" : std::string());
         auto org = symbolOrigin.find(g->symbol);
         if (g->type.isString() && org != symbolOrigin.end() && org->second < -1) return no("key " + g->symbol + " not by dictionary code: a computed value");
         if (g->type.isString() && org != symbolOrigin.end() && org->second == -1 && t->derived) return no("key " + g->symbol + " not by dictionary code: a derived table holds it by value");
-        if (org != symbolOrigin.end() && org->second >= 0 && g->type.isString() && dictJoinKeysEnabled()) {
+        if (org != symbolOrigin.end() && org->second >= 0 && g->type.isString() && dictJoinKeys) {
             // A string from a join's build side (RSQ_DICT_SCANS=2): dense by the dictionary its address points into (HashTable::DictOrigin),
             // where it has one - under the conditions of a scan-own coded key below, for this scan's table and the origin's alike.  The
             // origin table must be one of the statement's, so that a rebuilt dictionary refuses it (executeQuery).
@@ -180,9 +181,9 @@ void Walker::consumeAggregation(OpNode* o, OpNode* from) {
     collectAccumulators(o);
     const int W = (int)q.accums.size();
     std::string mode;
-    const int forced = envInt("RSQ_AGG_MODE", 0, 0, 5);     // 5 = generic hash aggregation even where a dense id exists (tests)
+    const int forced = sw::num<sw::RSQ_AGG_MODE>();     // 5 = generic hash aggregation even where a dense id exists (tests)
     denseRefusal.clear();
-    if (forced == 5 && dictJoinKeysEnabled()) for (Expr* g : o->exprs2) if (g->type.isString()) denseRefusal = "no dense ids: RSQ_AGG_MODE=5";
+    if (forced == 5 && sw::dictJoinKeysEnabled()) for (Expr* g : o->exprs2) if (g->type.isString()) denseRefusal = "no dense ids: RSQ_AGG_MODE=5";
     if (!(forced == 5 && !o->exprs2.empty()) && tryDenseKeys(o)) {
         const int64_t D = q.denseGroups, cells = D * W;
         // measured on MI355X (Q1 SF10, 42 cells): registers 0.47 ms, lane-private LDS 0.71 ms
@@ -221,6 +222,7 @@ void Walker::consumeAggregation(OpNode* o, OpNode* from) {
 // looks at the slot again (see the note at the loop about keeping this safe inside one wave).
 void Walker::emitHashAggregation(OpNode* o) {
     pipe.gridPerCU = 8;
+    const bool valuesByAddress = sw::num<sw::RSQ_GROUP_VALUES_BY_ADDRESS>() != 0;
     std::unique_ptr<HashTable> ht(new HashTable());
     ht->id = (int)q.hashTables.size();
     const std::string T = "ht" + std::to_string(ht->id);
@@ -333,7 +335,7 @@ void Walker::emitHashAggregation(OpNode* o) {
     // per carried value: the kernel then addresses the table with that stride (T_nw; TPC-H Q10: 7 words instead of 32 - the million slots
     // the groups spread over are 56 MB, not 268), and with the full stride when a table of the dependency chain fell back to its hash form
     const int NWc = K + (int)carriedVals.size();
-    const bool compactLayout = aggAos && NWc < NWtab && !carriedVals.empty() && envInt("RSQ_GROUP_VALUES_BY_ADDRESS", 1, 0, 1) != 0;
+    const bool compactLayout = aggAos && NWc < NWtab && !carriedVals.empty() && valuesByAddress;
     auto aggWord = [&, NWtab, aggAos, compactLayout](int w) {
         if (aggAos && compactLayout) return "a." + T + "_words[" + T + "_s * " + T + "_nw + " + std::to_string(w) + "]";
         return aggAos ? "a." + T + "_words[" + T + "_s * " + std::to_string(NWtab) + " + " + std::to_string(w) + "]"
@@ -392,7 +394,7 @@ void Walker::emitHashAggregation(OpNode* o) {
         int nCarriedWords = 0;
         for (auto& c : carriedVals) nCarriedWords += c.nWords;
         // (strings by address: RSQ_GROUP_VALUES_BY_ADDRESS=0 copies them into the entries as before)
-        bool byAddress = nCarriedWords > 0 && envInt("RSQ_GROUP_VALUES_BY_ADDRESS", 1, 0, 1) != 0;
+        bool byAddress = nCarriedWords > 0 && valuesByAddress;
         for (auto& c : carriedVals) if (c.g->type.isString() && (NWtab > 255 || c.g->type.len >= 4096)) byAddress = false;      // (what entryDerefCode can say)
         if (byAddress) {
             // row word w of the table part of a group row <- where it stands in the entry (engine.h entryDerefCode / entryPlainCode; 0: word w itself)
@@ -626,6 +628,7 @@ void Walker::emitHashAggregation(OpNode* o) {
 // host fails the execution.
 std::string Walker::groupIdExpr() {
     std::string gid = "0";
+    const bool checkStats = sw::num<sw::RSQ_CHECK_STATS>() != 0;
     for (size_t ki = 0; ki < q.denseKeys.size(); ki++) {
         DenseKey& k = q.denseKeys[ki];
         const std::string rv = "gk" + std::to_string(ki);
@@ -649,7 +652,7 @@ std::string Walker::groupIdExpr() {
             // the rank IS the code the scan loaded: no decode, no dictionary access.  Behind a wave compaction the code travels in the
             // queue (codegen.cpp compactThen), not the rsq::Str it would decode to.
             const std::string code = inStage2 ? stage2Code(k.scanCol) : "vc_" + std::to_string(k.scanCol);
-            if (!envInt("RSQ_CHECK_STATS", 0, 0, 1)) line("const int " + rv + " = (int)(" + code + ");");
+            if (!checkStats) line("const int " + rv + " = (int)(" + code + ");");
             else {
                 line("int " + rv + " = (int)(" + code + ");");
                 line("if ((u32)" + rv + " >= " + std::to_string((long long)k.card) + "u) { atomicOr(a.err, (u32)rsq::ERR_GROUP_OVERFLOW); " + rv + " = 0; }");
@@ -662,7 +665,7 @@ std::string Walker::groupIdExpr() {
         // taken: only adopted columns pay for the checks; TPC-H Q1's kernel is 6 % slower with them)
         bool check = true;
         if (k.expr->tag == RSQ_E_ATTRIBUTE) { const int ci = pipe.src->findCol(k.expr->symbol); if (ci >= 0 && pipe.src->cols[(size_t)ci].owned) check = false; }
-        if (envInt("RSQ_CHECK_STATS", 0, 0, 1)) check = true;
+        if (checkStats) check = true;
         if (k.byteSet && !check) {
             rank = "0";
             for (size_t d = 1; d < k.values.size(); d++) {
@@ -719,7 +722,7 @@ void Walker::emitGlobalFlush(std::ostringstream& s, const std::string& count, co
 // handed to the workgroup's LDS rings; the first-row tracker is kept beside it (stage_track).  Available when the
 // record fits 128 bits and the partitions fit the rings (<= 256); the wider cases stay with form 2.
 void Walker::emitStagedScatter(int64_t D, int W, int gpp, int shift, int P) {
-    if (P > 256 || !envInt("RSQ_STAGED", 1, 0, 1) || q.accums[0].merge != 2) return;
+    if (P > 256 || !sw::num<sw::RSQ_STAGED>() || q.accums[0].merge != 2) return;
     struct Field { int w; int bits; int64_t min; bool check; int word, off; };
     std::vector<Field> fields;
     fields.push_back({-1, shift, 0, false, 0, 0});
@@ -732,7 +735,7 @@ void Walker::emitStagedScatter(int64_t D, int W, int gpp, int shift, int P) {
                 const TableColumn& c = pipe.src->cols[(size_t)ci];
                 const uint64_t range = (uint64_t)c.stats.max - (uint64_t)c.stats.min;
                 int bits = 1; while (bits < 64 && (range >> bits) != 0) bits++;
-                if (bits < 64) { f.bits = bits; f.min = c.stats.min; f.check = !c.owned || envInt("RSQ_CHECK_STATS", 0, 0, 1); }
+                if (bits < 64) { f.bits = bits; f.min = c.stats.min; f.check = !c.owned || sw::num<sw::RSQ_CHECK_STATS>(); }
             }
         }
         fields.push_back(f);
@@ -879,7 +882,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
         // the width of |value| in bits, so one plan shape keeps one kernel text across scale factors (l_extendedprice: 24 bits at
         // SF 0.01 and SF 10).  Not behind a wave compaction (stage 2 runs from the drains, not once per row and tile).
         std::vector<char> part32((size_t)W, 0);
-        if (narrowScansEnabled() && !compacted && pipe.src && !pipe.src->derived) {
+        if (sw::flag<sw::RSQ_NARROW_SCANS>() && !compacted && pipe.src && !pipe.src->derived) {
             for (int w = 1; w < W; w++) {
                 const Accum& ac = q.accums[(size_t)w];
                 if (ac.merge != 0) continue;
@@ -950,7 +953,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
             }
             closeScope();
         }
-        const bool dbgTail = envInt("RSQ_DEBUG_TAIL", 0, 0, 1) != 0;      // (measurement only: device timestamps of the epilogue's stages)
+        const bool dbgTail = sw::num<sw::RSQ_DEBUG_TAIL>() != 0;      // (measurement only: device timestamps of the epilogue's stages)
         auto stamp = [&](int k) { if (dbgTail) ep << "    if (a.dbg && threadIdx.x == 0) a.dbg[(u64)blockIdx.x * 8 + " << k << "] = (u64)wall_clock64();\n"; };
         if (dbgTail) { addArg("dbg", "u64*", 0); prologue += "    if (a.dbg && threadIdx.x == 0) a.dbg[(u64)blockIdx.x * 8 + 0] = (u64)wall_clock64();\n"; }
         stamp(1);
@@ -1086,7 +1089,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
         const int64_t P = (D + gpp - 1) / gpp;
         int shift = 0; while ((1 << shift) < gpp) shift++;
         // (not behind a nested-loops join: a record carries row - row0 in 40 bits, and a pair's ordinal is outer row x inner rows + j)
-        const bool part = P >= 2 && P <= 4096 && envInt("RSQ_PARTITION", 1, 0, 2) != 0 && !underNestedLoops();
+        const bool part = P >= 2 && P <= 4096 && sw::num<sw::RSQ_PARTITION>() != 0 && !underNestedLoops();
         if (part) {
             pipe.partitioned = true; pipe.partCount = (int)P; pipe.partGroups = gpp;
             line("#if RSQ_AGG_VARIANT == 1");

@@ -18,12 +18,6 @@ namespace cg {
 
 struct Sym { std::string var; Type type; };
 
-inline int envInt(const char* name, int def, int lo, int hi) {
-    const char* e = getenv(name);
-    int v = e ? atoi(e) : def;
-    return v < lo ? lo : v > hi ? hi : v;
-}
-
 
 // ================================================================================================
 // expressions -> device code (emitExpression, reference src/ExpressionsJitFlounder.h:1080-1114)

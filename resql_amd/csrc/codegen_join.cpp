@@ -130,7 +130,7 @@ bool Walker::isGroupKey(const std::string& name) const {
 
 HashTable::DictOrigin Walker::payloadOriginOf(const std::string& name) const {
     const HashTable::DictOrigin none;
-    if (!dictJoinKeysEnabled() || !isGroupKey(name)) return none;
+    if (!sw::dictJoinKeysEnabled() || !isGroupKey(name)) return none;
     auto org = symbolOrigin.find(name);
     if (org == symbolOrigin.end()) return none;
     if (org->second == -1) {
@@ -158,6 +158,7 @@ void Walker::consumeBuild(OpNode* o, OpNode* from) {
 
 void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
     pipe.gridPerCU = 8;
+    const bool keyBitmap = sw::num<sw::RSQ_JOIN_BITMAP>() != 0;
     std::unique_ptr<HashTable> ht(new HashTable());
     ht->id = (int)q.hashTables.size();
     ht->unique = o->singleMatch;
@@ -191,7 +192,7 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
         else { ht->payload.push_back({a.name, it->second.type}); ht->payloadOrigin.push_back(payloadOriginOf(a.name)); }
     }
     // key-domain bitmap (see HashTable): one integer key that is a column of this pipeline's scan with usable statistics
-    if (o->exprs.size() == 1 && keyVars.size() == 1 && envInt("RSQ_JOIN_BITMAP", 1, 0, 1)) {
+    if (o->exprs.size() == 1 && keyVars.size() == 1 && keyBitmap) {
         Expr* l = o->exprs[0]->child;
         auto org = symbolOrigin.find(l->symbol);
         if (l->tag == RSQ_E_ATTRIBUTE && !l->type.isString() && org != symbolOrigin.end() && org->second == -1) {
@@ -204,7 +205,7 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
         }
     }
     // ... or, for a table with several key words, a bitmap over ONE integer component (HashTable::hasCompBitmap)
-    if (!ht->hasBitmap && keyVars.size() > 1 && envInt("RSQ_JOIN_BITMAP", 1, 0, 1))
+    if (!ht->hasBitmap && keyVars.size() > 1 && keyBitmap)
         for (size_t ki = 0; ki < o->exprs.size() && !ht->hasCompBitmap; ki++) {
             Expr* l = o->exprs[ki]->child;
             auto org = symbolOrigin.find(l->symbol);
@@ -242,7 +243,7 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
     // (A join probed for ALL matches qualifies too: with unique build keys every probe has at most one.  If such a table carries
     // nothing but its key - TPC-H Q3's customer side - the bitmap IS the table in the rank form: a KEY SET, no entries at all.)
     ht->rankCapable = (ht->unique || 1) && ht->hasBitmap && ht->keyCas && ht->aos && keyVars.size() == 1 &&
-                      envInt("RSQ_JOIN_RANK", 1, 0, 1) != 0;
+                      sw::num<sw::RSQ_JOIN_RANK>() != 0;
     ht->setOnly = ht->rankCapable && !ht->unique && ht->payload.empty();
     // IDENTITY: the build pipeline is the bare scan of a table in the order of its (engine-owned, hence immutable) key column.  If the
     // sizing pass then finds the keys unique and every row inserted, entry number rank(key) IS the row's number: the build writes
@@ -284,7 +285,7 @@ void Walker::consumeBuildBody(OpNode* o, OpNode* from) {
     bool checkKey = true, combineBits = false;
     if (ht->hasBitmap && o->exprs[0]->child->tag == RSQ_E_ATTRIBUTE) {
         const int ci = pipe.src->findCol(o->exprs[0]->child->symbol);
-        if (ci >= 0 && pipe.src->cols[(size_t)ci].owned && !envInt("RSQ_CHECK_STATS", 0, 0, 1)) checkKey = false;      // (engine-owned columns cannot change)
+        if (ci >= 0 && pipe.src->cols[(size_t)ci].owned && !sw::num<sw::RSQ_CHECK_STATS>()) checkKey = false;      // (engine-owned columns cannot change)
         // a table scanned in the order of its build key (column statistics): the rows of a wave fall into a few bitmap words, and
         // the lanes that meet in one word set their bits with ONE atomic (rsq_device.h bm_set_combined).  Memory-side atomics
         // run at ~25 G/s chip-wide: a build over all 15 M orders (TPC-H Q12) spent 0.6 of its 0.73 ms on them.

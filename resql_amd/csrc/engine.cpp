@@ -530,7 +530,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     double t0 = nowMs();
     std::unique_ptr<Query> q(new Query(ctx));
     int hits0 = ctx.jitCacheHits, comp0 = ctx.jitCompiles;
-    q->maxGrid = maxGridSetting();
+    q->maxGrid = (unsigned)sw::num<sw::RSQ_MAX_GRID>();
     for (int i = 0; i < nTables; i++) {
         Table* t = reinterpret_cast<Table*>(tables[i]);
         if (!t) failInvalid("null table");
@@ -561,11 +561,11 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     // A plan shape whose specialised kernels are not in the code-object cache starts on the pre-compiled generic pipeline
     // (generic.cpp) while hiprtc builds them on a host thread; RSQ_FORCE_GENERIC=1 keeps every eligible plan there (tests),
     // RSQ_GENERIC=0 restores the blocking compile.
-    const bool forceGeneric = getenv("RSQ_FORCE_GENERIC") && atoi(getenv("RSQ_FORCE_GENERIC")) != 0;
-    const bool allowGeneric = ctx.device >= 0 && !(getenv("RSQ_GENERIC") && atoi(getenv("RSQ_GENERIC")) == 0);
+    const bool forceGeneric = sw::flag<sw::RSQ_FORCE_GENERIC>();
+    const bool allowGeneric = ctx.device >= 0 && sw::flag<sw::RSQ_GENERIC>();
     bool cached = true;
     if (allowGeneric) for (const std::string& src : kernelSources(*q)) cached = cached && ctx.kernelCached(src);
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace] compile: code-object cache looked up at +%.3f ms\n", nowMs() - tBuilt);
+    traceLine("[rsq trace] compile: code-object cache looked up at +%.3f ms\n", nowMs() - tBuilt);
     if (allowGeneric && (forceGeneric || !cached)) {
         std::string why, why2;
         bool ok = buildGenericProgram(*q, q->generic, why);
@@ -574,11 +574,11 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
             RSQ_HIP(hipMemcpy(q->dGenericCode, q->generic.code.data(), q->generic.code.size() * sizeof(GenericInstr), hipMemcpyHostToDevice));
             q->explainText += "generic pre-compiled pipeline (" + std::to_string(q->generic.code.size()) + " instructions, " + std::to_string(q->generic.cols.size()) +
                               " columns)" + (forceGeneric ? " forced" : " until hiprtc has built the specialised kernel") + "\n";
-        } else if (!(getenv("RSQ_GENERIC2") && atoi(getenv("RSQ_GENERIC2")) == 0) && buildGenericPlan(*q, q->generic2Progs, why2)) {
+        } else if (sw::flag<sw::RSQ_GENERIC2>() && buildGenericPlan(*q, q->generic2Progs, why2)) {
             // joins, strings, hash aggregation, materialisation: the interpreter for whole pipelines, one program per pipeline
             ok = true; q->generic2 = true;
             size_t instr = 0;
-            if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace] compile: interpreter programs built at +%.3f ms\n", nowMs() - tBuilt);
+            traceLine("[rsq trace] compile: interpreter programs built at +%.3f ms\n", nowMs() - tBuilt);
             for (auto& gp : q->generic2Progs) {
                 instr += gp.code.size();
                 gp.dCode = (GenericInstr*)ctx.alloc(std::max<size_t>(1, gp.code.size()) * sizeof(GenericInstr));
@@ -589,10 +589,10 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
                 if (!gp.constPool.empty()) RSQ_HIP(hipMemcpy(gp.dConstPool, gp.constPool.data(), gp.constPool.size(), hipMemcpyHostToDevice));
             }
             for (auto& h : q->hashTables) q->savedAos.push_back(h->aos);
-            if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace] compile: interpreter programs on the device at +%.3f ms\n", nowMs() - tBuilt);
+            traceLine("[rsq trace] compile: interpreter programs on the device at +%.3f ms\n", nowMs() - tBuilt);
             q->explainText += "generic pre-compiled interpreter for " + std::to_string(q->generic2Progs.size()) + " pipeline(s) (" + std::to_string(instr) +
                               " instructions)" + (forceGeneric ? " forced" : " until hiprtc has built the specialised kernels") + "\n";
-        } else if (!why2.empty() && getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace] not interpreted: %s\n", why2.c_str());
+        } else if (!why2.empty()) traceLine("[rsq trace] not interpreted: %s\n", why2.c_str());
         if (ok) {
             q->genericActive = true; q->genericForced = forceGeneric;
             if (!cached) {
@@ -626,8 +626,8 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     }
     const double tGeneric = nowMs();
     if (!q->genericActive) resolveKernels(*q);
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace] compile: typing %.3f ms, pipelines + kernel text %.3f ms, cache lookup + interpreter programs %.3f ms, kernels %.3f ms\n",
-                                     tBuilt0 - t0, tBuilt - tBuilt0, tGeneric - tBuilt, nowMs() - tGeneric);
+    traceLine("[rsq trace] compile: typing %.3f ms, pipelines + kernel text %.3f ms, cache lookup + interpreter programs %.3f ms, kernels %.3f ms\n",
+              tBuilt0 - t0, tBuilt - tBuilt0, tGeneric - tBuilt, nowMs() - tGeneric);
     for (auto& p : q->pipelines) {
         q->allSource += p.source + "\n";
         q->explainText += p.explain + "\n";
@@ -748,8 +748,7 @@ static void ensureHostGroupRows(Query& q, size_t words) {
 
 // a single register-mode pipeline: its kernel carries the whole step (codegen.cpp, "The step in ONE launch")
 static bool fusedEligible(const Query& q) {
-    const bool off = getenv("RSQ_FUSED_STEP") && atoi(getenv("RSQ_FUSED_STEP")) == 0;
-    return !off && q.aggMode == AggMode::DENSE_REG && q.pipelines.size() == 1 && q.pipelines[0].sink == SinkKind::AGGREGATE &&
+    return sw::flag<sw::RSQ_FUSED_STEP>() && q.aggMode == AggMode::DENSE_REG && q.pipelines.size() == 1 && q.pipelines[0].sink == SinkKind::AGGREGATE &&
            !q.pipelines[0].partitioned && q.dFinTicket != nullptr;
 }
 
@@ -885,9 +884,8 @@ static void runSubQueries(Query& q) {
     for (DerivedState& d : q.derived) {              // (the interpreters decline plans over derived tables: generic*.cpp)
         if (!d.sub.external) {
             buildDerived(q, d);
-            if (getenv("RSQ_TRACE"))
-                fprintf(stderr, "[rsq trace] %s: %lld rows written from the %s tail's tuples\n", d.table->name.c_str(), (long long)d.table->nRows,
-                        d.sub.query->resultInPinned && d.sub.query->resultDev ? "device" : "host");
+            traceLine("[rsq trace] %s: %lld rows written from the %s tail's tuples\n", d.table->name.c_str(), (long long)d.table->nRows,
+                      d.sub.query->resultInPinned && d.sub.query->resultDev ? "device" : "host");
         }
         account(d.sub);
     }
@@ -975,32 +973,16 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     }
     const bool interp = q.genericActive && q.generic2;      // this execution's pipelines run on the interpreter for whole pipelines
     q.flatRun = (partialOnly || interp) && q.aggPad > 1;      // (the interpreter aggregates into the unpadded table)
-    const bool trace0 = getenv("RSQ_TRACE") != nullptr;
+    const sw::Level traceLevel = sw::level<sw::RSQ_TRACE>();
+    const bool trace = traceLevel.on;      // per-pipeline wall time (synchronises after each one)
     uint32_t topkCapacity = 0, topkSpec = 0;      // > 0: this execution pre-selects ORDER BY ... LIMIT candidates on the device
     bool topkRange = false;                       // ... with the short form (one histogram over the images' range)
     uint32_t groupRowsAllocated = 0;              // rows the group-row buffers of this execution can take
     uint64_t selectSeq = 0;                       // ... announced by this sequence number in pinned word 4
     bool selectPublished = false;                 // ... and the selection's launch has delivered candidates and status words to the host
     bool narrowRows = false;                      // ... from narrow group rows [slot | sort key]: q.dGroupRows was NOT written by this execution
-    auto ensureCandHost = [&]() {        // coherent pinned rows for topkCapacity candidates, and the device's view of them
-        const size_t need = (size_t)topkCapacity * (size_t)q.groupRowWords;
-        if (q.hCandRowsWords >= need && q.dHostCandRows) return;
-        if (q.hCandRows) ctx.freePinned(q.hCandRows);
-        q.hCandRows = nullptr; q.dHostCandRows = nullptr; q.hCandRowsWords = 0;
-        q.hCandRows = (int64_t*)ctx.allocPinned(std::max<size_t>(need, 8) * 8);
-        q.hCandRowsWords = need;
-        void* dv = nullptr;
-        if (hipHostGetDevicePointer(&dv, q.hCandRows, 0) == hipSuccess && dv) q.dHostCandRows = (int64_t*)dv; else (void)hipGetLastError();
-    };
-    auto fusedSelectOk = [&]() {
-        const bool off = getenv("RSQ_FUSED_SELECT") && atoi(getenv("RSQ_FUSED_SELECT")) == 0;
-        const bool publish = q.dPinnedDev && !(getenv("RSQ_PUBLISH_STATUS") && atoi(getenv("RSQ_PUBLISH_STATUS")) == 0);
-        if (off || q.fusedSelectOff || !publish || partialOnly || async || getenv("RSQ_TRACE")) return false;
-        ensureCandHost();
-        return q.dHostCandRows != nullptr;
-    };
     // ---- the step in one launch: a single register-mode pipeline whose last workgroup publishes the table ----
-    if (fusedEligible(q) && !trace0 && !interp) {
+    if (fusedEligible(q) && !trace && !interp) {
         Pipeline& p = q.pipelines[0];
         // the kernel leaves its working table, the error word and the ticket at their identities; make them so the first
         // time, after an execution that did not come back (an exception between launch and synchronisation), and whenever
@@ -1011,7 +993,6 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
             RSQ_HIP(hipMemsetAsync(ctx.dErr, 0, 4, ctx.stream));
             ctx.errWordClean = true;
         }
-        static const bool stepTrace0 = getenv("RSQ_TRACE") && atoi(getenv("RSQ_TRACE")) >= 2;
         // a step that runs to its end here takes the next pair of the event ring (read when somebody asks, or when the ring is
         // full); an asynchronous partial step keeps the single pair finalize / settle read
         const bool ringEvents = !(async && partialOnly);
@@ -1028,8 +1009,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         } else resolveKernelTime(q);                           // the previous step's events, before they are recorded again
         q.fusedReady = false;
         q.flatRun = false;                                     // always the padded kernel: the last workgroup unpads
-        const bool pollOk = !(getenv("RSQ_POLL") && atoi(getenv("RSQ_POLL")) == 0);
-        const bool poll = pollOk && !partialOnly;
+        const bool poll = sw::flag<sw::RSQ_POLL>() && !partialOnly;
         const uint64_t seq = poll ? ++q.finSeqCounter : 0;
         q.finSeq = seq;
         q.finOut = partialOnly ? q.dAgg : q.dFinHost;          // device partial table | host-mapped pinned read-back buffer
@@ -1037,28 +1017,14 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         if (!q.gev0) { q.gev0 = ctx.takeEvent(); q.gev1 = ctx.takeEvent(); }
         hipEvent_t evA = q.gev0, evB = q.gev1;
         if (ringEvents) { auto& e = q.evRing[q.evTail % q.evRing.size()]; evA = e.first; evB = e.second; }
-        // two event records around the launch.  (The extended launch that takes the events itself - RSQ_EXT_EVENTS=1 - costs the
-        // host 3 us more per step and the tail another 1.5: measured 16 us of step overhead against 11.5.)
-        const bool extEvents = false;
-        if (extEvents) launchPipelineKernel(q, p, *p.kernel, -1, 0, 0, evA, evB);
-        else {
-            const double tB = stepTrace0 ? nowMs() : 0;
-            RSQ_HIP(hipEventRecord(evA, ctx.stream));
-            const double tC = stepTrace0 ? nowMs() : 0;
-            launchPipelineKernel(q, p, *p.kernel, -1);
-            const double tD = stepTrace0 ? nowMs() : 0;
-            RSQ_HIP(hipEventRecord(evB, ctx.stream));
-            if (stepTrace0) {
-                static double a[3] = {0, 0, 0}; static int n = 0;
-                a[0] += tC - tB; a[1] += tD - tC; a[2] += nowMs() - tD;
-                if (++n == 64) { fprintf(stderr, "[rsq step]   event record %.1f us, launch %.1f us, event record %.1f us\n", a[0] / 64 * 1e3, a[1] / 64 * 1e3, a[2] / 64 * 1e3); a[0] = a[1] = a[2] = 0; n = 0; }
-            }
-        }
+        // two event records around the launch.  (An extended launch that takes the events itself costs the host 3 us more per step
+        // and the tail another 1.5: measured 16 us of step overhead against 11.5.)
+        RSQ_HIP(hipEventRecord(evA, ctx.stream));
+        launchPipelineKernel(q, p, *p.kernel, -1);
+        RSQ_HIP(hipEventRecord(evB, ctx.stream));
         q.finOut = nullptr;
         q.finSeq = 0;
         if (ringEvents) q.evTail++; else q.kernelTimePending = true;
-        static const bool stepTrace = getenv("RSQ_TRACE") && atoi(getenv("RSQ_TRACE")) >= 2;        // host-side phases of the one-launch step, averaged over 64 steps
-        const double tLaunched = stepTrace ? nowMs() : 0;
         q.report.bytes_read = (uint64_t)(p.bytesPerRow * p.src->nRows);
         if (async && partialOnly) {
             // (the kernel leaves its working table reset, and whatever comes next on this stream is ordered behind it)
@@ -1084,7 +1050,6 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
             std::atomic_thread_fence(std::memory_order_acquire);
         } else waitForStream(ctx);
         q.fusedReady = true;
-        const double tSeen = stepTrace ? nowMs() : 0;
         if (q.dDebugStamps) {
             static int nPrinted = 0;
             waitForStream(ctx);
@@ -1120,24 +1085,30 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
             q.report.finalize_time_ms = nowMs() - t1;
         }
         q.report.execution_time_ms = nowMs() - t0;
-        if (stepTrace) {
-            static double acc[4] = {0, 0, 0, 0}; static int n = 0; static double lastEnd = 0;
-            const double tEnd = nowMs();
-            acc[0] += tLaunched - t0; acc[1] += tSeen - tLaunched; acc[2] += tEnd - tSeen; if (lastEnd > 0) acc[3] += t0 - lastEnd;
-            lastEnd = tEnd;
-            if (++n == 64) {
-                fprintf(stderr, "[rsq step] enqueue %.1f us, launch -> result seen %.1f us, tail %.1f us, between executions %.1f us\n",
-                        acc[0] / 64 * 1e3, acc[1] / 64 * 1e3, acc[2] / 64 * 1e3, acc[3] / 63 * 1e3);
-                acc[0] = acc[1] = acc[2] = acc[3] = 0; n = 0; lastEnd = 0;
-            }
-        }
         return;
     }
+    // (read behind the one-launch step, which asks for neither)
+    const bool publishStatus = q.dPinnedDev && sw::flag<sw::RSQ_PUBLISH_STATUS>();      // status words by a kernel's stores into pinned memory
+    const bool fusedSelectOn = sw::flag<sw::RSQ_FUSED_SELECT>();
+    auto ensureCandHost = [&]() {        // coherent pinned rows for topkCapacity candidates, and the device's view of them
+        const size_t need = (size_t)topkCapacity * (size_t)q.groupRowWords;
+        if (q.hCandRowsWords >= need && q.dHostCandRows) return;
+        if (q.hCandRows) ctx.freePinned(q.hCandRows);
+        q.hCandRows = nullptr; q.dHostCandRows = nullptr; q.hCandRowsWords = 0;
+        q.hCandRows = (int64_t*)ctx.allocPinned(std::max<size_t>(need, 8) * 8);
+        q.hCandRowsWords = need;
+        void* dv = nullptr;
+        if (hipHostGetDevicePointer(&dv, q.hCandRows, 0) == hipSuccess && dv) q.dHostCandRows = (int64_t*)dv; else (void)hipGetLastError();
+    };
+    auto fusedSelectOk = [&]() {
+        if (!fusedSelectOn || q.fusedSelectOff || !publishStatus || partialOnly || async || trace) return false;
+        ensureCandHost();
+        return q.dHostCandRows != nullptr;
+    };
     if (denseMode(q)) enqueueTableInit(q);
     ctx.errWordClean = false;      // until this execution has read the word back as 0
     bool anyCompaction = false;
     for (auto& p : q.pipelines) anyCompaction |= p.compact;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;      // per-pipeline wall time (synchronises after each one)
     // everything small this execution wants cleared, in one launch (aot_kernels.hip k_fill_batch): the error word, the pipelines'
     // row counters, the group counter and the candidate selection's scratch of a compaction behind the last pipeline
     bool groupCountCleared = false, topkScratchCleared = false;
@@ -1310,7 +1281,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         // compaction never writes beyond the buffer: a larger count is noticed after the final synchronisation and
         // the execution is repeated with a fresh count.
         uint32_t nEntries = h.lastCount;
-        if ((q.aggMode != AggMode::AT_JOIN_ENTRY && !hashWarm) || nEntries == 0 || getenv("RSQ_TRACE")) {
+        if ((q.aggMode != AggMode::AT_JOIN_ENTRY && !hashWarm) || nEntries == 0 || trace) {
             RSQ_HIP(hipMemcpyAsync(&nEntries, h.dCount, 4, hipMemcpyDeviceToHost, ctx.stream));
             waitForStream(ctx);
             h.lastCount = nEntries;
@@ -1441,7 +1412,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     }
     // The execution's end event.  Where a status kernel follows, the event stands BEHIND it: an event between two kernels is a barrier
     // packet of its own and kept the status kernel waiting ~6 us (per-dispatch trace); behind the last kernel it delays nobody.
-    const bool statusKernelFollows = !selectPublished && q.dPinnedDev && !(getenv("RSQ_PUBLISH_STATUS") && atoi(getenv("RSQ_PUBLISH_STATUS")) == 0);
+    const bool statusKernelFollows = !selectPublished && publishStatus;
     if (!statusKernelFollows) RSQ_HIP(hipEventRecord(q.gev1, ctx.stream));
     q.kernelTimePending = true;
     bool devTail = false;                   // the rows of a large dense aggregation are made on the device (runDenseDeviceTail)
@@ -1453,7 +1424,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     if (!selectPublished) {
         const bool wantGroups = !partialOnly && (q.aggMode == AggMode::AT_JOIN_ENTRY || q.aggMode == AggMode::HASH || denseTopk);
         tableInline = statusKernelFollows && !partialOnly && denseMode(q) && !denseTopk && !trace && tableInlineWords > 0 && tableInlineWords <= 1024 && !(!async && denseDeviceTailWanted(q));
-        if (q.dPinnedDev && !(getenv("RSQ_PUBLISH_STATUS") && atoi(getenv("RSQ_PUBLISH_STATUS")) == 0)) {
+        if (publishStatus) {
             // error word, group count, candidate count and the pipelines' row counters: one kernel writes them into the pinned words
             if (wantGroups && !denseTopk && !topkCapacity && !q.holdTail && !trace && q.dGroupRows && q.groupRowWords > 0) {
                 const size_t need = (size_t)kInlineRows * (size_t)q.groupRowWords;
@@ -1494,7 +1465,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         q.report.execution_time_ms = nowMs() - t0;
         return;
     }
-    static const bool execTraceOn = getenv("RSQ_TRACE") && atoi(getenv("RSQ_TRACE")) >= 2;       // host-side phases of an execution of the general path, averaged over 8
+    const bool execTraceOn = traceLevel.atLeast(2);       // host-side phases of an execution of the general path, averaged over 8
     const double tEnqueued = execTraceOn ? nowMs() : 0;
     bool sawSequence = false;
     if (selectPublished) {
@@ -1900,8 +1871,7 @@ void mergeGathered(Query& q, const void* gathered, int nRanks) {
     const int64_t G = q.denseGroups;
     if (nRanks > 1) for (auto& p : q.pipelines) if (p.sink == SinkKind::AGGREGATE && p.src->nRowsTotal < 0) q.firstRowsForeign = true;
     // small tables: the merge kernel also publishes the result to host-mapped memory (finalizeQuery polls for it)
-    const bool pollOk = !(getenv("RSQ_POLL") && atoi(getenv("RSQ_POLL")) == 0);
-    const bool publish = pollOk && q.dFinHost && q.tableWords <= 2048;
+    const bool publish = sw::flag<sw::RSQ_POLL>() && q.dFinHost && q.tableWords <= 2048;
     q.mergePublishedSeq = publish ? ++q.finSeqCounter : 0;
     mergePartialsAsync(q.ctx, (const int64_t*)gathered, nRanks, (int64_t)q.tableWords, q.nMinBlocks * G, q.nMaxBlocks * G, q.nSumBlocks * G, (int64_t*)q.dAgg,
                        publish ? (int64_t*)q.dFinHost : nullptr, publish ? q.dFinHost + q.pinnedWords + 3 : nullptr, q.mergePublishedSeq);

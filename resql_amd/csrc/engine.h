@@ -19,6 +19,7 @@
 #include "hostref.h"
 #include "mempool.h"
 #include "resql_hip.h"
+#include "switches.h"
 
 #define RSQ_RANK_CHUNK_BLOCKS 1024       /* 32-byte bitmap blocks one workgroup of the rank index handles (aot_kernels.hip) */
 
@@ -69,23 +70,7 @@ struct TableColumn {
 
 // the width of a column's narrow image: a pure function of its type, ownership and statistics (0 = none)
 int narrowWidth(const TableColumn& c);
-// RSQ_NARROW_SCANS=0: no narrow images are built and no scan reads one - the kernels and their text are what they are without them
-// (read where the images are built and where the code generator picks them; flipped by tests/test_gpu_narrow_scan.py)
-inline bool narrowScansEnabled() { const char* e = getenv("RSQ_NARROW_SCANS"); return !e || atoi(e) != 0; }
-// RSQ_DICT_SCANS=1 builds the dictionary images and lets the scans read them; unset or 0: string columns are scanned at their width, the
-// kernels and their text are what they are without the images.  Off by default until the SF10 comparison (tools/dict_scan_bench.py) is on
-// record in docs/KERNELS.md.  RSQ_NARROW_SCANS=0 turns them off as well.
-inline bool dictScansEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return narrowScansEnabled() && e && atoi(e) != 0; }
-// RSQ_DICT_SCANS=2: everything 1 means, and a string that reaches an aggregation as a join's build-side payload is a dense group key by
-// the dictionary of the column it came from (codegen_join.cpp payloadOrigin, codegen_agg.cpp tryDenseKeys).  Read where a statement is
-// compiled; under 0 and 1 no text, explain line or cache key knows of it.
-inline bool dictJoinKeysEnabled() { const char* e = getenv("RSQ_DICT_SCANS"); return dictScansEnabled() && atoi(e) >= 2; }
-// RSQ_MAX_GRID=n (1..65535): the tile loops of a statement compiled under it launch at most n 256-thread workgroups' worth of threads
-// (Pipeline::maxGrid: n * 256 / block size workgroups, at least one); unset, 0 or out of range: the grid the pipeline asks for.  Read ONCE per statement, when it is compiled
-// (compileQuery): buffers sized from the grid then (engine_pipelines.cpp sizeJoinTable) fit every later launch.  A launch parameter only -
-// kernel text and code-object cache keys do not know it; the plan memo's key does.  For tests that need many tiles per wave from a small
-// table (tests/test_gpu_narrow_edges.py: the fold of the 32-bit partial sums).
-inline unsigned maxGridSetting() { const char* e = getenv("RSQ_MAX_GRID"); const long v = e ? atol(e) : 0; return v >= 1 && v <= 65535 ? (unsigned)v : 0u; }
+// (RSQ_NARROW_SCANS, RSQ_DICT_SCANS, RSQ_MAX_GRID and every other environment switch: switches.h; the long form is in docs/KERNELS.md)
 
 struct Context;
 
@@ -234,9 +219,7 @@ rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // ap
 inline bool jitInt16Cast(const Context& c) { return (c.cfg.compat_flags & RSQ_COMPAT_JIT_INT16_CAST) != 0; }
 
 // launch helper: kernel takes one struct of 8-byte slots by value
-// start / stop (optional): events that take the kernel's own begin and end (hipExtModuleLaunchKernel)
-void launch(Context& ctx, Kernel& k, unsigned grid, unsigned block, const std::vector<uint64_t>& args, hipEvent_t start = nullptr,
-            hipEvent_t stop = nullptr);
+void launch(Context& ctx, Kernel& k, unsigned grid, unsigned block, const std::vector<uint64_t>& args);
 
 // AOT kernels (aot_kernels.hip)
 void computeColumnStats(Context& ctx, Table& t);

@@ -109,9 +109,6 @@ void applySlice(DerivedState& d) {
     t.row0 = r0; t.nRows = rows; t.nRowsTotal = n;
 }
 
-bool deviceTailOff() { return getenv("RSQ_DEVICE_TAIL") && atoi(getenv("RSQ_DEVICE_TAIL")) == 0; }
-int64_t deviceTailMin() { return getenv("RSQ_DEVICE_TAIL_MIN") ? atoll(getenv("RSQ_DEVICE_TAIL_MIN")) : 65536; }
-
 void* mergeBuffer(Context& root, DerivedState& d, size_t bytes) {
     if ((int64_t)bytes > d.mergeCapacity || !d.dMerge) {
         if (d.dMerge) root.free(d.dMerge);
@@ -256,7 +253,7 @@ struct Runner {
             total += s.nGroupRows;
         }
         if (!s0.agg) failUnsupported("a derived table without an aggregation");
-        bool device = !deviceTailOff() && total >= deviceTailMin() && total < (1ll << 31) && s0.dGroupRows;
+        bool device = deviceTailTakes(total) && s0.dGroupRows;
         if (device && s0.rowTail < 0) s0.rowTail = planRowsDeviceTail(s0, s0.rtKeys, s0.rtCols, s0.rtTupleSize, s0.rtLimitRows, s0.rtSorts) ? 1 : 0;
         device = device && s0.rowTail == 1 && !s0.rtSorts && s0.accums.size() <= 32;
         if (!device) {
@@ -340,7 +337,7 @@ std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* co
 void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out) {
     out = DerivedMultiRun();
     Runner r;
-    r.onThreads = &onThreads; r.out = &out; r.trace = getenv("RSQ_TRACE") != nullptr;
+    r.onThreads = &onThreads; r.out = &out; r.trace = sw::traceOn();
     r.run(qs, "");
 }
 

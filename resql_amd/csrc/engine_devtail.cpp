@@ -19,9 +19,7 @@ namespace rsq {
 // uploaded once, into the tail's arena; where two CHAR(n) entries are equal up to trailing spaces their groups are merged on the device
 // first (devtail.hip k_dense_fold / k_dense_spell), in place in q.dAgg, which every execution's start puts back to its identities.
 bool denseDeviceTailWanted(Query& q) {
-    const bool off = getenv("RSQ_DEVICE_TAIL") && atoi(getenv("RSQ_DEVICE_TAIL")) == 0;      // (read per execution: tests switch it)
-    const int64_t minGroups = getenv("RSQ_DEVICE_TAIL_MIN") ? atoll(getenv("RSQ_DEVICE_TAIL_MIN")) : 65536;
-    if (off || q.holdTail || q.aggPad != 1 || q.denseGroups < minGroups || q.denseGroups >= (1ll << 31) || !q.dAgg) return false;
+    if (!deviceTailTakes(q.denseGroups) || q.holdTail || q.aggPad != 1 || !q.dAgg) return false;
     if (q.devTail < 0) q.devTail = planDenseDeviceTail(q, q.dtKeys, q.dtCols, q.dtTupleSize, q.dtLimitRows) ? 1 : 0;
     return q.devTail == 1;
 }
@@ -30,7 +28,7 @@ bool denseDeviceTailWanted(Query& q) {
 double runDenseDeviceTail(Query& q) {
     Context& ctx = q.ctx;
     const int64_t D = q.denseGroups;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;
+    const bool trace = sw::traceOn();
     double tPhase = nowMs();
     auto phase = [&](const char* what) {
         if (!trace) return;
@@ -125,7 +123,7 @@ double runDenseDeviceTail(Query& q) {
         denseGroupHashes(ctx, dGids, n, q.dtKeys, q.dtHashes);
         // the replay of the reference's table: on the device too (devtail.hip), unless switched off or out of its range
         std::vector<std::pair<uint64_t, uint64_t>> levels;
-        const bool devReplay = !(getenv("RSQ_DEVICE_REPLAY") && atoi(getenv("RSQ_DEVICE_REPLAY")) == 0) && q.dtReplayWork && n >= 4096 &&
+        const bool devReplay = sw::flag<sw::RSQ_DEVICE_REPLAY>() && q.dtReplayWork && n >= 4096 &&
                                replayLevels((uint64_t)n, opSize(q.agg), levels) && replayDeviceBytes((uint64_t)n, levels.back().first) <= q.dtReplayBytes;
         if (devReplay) {
             replayEmissionOrderDevice(ctx, q.dtHashes, (uint64_t)n, levels, q.dtReplayWork, q.dtOrder);
@@ -164,9 +162,7 @@ double runDenseDeviceTail(Query& q) {
 // The host path this replaces copies all group rows (n x words x 8 bytes over PCIe), decodes them, hashes, replays and builds the
 // rows on the worker pool: 5-30 ms per million groups.
 bool rowsDeviceTailWanted(Query& q, int64_t n) {
-    const bool off = getenv("RSQ_DEVICE_TAIL") && atoi(getenv("RSQ_DEVICE_TAIL")) == 0;
-    const int64_t minGroups = getenv("RSQ_DEVICE_TAIL_MIN") ? atoll(getenv("RSQ_DEVICE_TAIL_MIN")) : 65536;
-    if (off || q.holdTail || n < minGroups || n >= (1ll << 31) || !q.dGroupRows) return false;
+    if (!deviceTailTakes(n) || q.holdTail || !q.dGroupRows) return false;
     if (q.aggMode == AggMode::HASH && q.charGroupsNeedMerge) return false;      // groups equal up to trailing spaces: the host merges them first
     if (q.rowTail < 0) q.rowTail = planRowsDeviceTail(q, q.rtKeys, q.rtCols, q.rtTupleSize, q.rtLimitRows, q.rtSorts) ? 1 : 0;
     return q.rowTail == 1;
@@ -175,7 +171,7 @@ bool rowsDeviceTailWanted(Query& q, int64_t n) {
 double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows) {
     Context& ctx = q.ctx;
     const int64_t* src = groupRows ? groupRows : q.dGroupRows;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;
+    const bool trace = sw::traceOn();
     const double t0 = nowMs();
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     if (q.rtCapacity < n) {
@@ -197,9 +193,7 @@ double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows) {
     void* replayWork = d + at;
     const size_t replayBytes = replayDeviceBytes((uint64_t)cap, (uint64_t)cap * 4 + 1024);
     int64_t emit = n;
-    const bool limitHere = q.rtLimitRows >= 0 && !q.rtSorts;      // (with an ORDER BY the materialisation's own limit cuts the EMISSION order first, as materialize.h:197-206 does)
-    if (q.rtLimitRows >= 0) emit = std::min(emit, q.rtLimitRows);
-    (void)limitHere;
+    if (q.rtLimitRows >= 0) emit = std::min(emit, q.rtLimitRows);      // (with an ORDER BY too: the materialisation's own limit cuts the EMISSION order first, as materialize.h:197-206 does)
     const uint32_t* dIdx = nullptr;
     const uint32_t* dOrder = nullptr;
     const int stride = q.groupRowWords;

@@ -4,6 +4,8 @@
 
 #include <atomic>
 #include <chrono>
+#include <cstdarg>
+#include <cstdio>
 #include <thread>
 #include <map>
 #include <memory>
@@ -490,7 +492,7 @@ struct Query {
     uint64_t mergePublishedSeq = 0;        // > 0: rsq_query_merge_gathered also published the merged table to hPinned; finalize polls for this number
     bool kernelTimePending = false;        // the fused step's events have not been read yet (resolveKernelTime)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> evRing; size_t evHead = 0, evTail = 0;      // event pairs of the one-launch steps not read yet
-    hipEvent_t gev0 = nullptr, gev1 = nullptr;   // start / stop of the fused step's kernel (hipExtModuleLaunchKernel)
+    hipEvent_t gev0 = nullptr, gev1 = nullptr;   // recorded in front of and behind the fused step's kernel
     bool pendingFused = false;             // the enqueued asynchronous step was a fused one
     // generic pipeline in front of the specialised kernel (see GenericProgram)
     bool genericActive = false, genericForced = false;
@@ -512,7 +514,7 @@ struct Query {
     std::string allSource, explainText;
     std::string memoKey;                   // the context's plan memo entry of this query (empty: none)
     bool memoApplied = false;              // ... and an earlier query's entry was found when this one was compiled
-    unsigned maxGrid = 0;                  // RSQ_MAX_GRID as it stood when this query was compiled (engine.h maxGridSetting): every pipeline's maxGrid
+    unsigned maxGrid = 0;                  // RSQ_MAX_GRID as it stood when this query was compiled (switches.h): every pipeline's maxGrid
 
     explicit Query(Context& c) : ctx(c) {}
     ~Query();
@@ -528,6 +530,20 @@ void nameDerivedColumns(Query& q, OpNode* scan);      // engine.cpp: the walker 
 inline double nowMs() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// a line of RSQ_TRACE output (the whole line is the format's: "[rsq trace] ...\n"); nothing while the switch is unset
+__attribute__((format(printf, 1, 2))) inline void traceLine(const char* fmt, ...) {
+    if (!sw::traceOn()) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+}
+
+// do the device tails take an aggregation of this many groups?  (RSQ_DEVICE_TAIL, RSQ_DEVICE_TAIL_MIN: read per execution, tests switch them)
+inline bool deviceTailTakes(int64_t groups) {
+    return sw::flag<sw::RSQ_DEVICE_TAIL>() && groups >= sw::num<sw::RSQ_DEVICE_TAIL_MIN>() && groups < (1ll << 31);
 }
 
 // codegen.cpp: turns the operator tree below the last pipeline breaker into device pipelines
@@ -554,8 +570,7 @@ void freeMatCols(Query& q);
 uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTable);
 int residentWorkgroupsPerCU(Kernel* k, int blockThreads);
 unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm = false);
-void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid = 0, unsigned block = 0,
-                                 hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid = 0, unsigned block = 0);
 void waitForStream(Context& ctx);
 void debugStamps(Query& q, Pipeline& p);
 Kernel* fewGroupsKernel(Query& q, Pipeline& p, const std::string& source, const char* form, Kernel* large);

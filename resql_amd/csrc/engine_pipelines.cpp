@@ -126,20 +126,18 @@ unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm) {
     return (unsigned)std::max<int64_t>(1, grid);
 }
 
-void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid, unsigned block,
-                                 hipEvent_t start, hipEvent_t stop) {
+void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid, unsigned block) {
     p.lastGrid = grid ? grid : pipelineGrid(q, p);
     std::vector<uint64_t> args;
     for (auto& a : p.args) args.push_back(argValue(q, p, a, countOnlyTable));
-    launch(q.ctx, k, p.lastGrid, block ? block : (unsigned)p.blockThreads, args, start, stop);
+    launch(q.ctx, k, p.lastGrid, block ? block : (unsigned)p.blockThreads, args);
     q.report.num_kernels++;
 }
 
 // The synchronisation at the end of an execution: the stream is queried in a loop for up to 2 ms before the thread blocks
 // (hipStreamSynchronize sleeps on the completion signal's interrupt: 10-20 us of wake-up on a sub-millisecond execution).
 void waitForStream(Context& ctx) {
-    const bool spin = !(getenv("RSQ_POLL") && atoi(getenv("RSQ_POLL")) == 0);
-    if (spin) {
+    if (sw::flag<sw::RSQ_POLL>()) {
         const double deadline = nowMs() + 2.0;
         for (;;) {
             const hipError_t e = hipStreamQuery(ctx.stream);
@@ -176,7 +174,7 @@ void debugStamps(Query& q, Pipeline& p) {
     };
     unsigned early = 0;
     for (unsigned w = 0; w < p.lastGrid; w++) if (st[w * 8] && st[w * 8] - t0 < 500) early++;
-    if (getenv("RSQ_DEBUG_TAIL") && atoi(getenv("RSQ_DEBUG_TAIL")) >= 2) {
+    if (sw::unclamped<sw::RSQ_DEBUG_TAIL>() >= 2) {
         double byMod[8] = {0}, n8[8] = {0}, byQuarter[4] = {0}, n4[4] = {0};
         for (unsigned w = 0; w < p.lastGrid; w++) {
             if (!st[w * 8 + 1]) continue;
@@ -225,13 +223,13 @@ void launchPipeline(Query& q, Pipeline& p, int countOnlyTable, bool pass1) {
         else
         launchPipelineKernel(q, p, *p.kernelLazy, countOnlyTable, pipelineGrid(q, p, true));
         debugStamps(q, p);
-        if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     %s: late-load form, %u workgroups (%lld rows reached stage 2 last time)\n", p.entry.c_str(), p.lastGrid, (long long)p.stage2Rows);
+        traceLine("[rsq trace]     %s: late-load form, %u workgroups (%lld rows reached stage 2 last time)\n", p.entry.c_str(), p.lastGrid, (long long)p.stage2Rows);
         return;
     }
     if (Kernel* few = (!pass1 && k == p.kernel) ? fewGroupsKernel(q, p, p.source, "eager", k) : nullptr) launchPipelineKernel(q, p, *few, countOnlyTable, fewGroupsGrid(q, p, few));
     else
     launchPipelineKernel(q, p, *k, countOnlyTable);
-    if (getenv("RSQ_TRACE") && p.compact) fprintf(stderr, "[rsq trace]     %s: %u workgroups (%lld rows reached stage 2 last time)\n", p.entry.c_str(), p.lastGrid, (long long)p.stage2Rows);
+    if (p.compact) traceLine("[rsq trace]     %s: %u workgroups (%lld rows reached stage 2 last time)\n", p.entry.c_str(), p.lastGrid, (long long)p.stage2Rows);
     debugStamps(q, p);
 }
 
@@ -279,7 +277,7 @@ bool runStagedAggregation(Query& q, Pipeline& p, const std::vector<uint64_t>& es
     const unsigned nwg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx.numCUs, rounds));
     const uint64_t lineRecords = (uint64_t)(16 / p.stagedRecWords);
     const size_t recBytes = 8 * (size_t)p.stagedRecWords;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;
+    const bool trace = sw::traceOn();
     prepareStageBuffers(q, p);
     q.stageWorkgroups = nwg;
     std::vector<uint32_t> cap((size_t)P);
@@ -373,9 +371,8 @@ void runLargeDenseAggregation(Query& q, Pipeline& p) {
     const int64_t tiles = p.src->nRows >> 7;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx.numCUs, (tiles + 15) / 16));
     const int64_t rows = p.src->nRows;
-    const char* forceEnv = getenv("RSQ_PARTITION");
-    const bool force = forceEnv && atoi(forceEnv) == 2;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;
+    const bool force = sw::unclamped<sw::RSQ_PARTITION>() == 2;
+    const bool trace = sw::traceOn();
     if (!force && rows < (4 << 20)) { launchPipeline(q, p, -1); return; }       // small inputs: the extra passes cost more than they save
     const size_t words = (size_t)grid * (size_t)P;
     prepareStageBuffers(q, p);
@@ -508,11 +505,12 @@ void materializePipeline(Query& q, Pipeline& p) {
     q.matLimit = 0;
     launchPipeline(q, p, -1, true);
     // RSQ_SCAN_CHAINED: 0 never the one-launch scan, 2 at every size (tests: the form is otherwise out of a small table's reach), else by size
-    const int chainedWhen = getenv("RSQ_SCAN_CHAINED") ? atoi(getenv("RSQ_SCAN_CHAINED")) : 1;
+    const int chainedWhen = (int)sw::num<sw::RSQ_SCAN_CHAINED>();
     const bool chainedOk = chainedWhen != 0;
     // (the one-launch scan pays from ~8 M counts on; one count per 128 rows means tables beyond a billion rows)
     const bool chained = chainedOk && !q.scanChainedOff && (chainedWhen == 2 || tiles + 1 >= (8ll << 20));
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     %s: offset scan of %lld counts in %s\n", p.entry.c_str(), (long long)(tiles + 1), chained ? "one launch" : "three launches");
+    const bool trace = sw::traceOn();
+    if (trace) fprintf(stderr, "[rsq trace]     %s: offset scan of %lld counts in %s\n", p.entry.c_str(), (long long)(tiles + 1), chained ? "one launch" : "three launches");
     if (chained) exclusiveScanCountsChained(ctx, q.dMatTileCnt, q.dMatOffs, tiles + 1, q.dScanTemp, q.scanTempBytes);
     else exclusiveScanCounts(ctx, q.dMatTileCnt, q.dMatOffs, tiles + 1, q.dScanTemp, q.scanTempBytes);
     q.report.num_kernels++;
@@ -521,10 +519,10 @@ void materializePipeline(Query& q, Pipeline& p) {
     q.dMatTotal = q.dMatOffs + tiles;
     q.matWarmRun = false;
     {
-        const bool publish = q.dPinnedDev && !(getenv("RSQ_PUBLISH_STATUS") && atoi(getenv("RSQ_PUBLISH_STATUS")) == 0);
+        const bool publish = q.dPinnedDev && sw::flag<sw::RSQ_PUBLISH_STATUS>();
         uint64_t keepWarm = (uint64_t)std::max<int64_t>(q.matLastTotal, 0);
         if (q.matOp->hasLimit) keepWarm = std::min<uint64_t>(keepWarm, (uint64_t)std::max<int64_t>(q.matOp->limit, 1));
-        if (q.matLastTotal >= 0 && publish && !chained && !getenv("RSQ_TRACE") && !q.holdTail && !q.dMatCols.empty() && (int64_t)keepWarm <= q.matCapacity) {
+        if (q.matLastTotal >= 0 && publish && !chained && !trace && !q.holdTail && !q.dMatCols.empty() && (int64_t)keepWarm <= q.matCapacity) {
             q.matRows = (int64_t)keepWarm;
             q.matLimit = keepWarm;
             q.matWarmRun = true;
@@ -635,7 +633,7 @@ void sizeJoinTable(Query& q, Pipeline& p, HashTable& h, uint32_t n, bool dupKeys
         h.dWords = (int64_t*)ctx.alloc((size_t)h.capacity * 8 * std::max<size_t>(1, nWords));
     }
     if (q.aggTable == h.id) h.dAcc = (int64_t*)ctx.alloc((size_t)h.capacity * 8 * (size_t)h.nAccBlocks);
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     ht%d: %s, %u build rows\n", h.id, h.direct ? (h.dense ? "the build table's own columns (dense keys in row order: nothing is built)" : "the build table's own columns (keys in row order: only the key bitmap and its index are built)") : h.identity ? "bitmap-rank dictionary, entries in row order" : h.rank ? "bitmap-rank dictionary" : "hash table", n);
+    traceLine("[rsq trace]     ht%d: %s, %u build rows\n", h.id, h.direct ? (h.dense ? "the build table's own columns (dense keys in row order: nothing is built)" : "the build table's own columns (keys in row order: only the key bitmap and its index are built)") : h.identity ? "bitmap-rank dictionary, entries in row order" : h.rank ? "bitmap-rank dictionary" : "hash table", n);
 }
 
 // size (by a counting pass of the same pipeline), allocate and clear a join table, then build it
@@ -694,7 +692,7 @@ void buildHashTable(Query& q, Pipeline& p) {
         if (!prepared) { prepareTableAsync(ctx, nullptr, 0, 0, h.dTempUsed, (size_t)h.tempWaves, h.dBitmap, bmWords, h.dCount); q.report.num_kernels++; }
         launchPipeline(q, p, -1);
         // the index in one launch (chunk totals chained between the workgroups) when the prologue has zeroed the chain words
-        const bool chainedOk = !(getenv("RSQ_RANK_CHAINED") && atoi(getenv("RSQ_RANK_CHAINED")) == 0);
+        const bool chainedOk = sw::flag<sw::RSQ_RANK_CHAINED>();
         if (prepared && chainedOk && !q.chainedIndexOff) { rankTableIndexChained(ctx, h.dBitmap, h.bmBlocks, h.dChunkTotal, h.dChunkBase); q.report.num_kernels += 1; }
         else { rankTableIndex(ctx, h.dBitmap, h.bmBlocks, h.dChunkTotal, h.dChunkBase); q.report.num_kernels += 2; }
         if (!h.identity) {      // (identity: the build wrote every record to the entry with its row's number)

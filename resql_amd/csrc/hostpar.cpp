@@ -1,5 +1,6 @@
 // hostpar.cpp — see hostpar.h.
 #include "hostpar.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <atomic>
@@ -78,7 +79,7 @@ struct Pool {
 
 int configuredThreads() {
     static const int n = [] {
-        if (const char* e = getenv("RSQ_TAIL_THREADS")) return std::max(1, std::min(64, atoi(e)));
+        if (const int set = (int)sw::num<sw::RSQ_TAIL_THREADS>()) return set;
         unsigned hw = std::thread::hardware_concurrency();
         return (int)std::max(1u, std::min(16u, hw ? hw : 1u));
     }();

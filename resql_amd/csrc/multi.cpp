@@ -654,7 +654,7 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             // sort keys.  RSQ_MULTI_GENERAL_MERGE=1 forces the general merge (tests).
             std::string why;
             const bool disjoint = n > 1 && shardGroupsDisjoint(mq->qs, why);
-            const bool forceGeneral = getenv("RSQ_MULTI_GENERAL_MERGE") && atoi(getenv("RSQ_MULTI_GENERAL_MERGE")) != 0;
+            const bool forceGeneral = sw::flag<sw::RSQ_MULTI_GENERAL_MERGE>();
             mq->orderedFast = disjoint && queryOrderedWithLimit(*mq->qs[0]) && !forceGeneral;
             if (n == 1) mq->mergeText = "single shard";
             else if (mq->orderedFast) mq->mergeText = "ordered merge of the shards' LIMIT-ed rows (" + why + ")";

@@ -360,7 +360,7 @@ void Context::compileManyToCache(const std::vector<std::string>& sources) {
         for (auto& t : todo) seen = seen || t.first == key;
         if (!seen) todo.emplace_back(key, &src);
     }
-    const bool helpersOff = getenv("RSQ_COMPILE_HELPERS") && atoi(getenv("RSQ_COMPILE_HELPERS")) == 0;
+    const bool helpersOff = !sw::flag<sw::RSQ_COMPILE_HELPERS>();
     const std::string helper = libraryDir() + "/rsq_kernel_compiler";
     if (todo.size() > 1 && !helpersOff && access(helper.c_str(), X_OK) == 0) {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
@@ -431,7 +431,7 @@ void Context::compileToCache(const std::string& source) {
 Kernel& Context::getKernel(const std::string& source, const std::string& entry) {
     const std::string key = cacheKey(source);
     // (the build lists the keys it resolves so that it can remove the code objects of older kernel texts afterwards: __graft_entry__.py)
-    if (const char* usedLog = getenv("RSQ_KCACHE_USED_LOG")) {
+    if (const char* usedLog = sw::path<sw::RSQ_KCACHE_USED_LOG>()) {
         if (FILE* f = fopen(usedLog, "a")) { fprintf(f, "%s\n", key.c_str()); fclose(f); }
     }
     auto it = kernels.find(key);
@@ -459,17 +459,11 @@ Kernel& Context::getKernel(const std::string& source, const std::string& entry) 
     return kernels.emplace(key, k).first->second;
 }
 
-void launch(Context& ctx, Kernel& k, unsigned grid, unsigned block, const std::vector<uint64_t>& args, hipEvent_t start, hipEvent_t stop) {
+void launch(Context& ctx, Kernel& k, unsigned grid, unsigned block, const std::vector<uint64_t>& args) {
     if (!k.fn) throw Error(RSQ_ERR_DEVICE, "kernel not loaded (context without device)");
     size_t size = args.size() * sizeof(uint64_t);
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, (void*)args.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                       HIP_LAUNCH_PARAM_END};
-    if (start || stop) {
-        // the events take the timestamps of this dispatch itself: no marker packets around the kernel
-        // (the extended launch counts the GLOBAL size in work-items, not workgroups)
-        RSQ_HIP(hipExtModuleLaunchKernel(k.fn, grid * block, 1, 1, block, 1, 1, 0, ctx.stream, nullptr, config, start, stop, 0));
-        return;
-    }
     RSQ_HIP(hipModuleLaunchKernel(k.fn, grid, 1, 1, block, 1, 1, 0, ctx.stream, nullptr, config));
 }
 

@@ -398,8 +398,7 @@ static void runMaterializeTail(Query& q) {
 // i.e. one word of the group rows the device compacts.  Symbols are resolved the way the tail's HostCompiler does.
 void planDeviceTopK(Query& q) {
     q.topkWord = -1;
-    const char* env = getenv("RSQ_DEVICE_TOPK");
-    if (env && atoi(env) == 0) return;
+    if (!sw::flag<sw::RSQ_DEVICE_TOPK>()) return;
     OpNode* agg = q.agg;
     const bool dense = q.aggMode == AggMode::DENSE_GLOBAL;         // candidate rows [first row | group id | accumulator blocks]
     if (!agg || (q.aggMode != AggMode::AT_JOIN_ENTRY && q.aggMode != AggMode::HASH && !dense)) return;
@@ -480,7 +479,7 @@ void runTail(Query& q) {
     if (q.aggMode == AggMode::HASH) mergeSpaceEquivalentGroups(q, G);
     else if (q.aggMode != AggMode::AT_JOIN_ENTRY)      // (dense: two dictionary entries of a coded CHAR(n) key that differ in trailing spaces only are two ranks)
         for (auto& dk : q.denseKeys) if (dk.coded && dk.spaceEquivalent) { mergeEqualGroups(q, G); break; }
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     tail: %.3f ms  groups from the device tables\n", nowMs() - t0);
+    traceLine("[rsq trace]     tail: %.3f ms  groups from the device tables\n", nowMs() - t0);
     runTailOn(q, G);
 }
 
@@ -544,7 +543,7 @@ void runTailMerged(Query& root, const std::vector<Query*>& parts) {
     G.n = total;
     const double t0 = nowMs();
     mergeEqualGroups(root, G);
-    if (getenv("RSQ_TRACE")) fprintf(stderr, "[rsq trace]     tail: %.3f ms  %zu group rows of %zu shards merged into %zu groups\n", nowMs() - t0, total, parts.size(), G.n);
+    traceLine("[rsq trace]     tail: %.3f ms  %zu group rows of %zu shards merged into %zu groups\n", nowMs() - t0, total, parts.size(), G.n);
     runTailOn(root, G);
 }
 
@@ -749,7 +748,7 @@ void runRowsTailSort(Query& q, uint8_t* tuples, int64_t& rows) {
 
 static void runTailOn(Query& q, Groups& G) {
     OpNode* agg = q.agg;
-    const bool trace = getenv("RSQ_TRACE") != nullptr;
+    const bool trace = sw::traceOn();
     double tPhase = nowMs();
     auto phase = [&](const char* what) {
         if (!trace) return;

@@ -2,7 +2,7 @@
 fallback (a look-back that timed out, a table that fell back to its hash form, a host without mapped pinned memory, ...).  A
 form nobody runs rots: each switch is flipped here, in a fresh context, over seeded plans of the shapes it touches, and the
 answers are compared with the oracle byte for byte (multiset for plans without an order, as the reference's own tests do,
-test/test_common.h:152-190).  DESIGN.md lists the switches; `grep -oh '"RSQ_[A-Z0-9_]*"' resql_amd/csrc` must stay within them."""
+test/test_common.h:152-190).  DESIGN.md lists the switches; resql_amd/csrc/switches.h declares them and tests/test_switch_list.py holds the lists together."""
 import os
 import re
 
@@ -44,7 +44,7 @@ KNOBS = [
     ("RSQ_PARTITION", "2", ("dense_large",)),
     ("RSQ_STAGED", "0", ("dense_large",)),
     ("RSQ_AGG_MODE", "5", ("fuzz",)),
-    ("RSQ_TRACE", "2", ("tpch",)),                       # the traced paths synchronise between kernels: another order of the same calls
+    ("RSQ_TRACE", "2", ("tpch",)),                       # the traced paths synchronise between kernels: another order of the same calls (level 2 is read per execution: its paths are really taken)
     ("RSQ_DEBUG_TAIL", "1", ("q3",)),                    # device timestamps of the pipelines' workgroups (a kernel argument more)
 ]
 
