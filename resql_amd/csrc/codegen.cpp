@@ -144,7 +144,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     // 768: 0.367, 1024: 0.374, 2048: 0.395, 4096: 0.448 - a streaming kernel wants exactly 2 resident workgroups per CU
     // (RSQ_MAX_GRID, as the statement's compile read it, overrides that: a launch parameter, not part of the text)
     pipe.maxGrid = q.maxGrid;
-    colTypes.clear(); colIsString.clear(); colNarrow.clear(); colDict.clear(); nDictTables = 0; rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
+    colTypes.clear(); colIsString.clear(); colNarrow.clear(); colDict.clear(); colTyped.clear(); eg.typedLeaves.clear(); nDictTables = 0; rowParams.clear(); rowArgsTail.clear(); rowArgsTailGuarded.clear(); bitmapPrefetch.clear();
     body.clear(); stateDecl.clear(); stateInit.clear(); prologue.clear(); epilogue.clear(); fileScope.clear(); helperFns.clear();
     explainSteps.clear(); indent = 1; matchSlotTable = -1; slotVar.clear(); symbolOrigin.clear(); symbolWord.clear();
     multiMatchAbove = false; repeatedKeysAbove.clear(); denseRefusal.clear();

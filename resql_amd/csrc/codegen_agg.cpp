@@ -859,11 +859,69 @@ void Walker::emitStagedScatter(int64_t D, int W, int gpp, int shift, int P) {
     pipe.sourceStagedAgg = k.str();
 }
 
+// The envelope of a scanned column (see ExprGen::emitTyped): the sign class and the bit width of max(|min|, |max|) of its statistics.
+bool Walker::envelopeOf(const TableColumn& c, bool& neg, int& bits) {
+    if (!c.owned || !c.stats.valid || c.stats.min <= -(int64_t(1) << 40) || c.stats.max >= (int64_t(1) << 40)) return false;
+    const uint64_t m = (uint64_t)std::max(c.stats.max < 0 ? -c.stats.max : c.stats.max, c.stats.min < 0 ? -c.stats.min : c.stats.min);
+    bits = 0;
+    while (bits < 63 && (m >> bits) != 0) bits++;
+    neg = c.stats.min < 0;
+    return true;
+}
+
+// The register aggregation's scan, where its 32-bit partial sums apply: every i64 column read from a narrow image whose envelope fits
+// 31 bits is decoded as i32 - tile registers, tail rows and the row function's parameter n_<k> - and widened once, at the top of the row
+// function, into the v_<k> the selections, group ids and every other consumer already name.  The aggregation's own inputs are then
+// emitted from the n_<k> (ExprGen::emitTyped).  False: nothing changes.
+bool Walker::typeScanColumns() {
+    if (!sw::flag<sw::RSQ_NARROW_SCANS>() || compacted || !pipe.src || pipe.src->derived) return false;
+    colTyped.assign(colTypes.size(), 0);
+    std::string widen;
+    for (size_t k = 0; k < colTypes.size(); k++) {
+        if (colIsString[k] || coded((int)k) || !colNarrow[k] || colTypes[k] != "i64") continue;
+        bool neg = false; int bits = 0;
+        if (!envelopeOf(pipe.src->cols[(size_t)pipe.cols[k]], neg, bits) || bits > 31) continue;
+        const std::string K = std::to_string(k);
+        auto patch = [&](std::string& text, const std::string& from, const std::string& to) {
+            for (size_t at = 0; (at = text.find(from, at)) != std::string::npos; at += to.size()) {
+                const size_t end = at + from.size();
+                if (isdigit((unsigned char)from.back()) && end < text.size() && isdigit((unsigned char)text[end])) { at = end - to.size(); continue; }
+                text.replace(at, from.size(), to);
+            }
+        };
+        patch(rowParams, ", i64 v_" + K, ", i32 n_" + K);
+        patch(rowArgsTail, "rsq::dec<i64>(a.c" + K + "[", "rsq::dec<i32>(a.c" + K + "[");
+        patch(rowArgsTailGuarded, "rsq::dec<i64>(a.c" + K + "[", "rsq::dec<i32>(a.c" + K + "[");
+        colTyped[k] = 1; colTypes[k] = "i32";
+        eg.typedLeaves["v_" + K] = ExprGen::TypedLeaf{"n_" + K, neg, bits};
+        widen += "    const i64 v_" + K + " = (i64)n_" + K + "; (void)v_" + K + ";\n";
+    }
+    if (widen.empty()) return false;
+    body = widen + body;
+    return true;
+}
+
 void Walker::emitDenseAggregation(OpNode* o) {
     const int64_t D = q.denseGroups;
     const int W = (int)q.accums.size();
     line("const int gid = " + groupIdExpr() + ";");
-    for (int w = 1; w < W; w++) line("const i64 in" + std::to_string(w) + " = " + q.accums[(size_t)w].input + ";");
+    // (the register form over narrow scan columns: the inputs of its sums at the width their value range proves)
+    const bool typed = q.aggMode == AggMode::DENSE_REG && typeScanColumns();
+    // an input that feeds an i64 accumulator keeps its name and type at the use; the input of a 32-bit partial sum may be an i32
+    auto emitInputs = [&](const std::vector<char>& part32) {
+        for (int w = 1; w < W; w++) {
+            const Accum& ac = q.accums[(size_t)w];
+            const std::string name = "in" + std::to_string(w);
+            if (typed && ac.merge == 0 && ac.inputExpr && eg.pureArithmetic(ac.inputExpr)) {
+                const ExprGen::TV v = eg.emitTyped(ac.inputExpr);
+                if (v.is32 && part32[(size_t)w]) line("const i32 " + name + " = " + v.text + ";");
+                else line("const i64 " + name + " = " + ExprGen::wide(v) + ";");
+            } else line("const i64 " + name + " = " + ac.input + ";");
+        }
+    };
+    if (q.aggMode != AggMode::DENSE_REG) emitInputs(std::vector<char>((size_t)W, 0));
+    // the first-row tracker of the register form as a u32 of the row's offset in the launch (below): tables below 2^32 - 1 rows
+    const bool fr32 = typed && !underNestedLoops() && pipe.src->nRows < (int64_t)0xffffffffll && pipe.src->totalRows() < (int64_t)0xffffffffll;
     auto inOf = [&](int w) { return w == 0 ? std::string("row") : "in" + std::to_string(w); };
     addArg("out", "u64*", 0);
     std::ostringstream ep;
@@ -891,17 +949,23 @@ void Walker::emitDenseAggregation(OpNode* o) {
                 else if (ac.input.compare(0, 2, "v_") == 0 && ac.input.find_first_not_of("0123456789", 2) == std::string::npos && ac.input.size() > 2) {
                     const int k = atoi(ac.input.c_str() + 2);
                     if (k >= 0 && k < (int)pipe.cols.size() && !colIsString[(size_t)k]) {
-                        const TableColumn& c = pipe.src->cols[(size_t)pipe.cols[(size_t)k]];
-                        if (c.owned && c.stats.valid && c.stats.min > -(int64_t(1) << 40) && c.stats.max < (int64_t(1) << 40)) {
-                            const uint64_t m = (uint64_t)std::max(c.stats.max < 0 ? -c.stats.max : c.stats.max, c.stats.min < 0 ? -c.stats.min : c.stats.min);
-                            bits = 0;
-                            while (bits < 63 && (m >> bits) != 0) bits++;
-                        }
+                        bool neg = false;
+                        if (!envelopeOf(pipe.src->cols[(size_t)pipe.cols[(size_t)k]], neg, bits)) bits = -1;
                     }
                 }
                 if (bits >= 0 && bits <= 24) part32[(size_t)w] = 1;
             }
         }
+        emitInputs(part32);
+        // The first row of a group, accumulator 0, is min(row) with row = a.row0 + lr: a 64-bit compare and two selects per update.
+        // Below 2^32 - 1 rows the offset lr alone is tracked, as a u32 with the identity 0xffffffff and one unsigned minimum per
+        // update, and becomes the i64 cell in front of the epilogue; from s_lane on nothing changes.
+        if (fr32)
+            for (int64_t g = 0; g < D; g++) {
+                const std::string G = std::to_string((long long)g);
+                stateDecl += "    u32 fr_" + G + " = 0xffffffffu;\n";
+                ep << "    st.acc_0_" << G << " = st.fr_" << G << " == 0xffffffffu ? (i64)" << identityOf(2) << " : a.row0 + (i64)st.fr_" << G << ";\n";
+            }
         std::string fold;
         for (int w = 0; w < W; w++) {
             if (!part32[(size_t)w]) continue;
@@ -935,6 +999,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
                     std::string acc = "st.acc_" + std::to_string(w) + "_" + std::to_string((long long)g), in = inOf(w);
                     int m = q.accums[(size_t)w].merge;
                     if (m == 0) addLine(acc, w, in, in);
+                    else if (w == 0 && fr32) { const std::string fr = "st.fr_" + std::to_string((long long)g); line(fr + " = (u32)lr < " + fr + " ? (u32)lr : " + fr + ";"); }
                     else if (m == 2) line(acc + " = " + in + " < " + acc + " ? " + in + " : " + acc + ";");
                     else line(acc + " = " + in + " > " + acc + " ? " + in + " : " + acc + ";");
                 }
@@ -948,6 +1013,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
                 std::string acc = "st.acc_" + std::to_string(w) + "_" + std::to_string((long long)g), in = inOf(w);
                 int m = q.accums[(size_t)w].merge;
                 if (m == 0) addLine(acc, w, in, "m ? " + in + " : (i64)0");
+                else if (w == 0 && fr32) { const std::string fr = "st.fr_" + std::to_string((long long)g); line(fr + " = (m && (u32)lr < " + fr + ") ? (u32)lr : " + fr + ";"); }
                 else if (m == 2) line(acc + " = (m && " + in + " < " + acc + ") ? " + in + " : " + acc + ";");
                 else line(acc + " = (m && " + in + " > " + acc + ") ? " + in + " : " + acc + ";");
             }

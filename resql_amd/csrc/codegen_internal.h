@@ -215,6 +215,92 @@ struct ExprGen {
         }
     }
 
+    // ---- arithmetic typed by value range (the register aggregation over narrow scan columns, codegen_agg.cpp) ----
+    // A scan column read from a narrow image has an ENVELOPE from its statistics: a sign class (min >= 0 or not) and the bit width of
+    // max(|min|, |max|) - a power of two, never the values, so one plan shape keeps one text across scale factors and bases.  Where the
+    // envelope fits 31 bits the column reaches the row function as an i32 (typedLeaves: the i64 name other consumers read -> that
+    // parameter), and +, -, * over such leaves and constants are emitted at the width their own envelope proves: the exact result is
+    // then representable, so it IS the wrapped i64 result of rsq::add / sub / mul.  Everything else widens its operands and is
+    // emitted as before.
+    struct TypedLeaf { std::string narrow; bool neg; int bits; };
+    std::map<std::string, TypedLeaf> typedLeaves;
+    struct TV { std::string text; bool is32 = false, known = false; __int128 lo = 0, hi = 0; };
+    static std::string wide(const TV& v) { return v.is32 ? "((i64)(" + v.text + "))" : v.text; }
+    static TV constantTV(int64_t v) {
+        TV t; t.known = true; t.lo = t.hi = v;
+        t.is32 = v > -(int64_t(1) << 31) && v < (int64_t(1) << 31);
+        t.text = t.is32 ? "((i32)" + std::to_string((long long)v) + ")" : lit64(v);
+        return t;
+    }
+    TV arithTV(int tag, const TV& a, const TV& b) {
+        const __int128 M31 = ((__int128)1 << 31) - 1, M63 = ((__int128)1 << 63) - 1;
+        TV r;
+        if (a.known && b.known) {
+            if (tag == RSQ_E_ADD) { r.lo = a.lo + b.lo; r.hi = a.hi + b.hi; }
+            else if (tag == RSQ_E_SUB) { r.lo = a.lo - b.hi; r.hi = a.hi - b.lo; }
+            else {
+                const __int128 p[4] = {a.lo * b.lo, a.lo * b.hi, a.hi * b.lo, a.hi * b.hi};
+                r.lo = *std::min_element(p, p + 4); r.hi = *std::max_element(p, p + 4);
+            }
+            r.known = r.lo >= -M63 && r.hi <= M63;
+            if (r.known && r.lo == r.hi) return constantTV((int64_t)r.lo);      // (constants fold: `1` as DECIMAL(.., 2) is 100)
+        }
+        const char* op = tag == RSQ_E_ADD ? " + " : tag == RSQ_E_SUB ? " - " : " * ";
+        if (r.known && a.is32 && b.is32) {
+            if (r.lo >= -M31 && r.hi <= M31) {
+                r.is32 = true;
+                const __int128 U24 = ((__int128)1 << 24) - 1, S24 = ((__int128)1 << 23) - 1;
+                if (tag == RSQ_E_MUL && a.lo >= 0 && b.lo >= 0 && a.hi <= U24 && b.hi <= U24)
+                    r.text = "((i32)__umul24((u32)(" + a.text + "), (u32)(" + b.text + ")))";
+                else if (tag == RSQ_E_MUL && a.lo >= -S24 && b.lo >= -S24 && a.hi <= S24 && b.hi <= S24)
+                    r.text = "__mul24(" + a.text + ", " + b.text + ")";
+                else r.text = "(" + a.text + op + b.text + ")";
+            } else if (tag == RSQ_E_MUL && a.lo >= 0 && b.lo >= 0)        // widening 32 x 32 -> 64, by the sign classes
+                r.text = "((i64)((u64)(u32)(" + a.text + ") * (u64)(u32)(" + b.text + ")))";
+            else r.text = "((i64)(" + a.text + ")" + op + "(i64)(" + b.text + "))";
+            return r;
+        }
+        r.text = std::string(tag == RSQ_E_ADD ? "rsq::add(" : tag == RSQ_E_SUB ? "rsq::sub(" : "rsq::mul(") + wide(a) + ", " + wide(b) + ")";
+        return r;
+    }
+    // +, -, * over attributes, constants and casts alone: what emitTyped follows.  Anything else in an input (a CASE, whose conditions
+    // may be answered by truth tables that exist only while the input is first emitted) keeps the text it has.
+    bool pureArithmetic(const Expr* e) {
+        if (symbols.count(expressionName(e))) return true;
+        if (e->structure == LITERAL) return e->tag == RSQ_E_CONSTANT;
+        if (e->structure == UNARY) return (e->tag == RSQ_E_SUM || e->tag == RSQ_E_AS || e->tag == RSQ_E_TYPECAST) && e->child && pureArithmetic(e->child);
+        if (e->structure == BINARY) return (e->tag == RSQ_E_ADD || e->tag == RSQ_E_SUB || e->tag == RSQ_E_MUL) && pureArithmetic(e->child) && pureArithmetic(e->child->next);
+        return false;
+    }
+    TV emitTyped(Expr* e) {
+        TV v;
+        auto untyped = [&]() { v.text = emit(e); return v; };
+        auto it = symbols.find(expressionName(e));
+        if (it != symbols.end()) {
+            auto tl = typedLeaves.find(it->second.var);
+            if (tl == typedLeaves.end()) return untyped();
+            v.text = tl->second.narrow; v.is32 = v.known = true;
+            v.hi = ((__int128)1 << tl->second.bits) - 1; v.lo = tl->second.neg ? -v.hi : 0;
+            return v;
+        }
+        if (!tabled.empty() && tabled.count(e)) return untyped();
+        const bool arith = e->type.tag == RSQ_DECIMAL || e->type.tag == RSQ_BIGINT;
+        if (e->structure == LITERAL && e->tag == RSQ_E_CONSTANT && arith) return constantTV(e->ival);
+        if (e->structure == UNARY && e->child && e->tag != RSQ_E_COUNT) {
+            const Type from = e->child->type, to = e->type;
+            if (e->tag == RSQ_E_SUM || e->tag == RSQ_E_AS) return emitTyped(e->child);
+            if (e->tag == RSQ_E_TYPECAST && to.tag == RSQ_DECIMAL && (from.tag == RSQ_DECIMAL || from.tag == RSQ_BIGINT)) {
+                const int d = to.scale - (from.tag == RSQ_DECIMAL ? from.scale : 0);
+                if (d == 0) return emitTyped(e->child);      // (BIGINT -> DECIMAL(.., 0) is a multiplication by 1)
+                if (d > 0 && d <= 8) return arithTV(RSQ_E_MUL, emitTyped(e->child), constantTV(pow10(d)));
+            }
+            return untyped();
+        }
+        if (e->structure == BINARY && arith && (e->tag == RSQ_E_ADD || e->tag == RSQ_E_SUB || e->tag == RSQ_E_MUL))
+            return arithTV(e->tag, emitTyped(e->child), emitTyped(e->child->next));
+        return untyped();
+    }
+
     std::string emitCase(Expr* e) {   // ExpressionsJitFlounder.h:720-754
         std::string out, close;
         Expr* c = e->child;
@@ -272,8 +358,14 @@ struct Walker {
     // treats such a column as a one-byte tile column (colIsString 0, colTypes "u8") whose row-function parameter is the code, vc_<k>;
     // the row function's first lines turn it into the rsq::Str v_<k> that points into the dictionary (a.d<k>, a kernel argument).
     std::vector<int> colDict;
+    // Scan columns the register aggregation decodes as i32 (typeScanColumns, codegen_agg.cpp): the row function's parameter is n_<k>, and
+    // its first lines widen it into the i64 v_<k> every consumer that is not typed reads.
+    std::vector<char> colTyped;
+    bool typedCol(int k) const { return k >= 0 && k < (int)colTyped.size() && colTyped[(size_t)k] != 0; }
+    static bool envelopeOf(const TableColumn& c, bool& neg, int& bits);
+    bool typeScanColumns();
     bool coded(int k) const { return k >= 0 && k < (int)colDict.size() && colDict[(size_t)k] != 0; }
-    std::string paramName(int k) const { return (coded(k) ? "vc_" : "v_") + std::to_string(k); }
+    std::string paramName(int k) const { return (coded(k) ? "vc_" : typedCol(k) ? "n_" : "v_") + std::to_string(k); }
     std::string dictDecode(int k, const std::string& code) const {
         const std::string K = std::to_string(k), W = std::to_string(colDict[(size_t)k]);
         return "rsq::str(a.d" + K + " + (u32)(" + code + ") * " + W + "u, " + W + ")";
