@@ -151,7 +151,7 @@ void Walker::produceScan(OpNode* o, std::vector<std::string> request) {     // s
     selective = false; compacted = false; stage2Body.clear(); cqLive.clear();
     leadCond.clear(); leadCols.clear(); leadPass = 1.0; leadPassComplete = true;
     pairSplit = std::string::npos; pairCond.clear();
-    strPrefetch.clear(); strPrefetchWidth.clear(); strStaged.clear(); strStagedBytes = 0; postTile.clear(); foldTile.clear(); eg.strWordVars.clear();
+    strPrefetch.clear(); strPrefetchWidth.clear(); strStaged.clear(); strStagedBytes = 0; postTile.clear(); foldTile.clear(); accRegs = 0; eg.strWordVars.clear();
     eg.symbols.clear();
     o->schema.clear();
     const bool narrowScans = sw::flag<sw::RSQ_NARROW_SCANS>();

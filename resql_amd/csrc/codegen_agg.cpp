@@ -926,19 +926,17 @@ void Walker::emitDenseAggregation(OpNode* o) {
     addArg("out", "u64*", 0);
     std::ostringstream ep;
     if (q.aggMode == AggMode::DENSE_REG) {
-        // accumulators in VGPRs, branch-free per-group update.  (An `if (gid == g) acc_g += x` chain gets its
-        // common tail sunk by the compiler into one store through a selected pointer, which forces every
-        // accumulator into scratch.)
-        for (int w = 0; w < W; w++)
-            for (int64_t g = 0; g < D; g++)
-                stateDecl += "    i64 acc_" + std::to_string(w) + "_" + std::to_string((long long)g) + " = (i64)" + identityOf(q.accums[(size_t)w].merge) + ";\n";
         // 32-bit partial sums.  A sum whose input is a count or an owned column of the scan whose statistics bound |value| below
-        // 2^24 adds into an i32 per group, folded into the i64 accumulator every FOLD_TILES tiles of the wave and once behind the
+        // 2^24 adds into an i32 per group, folded into the 64-bit cell every FOLD_TILES tiles of the wave and once behind the
         // tail rows: at most 2 * 32 + 1 rows between folds, so the partial never overflows, and the fold adds the exact sum of
-        // those rows to the wrapping i64 - the same result as row by row.  A 64-bit add is two VALU operations (TPC-H Q1: 89
+        // those rows to the wrapping u64 - the same result as row by row.  A 64-bit add is two VALU operations (TPC-H Q1: 89
         // v_lshl_add_u64 per tile); the 32-bit one is one, and a narrow column's i32 input needs no 64-bit decode.  The bound is
         // the width of |value| in bits, so one plan shape keeps one kernel text across scale factors (l_extendedprice: 24 bits at
         // SF 0.01 and SF 10).  Not behind a wave compaction (stage 2 runs from the drains, not once per row and tile).
+        // The 64-bit cell is the lane's word of the workgroup's LDS image s_lane (the epilogue's, below), not a register pair: a
+        // fold target is touched once in 32 tiles, and two VGPRs per sum and group held all the while (TPC-H Q1: 48 of 172) kept
+        // the kernel at two waves per SIMD.  All waves of the workgroup add into the same 64 words of a cell, hence the LDS
+        // atomic; the image is filled with the identities, behind a barrier, in front of the tile loop.
         std::vector<char> part32((size_t)W, 0);
         if (sw::flag<sw::RSQ_NARROW_SCANS>() && !compacted && pipe.src && !pipe.src->derived) {
             for (int w = 1; w < W; w++) {
@@ -956,6 +954,12 @@ void Walker::emitDenseAggregation(OpNode* o) {
                 if (bits >= 0 && bits <= 24) part32[(size_t)w] = 1;
             }
         }
+        // accumulators in VGPRs, branch-free per-group update.  (An `if (gid == g) acc_g += x` chain gets its
+        // common tail sunk by the compiler into one store through a selected pointer, which forces every
+        // accumulator into scratch.)
+        for (int w = 0; w < W; w++)
+            for (int64_t g = 0; g < D && !part32[(size_t)w]; g++)
+                stateDecl += "    i64 acc_" + std::to_string(w) + "_" + std::to_string((long long)g) + " = (i64)" + identityOf(q.accums[(size_t)w].merge) + ";\n";
         emitInputs(part32);
         // The first row of a group, accumulator 0, is min(row) with row = a.row0 + lr: a 64-bit compare and two selects per update.
         // Below 2^32 - 1 rows the offset lr alone is tracked, as a u32 with the identity 0xffffffff and one unsigned minimum per
@@ -972,9 +976,11 @@ void Walker::emitDenseAggregation(OpNode* o) {
             for (int64_t g = 0; g < D; g++) {
                 const std::string sfx = std::to_string(w) + "_" + std::to_string((long long)g);
                 stateDecl += "    i32 p32_" + sfx + " = 0;\n";
-                fold += "st.acc_" + sfx + " = rsq::add(st.acc_" + sfx + ", (i64)st.p32_" + sfx + "); st.p32_" + sfx + " = 0; ";
+                fold += "rsq::lds_merge<0>(&s_lane[" + std::to_string((long long)((q.accumSlot[(size_t)w] * D + g) * 64)) + " + (threadIdx.x & 63)], (u64)(i64)st.p32_" + sfx +
+                        "); st.p32_" + sfx + " = 0; ";
             }
         }
+        for (int w = 0; w < W; w++) accRegs += (int)D * (part32[(size_t)w] || (w == 0 && fr32) ? 1 : 2);
         if (!fold.empty()) {
             stateDecl += "    int fold_n = 0;\n";
             foldTile = "            if (++st.fold_n == 32) { st.fold_n = 0; " + fold + "}\n";
@@ -1031,11 +1037,15 @@ void Walker::emitDenseAggregation(OpNode* o) {
             // reductions of TPC-H Q1's 42 cells in all 8 waves took 14-20 us of every launch as ds_bpermute butterflies and
             // still 9-11 us as DPP (device timestamps, RSQ_DEBUG_TAIL).
             const int64_t cells = W * D;
-            ep << "    __shared__ u64 s_lane[" << cells * 64 << "];\n";
-            ep << "    for (int i = threadIdx.x; i < " << cells * 64 << "; i += blockDim.x) { const int blk = (i >> 6) / " << D << "; s_lane[i] = " << blockIdentityExpr("blk") << "; }\n";
-            ep << "    __syncthreads();\n";
+            // (with partial sums the image is live from the first fold on: declared and filled in front of the tile loop)
+            std::ostringstream image;
+            image << "    __shared__ u64 s_lane[" << cells * 64 << "];\n";
+            image << "    for (int i = threadIdx.x; i < " << cells * 64 << "; i += blockDim.x) { const int blk = (i >> 6) / " << D << "; s_lane[i] = " << blockIdentityExpr("blk") << "; }\n";
+            image << "    __syncthreads();\n";
+            if (fold.empty()) ep << image.str();
+            else prologue += image.str();
             for (int w = 0; w < W; w++)
-                for (int64_t g = 0; g < D; g++)
+                for (int64_t g = 0; g < D && !part32[(size_t)w]; g++)
                     ep << "    rsq::lds_merge<" << q.accums[(size_t)w].merge << ">(&s_lane[" << (q.accumSlot[(size_t)w] * D + g) * 64 << " + (threadIdx.x & 63)], (u64)st.acc_" << w << "_" << g << ");\n";
             ep << "    __syncthreads();\n";
             ep << "    for (int c = threadIdx.x >> 6; c < " << cells << "; c += blockDim.x >> 6) {\n";

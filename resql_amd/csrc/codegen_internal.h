@@ -448,6 +448,7 @@ struct Walker {
     // region, from which each lane reads its rows' words (ds_read_b64 takes any address on gfx950).  All words of the value then arrive
     // as row-function parameters.
     std::string foldTile;                                  // code behind every tile of the tile loops: the periodic fold of 32-bit partial sums (codegen_agg.cpp)
+    int accRegs = 0;                                       // VGPRs the register aggregation's State holds per lane: 2 per i64 accumulator, 1 per partial sum or u32 first row
     std::string postTile;                                  // code behind the two row_fn calls of a tile in the tile loops ($TILE = the tile's number; wave-uniform)
     std::map<int, int> strStaged;                          // scanned column -> byte offset of its tile in the wave's LDS region
     int strStagedBytes = 0;                                // bytes of that region (128 x the staged widths)
