@@ -74,6 +74,8 @@ typedef struct rsq_config {
                                   * device's memory) */
     int64_t  nested_loops_max_pairs;/* RSQ_ENGINE_NESTED_LOOPS: most (outer rows x inner rows) one nested-loops join may pair; an execution
                                   * beyond it is RSQ_ERR_UNSUPPORTED before any pair is formed (0: 2^36; < 0: RSQ_ERR_INVALID) */
+    int32_t nested_loops_inner_slices;   /* 0: chosen per execution; 1: never split; 2..4096: that many (at most the grid cap); else RSQ_ERR_INVALID */
+    int32_t reserved1;
 } rsq_config;
 
 /* A ReSQL host compiles a statement, executes it ONCE and deletes the plan (reference src/execute.h:213-247).  Two things make that one
@@ -89,6 +91,12 @@ typedef struct rsq_config {
  * tables are not all linked by equalities; RSQ_OP_NESTEDLOOPSJOIN in a plan description).  Such a join costs outer x inner pairs, so
  * a host enables it explicitly and bounds it with rsq_config.nested_loops_max_pairs.  Without the flag those plans are refused
  * (RSQ_ERR_UNSUPPORTED) as before.
+ * The reference folds FROM pieces in creation order, so `from big, small` pairs FEW outer rows with MANY inner rows, and the outer rows
+ * alone do not fill a GPU.  A join whose pairs end in an aggregation therefore splits its inner rows into S slices at launch: S workgroups
+ * per group of outer rows, each pairing those rows with one slice (rsq_config.nested_loops_inner_slices; the policy is
+ * rsq_nested_loops_slices below, the S of an execution rsq_query_nested_loops_slices).  Sums, counts, minima, maxima and a group's first
+ * pair merge in any order, so the result is the same bytes for every S.  A join whose pairs are materialised, or fill a hash join's
+ * build side, keeps S = 1: their output positions follow the scan order.
  * RSQ_ENGINE_DERIVED_MULTI (off by default) lets a multi-GPU handle (rsq_multi_config.base) run plans with derived aggregations; see
  * rsq_multi_* below.  It is a setting of multi-GPU handles only: rsq_ctx_create refuses it (one context runs such plans without it). */
 enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u, RSQ_ENGINE_DERIVED_MULTI = 8u };
@@ -271,6 +279,17 @@ int  rsq_query_report(const rsq_query* q, rsq_report* out);
  * benchmark loop reads ONCE after its timed region instead of a report per step (the reference prints executionTime per
  * query, JitContextFlounder.h:132-150; a loop of 50 steps would otherwise time its own bookkeeping). */
 int  rsq_query_kernel_time_stats(rsq_query* q, double* sum_ms, uint64_t* executions, int32_t reset);
+/* *out = S, the inner-range slices of the most recent execution's top nested-loops pipeline: 1 where it was not split (a materialising
+ * pipeline, a small inner side, nested_loops_inner_slices = 1), 0 for a plan without such a join or before the first execution. */
+int  rsq_query_nested_loops_slices(const rsq_query* q, int32_t* out);
+/* The policy behind S, a pure function (no context, no device).  base_workgroups: the workgroups the outer side's tiles ask for;
+ * max_workgroups: the most this pipeline launches (workgroups per CU x CUs, scaled by the block size, clamped to what is resident);
+ * configured: rsq_config.nested_loops_inner_slices.
+ *   configured == 1 -> 1;  configured >= 2 -> min(configured, max_workgroups);
+ *   configured == 0 -> max(1, min(max_workgroups / base_workgroups, ceil(inner_rows / RSQ_NLJ_MIN_SLICE_ROWS)))
+ * The launch then has S x max(1, min(base_workgroups, max_workgroups / S)) workgroups. */
+#define RSQ_NLJ_MIN_SLICE_ROWS 512     /* fewest inner rows worth a slice of their own: it re-reads the outer rows and flushes its own partial result */
+int32_t rsq_nested_loops_slices(int64_t base_workgroups, int64_t max_workgroups, int64_t inner_rows, int32_t configured);
 /* Generated HIP source and pipeline description of the compiled query (debugging). */
 const char* rsq_query_source(const rsq_query* q);
 const char* rsq_query_explain(const rsq_query* q);
@@ -440,6 +459,8 @@ void rsq_db_destroy(rsq_db* db);
  * rsq_config.nested_loops_max_pairs bounds the statement: total outer rows x total inner rows, checked after the gather and before
  * any outer pipeline runs.  The report counts the inner sides' kernels and bytes, rsq_multi_query_collective_ms includes the gather,
  * rsq_multi_query_merge_name states the split ("nested-loops: outer rows over N shards, inner side gathered (...)" / "replicated").
+ * Every shard slices the inner range of its own launch (nested_loops_inner_slices of the base config, its own outer rows, the whole
+ * inner side's rows).
  *
  * Derived aggregations (an aggregation below a selection, a join or another aggregation; base->engine_flags has RSQ_ENGINE_DERIVED_MULTI;
  * without it rsq_multi_query_compile refuses them, RSQ_ERR_UNSUPPORTED).  Every derived table is built on every shard before the plan's

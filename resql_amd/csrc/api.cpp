@@ -76,6 +76,8 @@ rsq_config readConfig(const rsq_config* cfg, bool multiBase) {
         failInvalid("rsq_config.engine_flags has RSQ_ENGINE_DERIVED_MULTI, a setting of multi-GPU handles (rsq_multi_config.base) only");
     if (c.nested_loops_max_pairs < 0) failInvalid("rsq_config.nested_loops_max_pairs is negative (0: the default of 2^36 pairs)");
     if (c.nested_loops_max_pairs == 0) c.nested_loops_max_pairs = (int64_t)1 << 36;
+    if (c.nested_loops_inner_slices < 0 || c.nested_loops_inner_slices > 4096)
+        failInvalid("rsq_config.nested_loops_inner_slices is " + std::to_string(c.nested_loops_inner_slices) + " (0: chosen per execution, 1: never split, 2..4096: that many)");
     return c;
 }
 }  // namespace rsq
@@ -433,6 +435,23 @@ int rsq_query_report(const rsq_query* q, rsq_report* out) {
 int rsq_query_kernel_time_stats(rsq_query* q, double* sum_ms, uint64_t* executions, int32_t reset) {
     if (!q) return RSQ_ERR_INVALID;
     return guarded(QH(q)->ctx, [&] { queryKernelTimeStats(*QH(q)->q, sum_ms, executions, reset != 0); });
+}
+
+int rsq_query_nested_loops_slices(const rsq_query* q, int32_t* out) {
+    if (!q || !out) return RSQ_ERR_INVALID;
+    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
+    return guarded(h->ctx, [&] {
+        *out = queryNestedLoopsSlices(*h->q);
+    });
+}
+
+// slices of a nested-loops pair loop's inner range (resql_hip.h)
+int32_t rsq_nested_loops_slices(int64_t base_workgroups, int64_t max_workgroups, int64_t inner_rows, int32_t configured) {
+    const int64_t cap = std::max<int64_t>(1, max_workgroups), base = std::max<int64_t>(1, base_workgroups);
+    if (configured == 1) return 1;
+    if (configured >= 2) return (int32_t)std::min<int64_t>(configured, cap);
+    const int64_t byRows = inner_rows <= 0 ? 1 : (inner_rows + RSQ_NLJ_MIN_SLICE_ROWS - 1) / RSQ_NLJ_MIN_SLICE_ROWS;
+    return (int32_t)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(cap / base, byRows), INT32_MAX));
 }
 
 const char* rsq_query_source(const rsq_query* q) { return q ? querySource(*reinterpret_cast<const QueryHandle*>(q)->q) : ""; }

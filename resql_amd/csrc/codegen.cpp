@@ -73,6 +73,30 @@ void Walker::produce(OpNode* o, std::vector<std::string> request) {
 // order the materialisation's count / write passes keep - the reference's order.  All lanes stand at the same inner row at the same
 // moment, so the inner columns are read with wave-uniform scalar loads (rsq::nlj_ld).  The pair's ordinal for the aggregation's
 // first-row tracker is outer row x inner rows + inner position (the order in which the reference meets the pairs).
+//
+// Blocked loads: the loop takes B inner rows per trip - B consecutive rows of every bound non-string column first (rsq::nlj_ld_block:
+// one wide scalar load and one wait per column and block), then the B pairs in inner order, unrolled - and a remainder loop of single
+// rows in the form the whole loop had before.  B is part of the text: 8 where a dense aggregation follows the join without a probe in
+// between, 4 otherwise, halved while B copies of the pair's text are more than 128 lines, 1 (the single-row loop alone) where no bound
+// column is numeric.  The pair's text is generated once and stands in both loops.
+//
+// Inner-range slices: a pipeline that ends in an aggregation runs its pair loop over ONE SLICE of the inner rows per workgroup.  The
+// launch starts S workgroups per virtual workgroup (a.nlj<k>_s, an argument: one text serves every S); the tiles of the outer side are
+// dealt to the virtual ones (finishPipeline: nlj_vb / nlj_vg in place of blockIdx.x / gridDim.x), so every slice meets every outer row
+// once.  Sums, counts, minima, maxima and the first-row tracker merge through atomics in any order, and the pair's ordinal does not
+// depend on who evaluates it: the answer is the same bytes for every S.  A materialisation's positions follow the lanes' scan order and
+// a build's entries their arrival: those pipelines keep the whole range.
+bool Walker::nestedLoopsFeedsAggregation(OpNode* o, bool& probesAbove) {
+    probesAbove = false;
+    for (OpNode* p = o->parent; p; p = p->parent) {
+        if (p->tag == RSQ_OP_AGGREGATION) return true;
+        if (p->tag == RSQ_OP_HASHJOIN) { if (joinPhase[p] == 1) return false; probesAbove = true; }
+        if (p->tag == RSQ_OP_NESTEDLOOPSJOIN) probesAbove = true;
+        if (p->tag == RSQ_OP_MATERIALIZE && !(p->parent && p->parent->tag == RSQ_OP_NESTEDLOOPSJOIN)) return false;
+    }
+    return false;
+}
+
 void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
     NljState& n = q.nljs[(size_t)o->nlj];
     Query& in = *n.sub.query;
@@ -92,10 +116,25 @@ void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
     for (auto& a : from->schema) out.push_back(a);
     o->schema = out;
     addArg(N + "_n", "i64", 0);
+    // the first pair loop of a pipeline whose rows end in an aggregation is sliced (a second one inside it keeps its whole range)
+    bool probesAbove = false;
+    const bool sliced = nestedLoopsFeedsAggregation(o, probesAbove) && pipe.nljSliced < 0;
+    if (sliced) { pipe.nljSliced = o->nlj; addArg(N + "_s", "i64", 1); }
+    n.sliced = sliced;
     openScope("{");
     line("const i64 " + N + "_orow = row;");
-    openScope("for (i64 " + N + "_j = 0; " + N + "_j < a." + N + "_n; " + N + "_j++) {");
+    // the pair's text, once: between two marker lines (the operators above may still put lines in FRONT of the body), at the depth it
+    // has inside the block loop (names of the operators above carry their depth: a loop without numeric columns is not blocked and keeps
+    // the text it always had)
+    bool blocked = false;
+    for (const Attr& at : n.innerSchema) blocked = blocked || !(at.type.isString() && !(at.type.tag == RSQ_CHAR && at.type.len == 1));
+    const std::string mark0 = "//@" + N + " pair", mark1 = "//@" + N + " end";
+    const int loopIndent = indent;
+    line(mark0);
+    indent = loopIndent + (blocked ? 2 : 1);
     line("const i64 row = " + N + "_orow * a." + N + "_n + " + N + "_j; (void)row;");
+    struct Bound { std::string ct, cn, var; };
+    std::vector<Bound> numeric;
     for (size_t k = 0; k < n.innerSchema.size(); k++) {
         const Attr& at = n.innerSchema[k];
         const std::string cn = N + "_c" + std::to_string(k), var = N + "_v" + std::to_string(k);
@@ -105,13 +144,14 @@ void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
         } else {
             const std::string ct = ExprGen::ctype(at.type);
             addArg(cn, "const " + ct + "*", 0);
-            line("const " + ct + " " + var + " = rsq::nlj_ld(a." + cn + ", " + N + "_j);");
+            numeric.push_back({ct, cn, var});
         }
         eg.symbols[at.name] = Sym{var, at.type};
         symbolOrigin[at.name] = -2;
     }
     multiMatchAbove = true;
     pipe.gridPerCU = 8;                // the pair loop is arithmetic, not a stream: latency wants waves
+    const size_t explainAt = explainSteps.size();
     explainSteps.push_back("nested-loops join: every row meets the " + std::to_string(n.innerSchema.size()) + " bound column(s) of the inner side");
     if (!o->exprs.empty()) {
         q.pool.addId(o->exprs[0]);
@@ -119,7 +159,73 @@ void Walker::consumeNestedLoops(OpNode* o, OpNode* from) {
         consume(o->parent, o);
         closeScope();
     } else consume(o->parent, o);
-    closeScope();
+    indent = loopIndent;
+    line(mark1);
+    if (sliced && pipe.sink != SinkKind::AGGREGATE) failUnsupported("internal: the pair loop of " + N + " was sliced, but its pipeline does not aggregate");
+    // ---- the loops around the pair's text ----
+    const size_t m0 = body.find(std::string((size_t)loopIndent * 4, ' ') + mark0 + "\n"), m1 = body.rfind(std::string((size_t)loopIndent * 4, ' ') + mark1 + "\n");
+    if (m0 == std::string::npos || m1 == std::string::npos || m1 < m0) failUnsupported("internal: the pair loop of " + N + " lost its text");
+    const size_t p0 = m0 + (size_t)loopIndent * 4 + mark0.size() + 1;
+    const std::string pairDeep = body.substr(p0, m1 - p0);
+    body.erase(m0);                    // (the end marker was the body's last line)
+    std::string pairFlat;              // ... one level up, for the single-row loop
+    if (!blocked) pairFlat = pairDeep;
+    else for (size_t at = 0; at < pairDeep.size();) {
+        size_t nl = pairDeep.find('\n', at);
+        nl = nl == std::string::npos ? pairDeep.size() : nl + 1;
+        pairFlat += pairDeep.compare(at, 4, "    ") == 0 ? pairDeep.substr(at + 4, nl - at - 4) : pairDeep.substr(at, nl - at);
+        at = nl;
+    }
+    const bool denseAbove = pipe.sink == SinkKind::AGGREGATE && !probesAbove &&
+                            (q.aggMode == AggMode::DENSE_REG || q.aggMode == AggMode::DENSE_LDS_PRIVATE || q.aggMode == AggMode::DENSE_LDS_SHARED || q.aggMode == AggMode::DENSE_GLOBAL);
+    // ... halved while the unrolled block would hold more than 128 lines of the pair's text: 25 groups in registers are 60 lines a pair, and
+    // eight copies of them took hiprtc 10.5 s instead of 1.4 and 18 more VGPRs (docs/KERNELS.md)
+    const int64_t pairLines = std::count(pairDeep.begin(), pairDeep.end(), '\n');
+    int B = !blocked ? 1 : denseAbove ? 8 : 4;
+    while (B > 1 && B * pairLines > 128) B /= 2;
+    n.block = B;
+    const std::string Bs = std::to_string(B);
+    std::string lo = "0", hi = "a." + N + "_n";
+    if (sliced) {
+        stateDecl += "    i64 " + N + "_lo = 0, " + N + "_hi = 0;\n";
+        prologue += "    // the inner range of " + N + " in a." + N + "_s slices of whole blocks: this workgroup is slice nlj_slice of virtual workgroup nlj_vb (of nlj_vg)\n";
+        prologue += "    const u32 nlj_s = (u32)a." + N + "_s;\n";
+        prologue += "    const u32 nlj_vb = blockIdx.x / nlj_s, nlj_slice = blockIdx.x - nlj_vb * nlj_s, nlj_vg = gridDim.x / nlj_s;\n";
+        prologue += "    {\n        const i64 chunk = (((a." + N + "_n + (i64)nlj_s - 1) / (i64)nlj_s + " + std::to_string(B - 1) + ") / " + Bs + ") * " + Bs + ";\n";
+        prologue += "        const i64 lo = (i64)nlj_slice * chunk, hi = lo + chunk;\n";
+        prologue += "        st." + N + "_lo = lo < a." + N + "_n ? lo : a." + N + "_n;\n        st." + N + "_hi = hi < a." + N + "_n ? hi : a." + N + "_n;\n    }\n";
+        lo = "st." + N + "_lo"; hi = "st." + N + "_hi";
+        explainSteps[explainAt] += " [inner range split across workgroups at launch]";
+    }
+    auto singleLoads = [&]() { for (auto& b : numeric) line("const " + b.ct + " " + b.var + " = rsq::nlj_ld(a." + b.cn + ", " + N + "_j);"); };
+    // (loops that do not start at 0 end on `!=`: lo <= hi always, and the wave-uniform counter then compares on the scalar unit, which
+    // has no signed 64-bit less-than - the vector compare it took instead cost a slice-less launch of 1.5 M inner rows 15 %)
+    if (B == 1) {
+        openScope(sliced ? "for (i64 " + N + "_j = " + lo + "; " + N + "_j != " + hi + "; " + N + "_j++) {"
+                         : "for (i64 " + N + "_j = " + lo + "; " + N + "_j < " + hi + "; " + N + "_j++) {");
+        body += pairFlat.substr(0, pairFlat.find('\n') + 1);      // (the ordinal first, as the loop always had it)
+        singleLoads();
+        body += pairFlat.substr(pairFlat.find('\n') + 1);
+        closeScope();
+    } else {
+        line("i64 " + N + "_jb = " + lo + ";");
+        line("const i64 " + N + "_be = " + N + "_jb + ((" + hi + " - " + N + "_jb) & ~(i64)" + std::to_string(B - 1) + ");      // the end of the whole blocks");
+        openScope("for (; " + N + "_jb != " + N + "_be; " + N + "_jb += " + Bs + ") {");
+        for (auto& b : numeric) line(b.ct + " " + b.var + "_b[" + Bs + "]; rsq::nlj_ld_block<" + b.ct + ", " + Bs + ">(a." + b.cn + ", " + N + "_jb, " + b.var + "_b);");
+        line("#pragma unroll");
+        openScope("for (int " + N + "_u = 0; " + N + "_u < " + Bs + "; " + N + "_u++) {");
+        line("const i64 " + N + "_j = " + N + "_jb + " + N + "_u;");
+        body += pairDeep.substr(0, pairDeep.find('\n') + 1);
+        for (auto& b : numeric) line("const " + b.ct + " " + b.var + " = " + b.var + "_b[" + N + "_u];");
+        body += pairDeep.substr(pairDeep.find('\n') + 1);
+        closeScope();
+        closeScope();
+        openScope("for (i64 " + N + "_j = " + N + "_jb; " + N + "_j != " + hi + "; " + N + "_j++) {");
+        body += pairFlat.substr(0, pairFlat.find('\n') + 1);
+        singleLoads();
+        body += pairFlat.substr(pairFlat.find('\n') + 1);
+        closeScope();
+    }
     closeScope();
 }
 

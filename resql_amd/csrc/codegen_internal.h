@@ -534,6 +534,7 @@ struct Walker {
 
     void consumeMaterialize(OpNode* o, OpNode* from);
     void consumeNestedLoops(OpNode* o, OpNode* from);
+    bool nestedLoopsFeedsAggregation(OpNode* o, bool& probesAbove);      // the rows above join `o` end in this pipeline's aggregation (... through a probe or another pair loop)
 
     std::string postTileFor(const std::string& tile);
     int stagedRounds(int col) { return (8 * strPrefetchWidth[col] + 63) / 64; }

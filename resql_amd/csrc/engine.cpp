@@ -811,6 +811,14 @@ void bindNestedLoops(Query& q, NljState& n, int64_t outer, int64_t nInner) {
         failUnsupported("nested-loops join: " + std::to_string((long long)n.nInner) + " inner rows - a 128-row tile of the outer side could emit "
                         "2^32 or more tuples, beyond the materialisation's 32-bit tile counts");
     n.sub.ensureColumns(ctx, n.innerSchema, n.nInner, std::max<int64_t>(n.nInner, 64));
+    // the slices of the inner range in this execution's launch (an aggregating pipeline: codegen.cpp consumeNestedLoops), from the grid the
+    // outer rows ask for, the most the pipeline launches and the inner rows; pipelineGrid and the kernel's argument read it from here
+    n.slices = 1;
+    if (n.sliced && n.pipeline >= 0 && q.pipelines[(size_t)n.pipeline].nljSliced >= 0) {
+        int64_t want, cap;
+        pipelineGridLimits(q, q.pipelines[(size_t)n.pipeline], false, want, cap);
+        n.slices = rsq_nested_loops_slices(want, cap, n.nInner, ctx.cfg.nested_loops_inner_slices);
+    }
 }
 
 NljState& topNestedLoops(Query& q) {
@@ -1504,6 +1512,8 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         for (size_t i = 0; i < q.pipelines.size(); i++) {
             Pipeline& p = q.pipelines[i];           // the first 64 workgroups report: scale to the grid
             if (p.compact) p.stage2Rows = (int64_t)((double)q.hPinned[words + 8 + i] * (double)std::max(1u, p.lastGrid) / (double)std::min(64u, std::max(1u, p.lastGrid)));
+            // (every slice of a nested-loops join's inner range sends the same outer rows to stage 2: one of them counts)
+            if (p.compact && p.nljSliced >= 0) p.stage2Rows /= std::max<int32_t>(1, q.nljs[(size_t)p.nljSliced].slices);
         }
     ctx.errWordClean = (uint32_t)q.hPinned[words] == 0;
     if (((uint32_t)q.hPinned[words] & 256u) && !async && !q.fusedSelectOff) {
@@ -1909,6 +1919,11 @@ void queryReport(const Query& q, rsq_report* out) {
     resolveKernelTime(const_cast<Query&>(q));
     *out = q.report;
 }
+int32_t queryNestedLoopsSlices(const Query& q) {
+    for (const NljState& n : q.nljs) if (n.sub.query && n.outerSrc) return n.slices;      // (the top one: the others run inside its inner side)
+    return 0;
+}
+
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset) {
     resolveKernelTime(q);
     if (sumMs) *sumMs = q.kernelTimeSumMs;

@@ -404,6 +404,7 @@ void partialBuffer(Query& q, void** dptr, int64_t* nMin, int64_t* nMax, int64_t*
 void queryResult(Query& q, rsq_result_view* out);
 void queryReport(const Query& q, rsq_report* out);
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset);
+int32_t queryNestedLoopsSlices(const Query& q);      // S of the most recent execution's top nested-loops pipeline (0: none, or not executed yet)
 const char* querySource(const Query& q);
 const char* queryExplain(const Query& q);
 void destroyQuery(Query* q);

@@ -261,6 +261,7 @@ struct Pipeline {
     int extraLdsBytes = 0;           // LDS a pipeline takes besides the compaction queues (hash aggregation's front table)
     int blockThreads = 256;
     int unroll = 2;
+    int nljSliced = -1;              // the nested-loops join (Query::nljs) whose inner range this pipeline's launch slices: the grid is S x virtual workgroups
     unsigned maxGrid = 0;            // 256-thread workgroups per launch; 0 = gridPerCU per CU
     int gridPerCU = 2;               // 2 for pure streaming pipelines (measured optimum), 8 when the row path
                                      // does dependent random accesses (hash tables, HBM atomics): latency wants waves
@@ -302,6 +303,9 @@ struct NljState {
     const Table* outerSrc = nullptr; // the table the outer pipeline scans (the pair budget counts its rows)
     int pipeline = -1;               // index of that pipeline in Query::pipelines
     int64_t nInner = 0;              // rows of the inner side in this execution (across GPUs: of the whole inner side, all shards' parts)
+    bool sliced = false;             // the pair loop runs over one slice of the inner range per workgroup (an aggregating pipeline: codegen.cpp consumeNestedLoops)
+    int block = 1;                   // B: inner rows per trip of the blocked loop (part of the kernel text; a slice is whole blocks)
+    int32_t slices = 0;              // S of this execution (bindNestedLoops; 1 where the loop is not sliced, 0 before the first execution)
 };
 
 // A derived aggregation: an AGGREGATION with an ancestor other than PROJECTION / MATERIALIZE / ORDERBY (aggregation.h:298-343 hands its
@@ -569,6 +573,7 @@ void allocMatCols(Query& q, int64_t capacity);
 void freeMatCols(Query& q);
 uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTable);
 int residentWorkgroupsPerCU(Kernel* k, int blockThreads);
+void pipelineGridLimits(const Query& q, const Pipeline& p, bool lazyForm, int64_t& want, int64_t& cap);
 unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm = false);
 void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid = 0, unsigned block = 0);
 void waitForStream(Context& ctx);

@@ -56,6 +56,7 @@ uint64_t argValue(Query& q, const Pipeline& p, const ArgSlot& a, int countOnlyTa
         const size_t us = a.name.find('_');
         const NljState& n = q.nljs[(size_t)atoi(a.name.c_str() + 3)];
         if (a.name.compare(us, 2, "_n") == 0) return (uint64_t)n.nInner;
+        if (a.name.compare(us, 2, "_s") == 0) return (uint64_t)std::max<int32_t>(1, n.slices);      // (the grid is a multiple of it: pipelineGrid)
         const size_t k = (size_t)atoi(a.name.c_str() + us + 2);
         return k < n.sub.dCols.size() ? (uint64_t)(uintptr_t)n.sub.dCols[k] : 0;
     }
@@ -112,22 +113,41 @@ int residentWorkgroupsPerCU(Kernel* k, int blockThreads) {
     return n;
 }
 
-unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm) {
+// The workgroups the outer side's tiles ask for (at least 1) and the most the pipeline launches: workgroups per CU x CUs, scaled by the
+// block size, clamped to what is resident.
+void pipelineGridLimits(const Query& q, const Pipeline& p, bool lazyForm, int64_t& want, int64_t& cap) {
     const int64_t tiles = p.src->nRows >> 7;
     const int wavesPerBlock = p.blockThreads / 64;
-    int64_t want = (tiles + (int64_t)wavesPerBlock * p.unroll - 1) / ((int64_t)wavesPerBlock * p.unroll);
+    want = std::max<int64_t>(1, (tiles + (int64_t)wavesPerBlock * p.unroll - 1) / ((int64_t)wavesPerBlock * p.unroll));
     const int64_t maxGrid = p.maxGrid ? (int64_t)p.maxGrid : (int64_t)(lazyForm ? p.gridPerCULazy : p.gridPerCU) * (int64_t)q.ctx.numCUs;
-    int64_t grid = std::min<int64_t>(maxGrid * 256 / p.blockThreads, want);
+    cap = maxGrid * 256 / p.blockThreads;
     const bool clamp = true;
     if (clamp && !p.maxGrid) {
         Kernel* k = lazyForm && p.kernelLazy ? p.kernelLazy : p.kernel;
-        grid = std::min<int64_t>(grid, (int64_t)residentWorkgroupsPerCU(k, p.blockThreads) * (int64_t)q.ctx.numCUs);
+        cap = std::min<int64_t>(cap, (int64_t)residentWorkgroupsPerCU(k, p.blockThreads) * (int64_t)q.ctx.numCUs);
     }
-    return (unsigned)std::max<int64_t>(1, grid);
+    cap = std::max<int64_t>(1, cap);
+}
+
+// ... and the grid: min(want, cap) - or, where the launch slices the inner range of a nested-loops join (Pipeline::nljSliced), S workgroups
+// for each of max(1, min(want, cap / S)) virtual ones.  The kernel divides blockIdx.x and gridDim.x by S (codegen.cpp
+// consumeNestedLoops): the grid of such a pipeline is ALWAYS a multiple of the S its argument nlj<k>_s carries.
+unsigned slicedGrid(const Query& q, const Pipeline& p, int64_t want, int64_t cap) {
+    const int64_t S = p.nljSliced >= 0 ? std::max<int32_t>(1, q.nljs[(size_t)p.nljSliced].slices) : 1;
+    return (unsigned)(S * std::max<int64_t>(1, std::min<int64_t>(want, cap / S)));
+}
+
+unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm) {
+    int64_t want, cap;
+    pipelineGridLimits(q, p, lazyForm, want, cap);
+    return slicedGrid(q, p, want, cap);
 }
 
 void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid, unsigned block) {
     p.lastGrid = grid ? grid : pipelineGrid(q, p);
+    if (p.nljSliced >= 0 && p.lastGrid % (unsigned)std::max<int32_t>(1, q.nljs[(size_t)p.nljSliced].slices) != 0)
+        failRuntime("internal error: " + p.entry + " launches " + std::to_string(p.lastGrid) + " workgroups, no multiple of its " +
+                    std::to_string(q.nljs[(size_t)p.nljSliced].slices) + " inner-range slices");
     std::vector<uint64_t> args;
     for (auto& a : p.args) args.push_back(argValue(q, p, a, countOnlyTable));
     launch(q.ctx, k, p.lastGrid, block ? block : (unsigned)p.blockThreads, args);
@@ -209,8 +229,8 @@ unsigned fewGroupsGrid(Query& q, Pipeline& p, Kernel* k) {
     const int64_t tiles = p.src->nRows >> 7;
     const int wavesPerBlock = p.blockThreads / 64;
     const int64_t want = std::max<int64_t>(1, (tiles + (int64_t)wavesPerBlock * p.unroll - 1) / ((int64_t)wavesPerBlock * p.unroll));
-    if (p.maxGrid) return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)p.maxGrid * 256 / p.blockThreads));
-    return (unsigned)std::min<int64_t>(want, (int64_t)std::min(p.unroll >= 3 ? 6 : 8, residentWorkgroupsPerCU(k, p.blockThreads)) * q.ctx.numCUs);
+    if (p.maxGrid) return slicedGrid(q, p, want, std::max<int64_t>(1, (int64_t)p.maxGrid * 256 / p.blockThreads));
+    return slicedGrid(q, p, want, (int64_t)std::min(p.unroll >= 3 ? 6 : 8, residentWorkgroupsPerCU(k, p.blockThreads)) * q.ctx.numCUs);
 }
 
 void launchPipeline(Query& q, Pipeline& p, int countOnlyTable, bool pass1) {

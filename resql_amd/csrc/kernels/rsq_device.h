@@ -321,6 +321,14 @@ RSQ_DEV i64 str_addr(const Str& s) { return (i64)(u64)reinterpret_cast<unsigned 
 template <typename T> RSQ_DEV T nlj_ld(const T* col, i64 j) {
     return reinterpret_cast<const __attribute__((address_space(4))) T*>(reinterpret_cast<unsigned long long>(col))[j];
 }
+// Rows j .. j + B - 1 of such a column at once (the caller keeps j + B within the column).  The B loads stand next to each other
+// with nothing between them, so the compiler merges them - eight i64 into one s_load_dwordx16, eight i32 into one s_load_dwordx8 -
+// and the B pairs that follow wait for memory once, not once each (docs/KERNELS.md, "The nested-loops join's pair loop").
+template <typename T, int B> RSQ_DEV void nlj_ld_block(const T* col, i64 j, T (&out)[B]) {
+    const __attribute__((address_space(4))) T* p = reinterpret_cast<const __attribute__((address_space(4))) T*>(reinterpret_cast<unsigned long long>(col)) + j;
+#pragma unroll
+    for (int i = 0; i < B; i++) out[i] = p[i];
+}
 RSQ_DEV Str str_from_addr(i64 w, int cap) { return str(reinterpret_cast<const char*>((unsigned long long)(u64)w), cap); }
 
 // LIKE ('%' any run, '_' any one character) with the reference's results (stringLikeCheck, src/qlib/scalar.h:49-118;

@@ -27,13 +27,15 @@ class rsq_config(C.Structure):
                 ("num_threads", C.c_int32), ("emit_machine_code", C.c_int32), ("optimize", C.c_int32),
                 ("device", C.c_int32), ("kernel_cache_dir", C.c_char_p), ("emission_order", C.c_int32),
                 ("compat_flags", C.c_uint32), ("engine_flags", C.c_uint32), ("reserved0", C.c_uint32),
-                ("arena_reserve_bytes", C.c_int64), ("arena_keep_bytes", C.c_int64), ("nested_loops_max_pairs", C.c_int64)]
+                ("arena_reserve_bytes", C.c_int64), ("arena_keep_bytes", C.c_int64), ("nested_loops_max_pairs", C.c_int64),
+                ("nested_loops_inner_slices", C.c_int32), ("reserved1", C.c_int32)]
 
     @classmethod
     def make(cls, device: int, cache_dir=None, print_source: bool = False, emission_order: int = 0, compat_flags: int = 0,
-             engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0, nested_loops_max_pairs: int = 0):
+             engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0, nested_loops_max_pairs: int = 0,
+             nested_loops_inner_slices: int = 0):
         return cls(C.sizeof(cls), 1 if print_source else 0, 0, 0, 1, 1, 0, device, cache_dir, emission_order, compat_flags,
-                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes, nested_loops_max_pairs)
+                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes, nested_loops_max_pairs, nested_loops_inner_slices, 0)
 
 
 class rsq_report(C.Structure):
@@ -128,6 +130,9 @@ def lib():
         L.rsq_query_result.argtypes = [vp, C.POINTER(P.rsq_result_view)]
         L.rsq_query_report.argtypes = [vp, C.POINTER(rsq_report)]
         L.rsq_query_kernel_time_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32]
+        L.rsq_query_nested_loops_slices.argtypes = [vp, C.POINTER(i32)]
+        L.rsq_nested_loops_slices.restype = i32
+        L.rsq_nested_loops_slices.argtypes = [i64, i64, i64, i32]
         L.rsq_query_source.restype = C.c_char_p
         L.rsq_query_source.argtypes = [vp]
         L.rsq_query_explain.restype = C.c_char_p
@@ -197,7 +202,7 @@ EXPORTED_SYMBOLS = [
     "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_total_rows",
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
-    "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_source", "rsq_query_explain",
+    "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_nested_loops_slices", "rsq_nested_loops_slices", "rsq_query_source", "rsq_query_explain",
     "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
@@ -208,6 +213,14 @@ EXPORTED_SYMBOLS = [
     "rsq_multi_shard_rows", "rsq_multi_table_generate", "rsq_multi_table_generate_on_key", "rsq_multi_query_merge_name", "rsq_multi_query_compile", "rsq_multi_query_execute",
     "rsq_multi_query_result", "rsq_multi_query_report", "rsq_multi_query_collective_ms", "rsq_multi_query_destroy",
 ]
+
+NLJ_MIN_SLICE_ROWS = 512      # include/resql_hip.h RSQ_NLJ_MIN_SLICE_ROWS: the policy's floor on inner rows per slice
+
+
+def nested_loops_slices(base_workgroups: int, max_workgroups: int, inner_rows: int, configured: int = 0) -> int:
+    """rsq_nested_loops_slices: the slices a launch with these workgroup counts cuts the inner rows of a nested-loops join into"""
+    return lib().rsq_nested_loops_slices(base_workgroups, max_workgroups, inner_rows, configured)
+
 
 GEN_LINEITEM, GEN_ORDERS, GEN_CUSTOMER, GEN_SYNTHETIC = 0, 1, 2, 3
 RANK_CHUNK_BLOCKS = 1024      # csrc/engine.h RSQ_RANK_CHUNK_BLOCKS: 32-byte bitmap blocks per entry of the rank index's chunk_base
@@ -229,14 +242,15 @@ class Context:
 
     def __init__(self, device: int = 0, cache_dir: Optional[str] = None, print_source: bool = False, emission_order: int = 0,
                  compat_flags: int = 0, engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0,
-                 nested_loops_max_pairs: int = 0):
+                 nested_loops_max_pairs: int = 0, nested_loops_inner_slices: int = 0):
         """emission_order: EMIT_REFERENCE (0: rows of an unsorted aggregation in the reference's hash-table order) or EMIT_ANY;
         compat_flags: rsq_compat bits (COMPAT_JIT_INT16_CAST); engine_flags: rsq_engine_flags bits (ENGINE_DRIVER_ALLOC,
-        ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS); arena_*, nested_loops_max_pairs (0: 2^36 pairs): see rsq_config"""
+        ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS); arena_*, nested_loops_max_pairs (0: 2^36 pairs), nested_loops_inner_slices (0: chosen per execution,
+        1: never split, 2..4096: that many slices of an aggregating nested-loops join's inner rows): see rsq_config"""
         self._L = lib()
         self._cache = cache_dir.encode() if cache_dir else None
         cfg = rsq_config.make(device, self._cache, print_source, emission_order, compat_flags, engine_flags, arena_reserve_bytes, arena_keep_bytes,
-                              nested_loops_max_pairs)
+                              nested_loops_max_pairs, nested_loops_inner_slices)
         h = C.c_void_p()
         rc = self._L.rsq_ctx_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -594,6 +608,13 @@ class Query:
         self.ctx._check(self.ctx._L.rsq_query_kernel_time_stats(self.h, C.byref(s), C.byref(n), 1 if reset else 0))
         return s.value, n.value
 
+    def nested_loops_slices(self) -> int:
+        """S of the most recent execution's top nested-loops pipeline: the slices its launch cut the inner rows into (1: not split;
+        0: no such join in the plan, or not executed yet)"""
+        s = C.c_int32(0)
+        self.ctx._check(self.ctx._L.rsq_query_nested_loops_slices(self.h, C.byref(s)))
+        return s.value
+
     @property
     def source(self) -> str:
         return self.ctx._L.rsq_query_source(self.h).decode()
@@ -666,15 +687,15 @@ class MultiContext:
     """one host process, N GPUs (include/resql_hip.h rsq_multi_*): shard contexts + the RCCL (or peer-copy) group-by merge"""
 
     def __init__(self, devices: Sequence[int], merge: int = MERGE_AUTO, cache_dir: Optional[str] = None, emission_order: int = 0,
-                 compat_flags: int = 0, engine_flags: int = 0, nested_loops_max_pairs: int = 0):
-        """engine_flags, nested_loops_max_pairs: as for Context, on every shard (ENGINE_DERIVED_MULTI, for these handles only, runs derived
+                 compat_flags: int = 0, engine_flags: int = 0, nested_loops_max_pairs: int = 0, nested_loops_inner_slices: int = 0):
+        """engine_flags, nested_loops_max_pairs, nested_loops_inner_slices: as for Context, on every shard (ENGINE_DERIVED_MULTI, for these handles only, runs derived
         aggregations across the shards; ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
         by its outer side's rows; the budget bounds the whole statement's pairs)"""
         self._L = lib()
         self._devs = (C.c_int32 * len(devices))(*devices)
         self._cache = cache_dir.encode() if cache_dir else None
         self._base = rsq_config.make(0, self._cache, False, emission_order, compat_flags, engine_flags,
-                                     nested_loops_max_pairs=nested_loops_max_pairs)
+                                     nested_loops_max_pairs=nested_loops_max_pairs, nested_loops_inner_slices=nested_loops_inner_slices)
         cfg = rsq_multi_config(C.sizeof(rsq_multi_config), len(devices), C.pointer(self._base), self._devs, merge, 0)
         h = C.c_void_p()
         rc = self._L.rsq_multi_create(C.byref(cfg), C.byref(h))

@@ -8,7 +8,10 @@ The FROM order decides the sides: the reference folds pieces in creation order, 
 Each case runs in a child process of its own under `timeout -k 10`; a case that fails or times out ends the script there.
 VALU bound = pairs x VALU instructions per pair (read off the kernel's ISA, tools/isa.sh) / (256 CUs x 64 lanes x 2.4 GHz).
 
-usage: python tools/nested_loops_timing.py [--reps N] [--out FILE.jsonl]
+--slices N is the context's nested_loops_inner_slices (0: the engine chooses per execution, 1: the inner range is never split); every
+output line holds it, and the slice count the last execution launched with.
+
+usage: python tools/nested_loops_timing.py [--reps N] [--slices N] [--out FILE.jsonl]
 """
 import argparse
 import json
@@ -27,12 +30,13 @@ CLOCK_HZ = 2.4e9
 LANES_PER_CLOCK = 256 * 64
 
 
-def child(name, reps):
+def child(name, reps, slices):
     sys.path.insert(0, ROOT)
     from resql_amd import engine, tpch_full
     sql, outer, inner, valu = CASES[name]
     db = tpch_full.database(1.0)                     # (every column filled: o_totalprice is not one the TPC-H statements read)
-    ctx = engine.Context(device=0, engine_flags=engine.ENGINE_NESTED_LOOPS, nested_loops_max_pairs=1 << 40)
+    ctx = engine.Context(device=0, engine_flags=engine.ENGINE_NESTED_LOOPS, nested_loops_max_pairs=1 << 40,
+                         nested_loops_inner_slices=slices)
     tabs = [ctx.table(db[k]) for k in sorted(db)]
     q = ctx.sql_compile(sql, tabs)
     q.execute()                                      # (first execution: kernels loaded, inner side sized)
@@ -43,7 +47,8 @@ def child(name, reps):
     best = min(kernel_s)
     pairs = db[outer].n_rows * db[inner].n_rows
     bound = pairs * valu / (LANES_PER_CLOCK * CLOCK_HZ)
-    print(json.dumps({"case": name, "sql": sql, "pairs": pairs, "kernel_s_best": best, "pairs_per_s": pairs / best,
+    print(json.dumps({"case": name, "sql": sql, "pairs": pairs, "slices": slices, "slices_launched": q.nested_loops_slices(), "kernel_s": kernel_s,
+                      "kernel_s_best": best, "pairs_per_s": pairs / best,
                       "valu_per_pair": valu, "valu_bound_s": bound, "fraction_of_valu_bound": bound / best, "result_rows": q.result().n_rows}))
     q.close()
     for t in tabs:
@@ -55,14 +60,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--slices", type=int, default=0)
+    ap.add_argument("--only", choices=sorted(CASES), help="run this case alone")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.reps)
+        child(a.child, a.reps, a.slices)
         return
     lines = []
     for name in CASES:
-        pr = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps)],
+        if a.only and name != a.only:
+            continue
+        pr = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
+                             "--slices", str(a.slices)],
                             capture_output=True, text=True)
         if pr.returncode != 0:
             sys.stderr.write(f"{name}: exit status {pr.returncode}\n{pr.stdout[-2000:]}\n{pr.stderr[-4000:]}\n")
