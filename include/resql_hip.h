@@ -367,6 +367,14 @@ int   rsq_prim_merge_group_rows(rsq_ctx* ctx, const int64_t* rows /* [n * stride
 int   rsq_prim_topk_select(rsq_ctx* ctx, const int64_t* rows /* [n_rows * stride] */, int64_t n_rows, int64_t rows_upper_bound, int32_t stride,
                            int32_t key_word, int32_t is32, int32_t desc, int64_t want, int32_t form, const uint64_t* image_range /* [2], form 1 */,
                            int64_t capacity, int64_t* cand_out /* [capacity * stride] */, uint32_t* cand_count, uint32_t* notes);
+/* What the statistics pass left beside a column (aot_kernels.hip computeColumnStats), copied back as it lies: which 0 the narrow image
+ * (rows values of `width` bytes, each the row's value minus `base`), 1 the dictionary's entries (as many as the column has, each as wide as
+ * the column, in memcmp order), 2 the dictionary codes (one byte per row).  info = {width in bytes (0: no narrow image), base, dictionary
+ * entries (0: no dictionary), rows} is filled whatever `which` and `bytes` are; with bytes == 0 nothing else happens.  No kernel runs and
+ * no state changes.  RSQ_ERR_INVALID for null pointers, a `which` outside 0..2, an unknown column and a read beyond rows * width,
+ * entries * column width or rows.  A compile-only context has no images: which 0 and 2 with bytes > 0 are RSQ_ERR_UNSUPPORTED there, and
+ * which 1 is the host's copy of the entries. */
+int   rsq_table_read_image(rsq_ctx* ctx, const rsq_table* t, const char* column, int32_t which, void* host_dst, size_t bytes, int64_t info[4]);
 
 /* ---- SQL text in front of the path --------------------------------------
  * The reference turns SQL text into an operator tree with parseSql (src/parser/parseSql.h:130-166:

@@ -56,6 +56,10 @@ __global__ void __launch_bounds__(256) k_byteset(const unsigned char* __restrict
     if (threadIdx.x < 8 && s[threadIdx.x]) atomicOr(&out[threadIdx.x], s[threadIdx.x]);
 }
 
+// the columns whose statistics are a range and an order (engine.h ColumnStats: "numeric / date columns"): by TAG, the same for the host's
+// pass and the device's.  Whatever else is no string by Type::isString() - a CHAR(0), which holds no bytes to read - has no statistics.
+static bool rangeStatsType(const Type& t) { return t.tag == RSQ_INT || t.tag == RSQ_DATE || t.tag == RSQ_BIGINT || t.tag == RSQ_DECIMAL; }
+
 static void hostStats(Table& t) {
     for (auto& c : t.cols) {
         c.stats = ColumnStats();
@@ -68,8 +72,7 @@ static void hostStats(Table& t) {
             for (int v = 0; v < 256; v++) if (seen[v]) c.stats.distinctBytes.push_back((uint8_t)v);
             c.stats.min = c.stats.distinctBytes.front(); c.stats.max = c.stats.distinctBytes.back();
             c.stats.valid = true;
-        } else if (w == 4 || w == 8) {
-            if (c.type.isString()) continue;
+        } else if (rangeStatsType(c.type)) {
             int64_t mn = INT64_MAX, mx = INT64_MIN, prev = INT64_MIN;
             bool asc = true, strict = true;
             for (int64_t i = 0; i < t.nRows; i++) {
@@ -342,7 +345,11 @@ static void buildNarrowImages(Context& ctx, Table& t) {
 
 void computeColumnStats(Context& ctx, Table& t) {
     if (ctx.device < 0) { hostStats(t); buildNarrowImages(ctx, t); return; }
-    if (t.nRows == 0) { buildNarrowImages(ctx, t); return; }
+    if (t.nRows == 0) {          // (nothing to read: no statistics, as hostStats leaves them, and whatever images there were go)
+        for (auto& c : t.cols) c.stats = ColumnStats();
+        buildNarrowImages(ctx, t);
+        return;
+    }
     RSQ_HIP(hipSetDevice(ctx.device));
     i64* dmm = (i64*)ctx.alloc(4 * sizeof(i64));
     unsigned* dset = (unsigned*)ctx.alloc(8 * sizeof(unsigned));
@@ -358,7 +365,7 @@ void computeColumnStats(Context& ctx, Table& t) {
             RSQ_HIP(hipStreamSynchronize(ctx.stream));
             for (int v = 0; v < 256; v++) if (h[v >> 5] & (1u << (v & 31))) c.stats.distinctBytes.push_back((uint8_t)v);
             if (!c.stats.distinctBytes.empty()) { c.stats.min = c.stats.distinctBytes.front(); c.stats.max = c.stats.distinctBytes.back(); c.stats.valid = true; }
-        } else if (!c.type.isString()) {
+        } else if (rangeStatsType(c.type)) {
             i64 init[4] = {0x7fffffffffffffffll, (i64)0x8000000000000000ull, 0, 0};
             RSQ_HIP(hipMemcpyAsync(dmm, init, 32, hipMemcpyHostToDevice, ctx.stream));
             if (c.type.tag == RSQ_INT) hipLaunchKernelGGL(k_minmax<int>, dim3(grid), dim3(256), 0, ctx.stream, (const int*)c.dptr, (i64)t.nRows, dmm);

@@ -353,6 +353,30 @@ int rsq_table_read_column(rsq_ctx* ctx, const rsq_table* t, const char* name, vo
     });
 }
 
+int rsq_table_read_image(rsq_ctx* ctx, const rsq_table* t, const char* name, int32_t which, void* host_dst, size_t bytes, int64_t info[4]) {
+    if (!ctx || !t || !name || !info || which < 0 || which > 2 || (bytes && !host_dst)) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        const Table* tb = reinterpret_cast<const Table*>(t);
+        if (tb->ctx != C(ctx)) failInvalid("the table belongs to another context");
+        int ci = tb->findCol(name);
+        if (ci < 0) failInvalid(std::string("no such column: ") + name);
+        const TableColumn& c = tb->cols[(size_t)ci];
+        info[0] = c.nw; info[1] = c.nw ? c.nbase : 0; info[2] = c.dictN; info[3] = tb->nRows;
+        if (!bytes) return;
+        const bool device = C(ctx)->device >= 0;
+        if (!device && which != 1) failUnsupported("a compile-only context keeps no narrow image and no dictionary codes");
+        const size_t have = which == 0 ? (size_t)tb->nRows * (size_t)c.nw
+                          : which == 1 ? (size_t)c.dictN * (size_t)columnWidth(c.type)
+                                       : (c.dictN ? (size_t)tb->nRows : 0);
+        if (bytes > have) failInvalid("read beyond the image");
+        if (!device) { memcpy(host_dst, c.dict.data(), bytes); return; }
+        const void* src = which == 0 ? c.nptr : which == 1 ? c.dictPtr : c.codePtr;
+        if (!src) failInvalid("the column has no such image");
+        RSQ_HIP(hipStreamSynchronize(C(ctx)->stream));
+        RSQ_HIP(hipMemcpy(host_dst, src, bytes, hipMemcpyDeviceToHost));
+    });
+}
+
 void rsq_table_destroy(rsq_table* t) { delete T(t); }
 
 int rsq_query_compile(rsq_ctx* ctx, const rsq_plan_desc* plan, rsq_table* const* tables, int32_t n_tables, rsq_query** out) {

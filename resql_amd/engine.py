@@ -106,6 +106,7 @@ def lib():
         L.rsq_table_rows.restype = i64
         L.rsq_table_rows.argtypes = [vp]
         L.rsq_table_read_column.argtypes = [vp, vp, C.c_char_p, vp, C.c_size_t]
+        L.rsq_table_read_image.argtypes = [vp, vp, C.c_char_p, i32, vp, C.c_size_t, C.POINTER(i64)]
         L.rsq_table_set_first_row.argtypes = [vp, i64]
         L.rsq_table_refresh_stats.argtypes = [vp]
         L.rsq_table_append.argtypes = [vp, vp]
@@ -198,7 +199,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "rsq_ctx_create", "rsq_ctx_destroy", "rsq_last_error", "rsq_table_create", "rsq_table_create_device",
-    "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column",
+    "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
     "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_total_rows",
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
@@ -384,7 +385,7 @@ class Context:
         d = t.to_c(keep)
         h = C.c_void_p()
         self._check(self._L.rsq_table_create(self.h, C.byref(d), C.byref(h)))
-        return DeviceTable(self, h, t.name)
+        return DeviceTable(self, h, t.name, {c.name: c.type.width for c in t.columns})
 
     def table_from_device(self, name: str, n_rows: int, columns) -> "DeviceTable":
         """columns: list of (name, SqlType, device_pointer_or_None); pointers stay owned by the caller"""
@@ -394,7 +395,7 @@ class Context:
         d = P.rsq_table_desc(); d.name = name.encode(); d.n_rows = n_rows; d.n_cols = len(columns); d.cols = cols
         h = C.c_void_p()
         self._check(self._L.rsq_table_create_device(self.h, C.byref(d), C.byref(h)))
-        return DeviceTable(self, h, name)
+        return DeviceTable(self, h, name, {cn: ct.width for cn, ct, _ in columns})
 
     def load_tbl(self, schema: P.Table, path: str, terminator: str = "|", threads: int = 0) -> "DeviceTable":
         """BULK INSERT of a '.tbl' text file into a table with `schema`'s column names and types"""
@@ -403,7 +404,7 @@ class Context:
         d = bare.to_c(keep)
         h = C.c_void_p()
         self._check(self._L.rsq_table_load_tbl(self.h, C.byref(d), path.encode(), terminator.encode()[:1], threads, C.byref(h)))
-        return DeviceTable(self, h, schema.name)
+        return DeviceTable(self, h, schema.name, {c.name: c.type.width for c in schema.columns})
 
     def generate(self, kind: int, n_rows: int, sf: float, row0: int = 0, param: int = 0,
                  seed: int = 20240613) -> "DeviceTable":
@@ -496,8 +497,9 @@ class Context:
 
 
 class DeviceTable:
-    def __init__(self, ctx: Context, h, name: str):
+    def __init__(self, ctx: Context, h, name: str, widths: Optional[dict] = None):
         self.ctx, self.h, self.name = ctx, h, name
+        self.widths = dict(widths or {})          # bytes per row of the columns, by name, where the schema came through Python (read_image)
         ctx._adopt(self)
 
     @property
@@ -538,6 +540,26 @@ class DeviceTable:
         n = self.n_rows if count is None else count
         out = np.empty(n, dtype=dtype)
         self.ctx._check(self.ctx._L.rsq_table_read_column(self.ctx.h, self.h, name.encode(), out.ctypes.data, out.nbytes))
+        return out
+
+    def image_info(self, name: str) -> tuple:
+        """(narrow image's width in bytes or 0, its base, dictionary entries or 0, rows) of a column (rsq_table_read_image)"""
+        info = (C.c_int64 * 4)()
+        self.ctx._check(self.ctx._L.rsq_table_read_image(self.ctx.h, self.h, name.encode(), 0, None, 0, info))
+        return tuple(int(v) for v in info)
+
+    def read_image(self, name: str, which: int) -> np.ndarray:
+        """the whole of a column's narrow image (which 0), dictionary entries (1) or dictionary codes (2), as bytes; empty if there is none"""
+        if which not in (0, 1, 2):
+            raise ValueError("read_image: which is 0 (narrow image), 1 (dictionary entries) or 2 (dictionary codes)")
+        width, _, entries, rows = self.image_info(name)
+        if which == 1 and entries and name not in self.widths:
+            raise KeyError(f"read_image: the width of column {name} is not known to this handle")
+        n = (rows * width, entries * self.widths.get(name, 0), rows if entries else 0)[which]
+        out = np.empty(n, dtype=np.uint8)
+        if n:
+            info = (C.c_int64 * 4)()
+            self.ctx._check(self.ctx._L.rsq_table_read_image(self.ctx.h, self.h, name.encode(), which, out.ctypes.data, n, info))
         return out
 
     def close(self):

@@ -15,7 +15,10 @@ T = P.TypeInit
 NOTE = "the build table's own columns"
 
 
-def _dim(m, kind, seed=3):
+STRIDE = 1024 * 256          # the grid stride of the statistics' k_minmax (aot_kernels.hip computeColumnStats; tests/statcases.py)
+
+
+def _dim(m, kind, seed=3, at=None):
     rng = np.random.default_rng(seed)
     if kind == "dense":
         dk = np.arange(7, 7 + m, dtype=np.int32)
@@ -23,6 +26,12 @@ def _dim(m, kind, seed=3):
         dk = (7 + np.cumsum(rng.integers(1, 5, m))).astype(np.int32)
     elif kind == "shuffled":
         dk = rng.permutation(np.arange(7, 7 + m, dtype=np.int32))
+    elif kind == "dup_at":      # ascending, the key of row at[0] again in row at[1] = at[0] + 1
+        dk = np.arange(7, 7 + m, dtype=np.int32)
+        dk[at[1]] = dk[at[0]]
+    elif kind == "descent_at":      # unique keys, ascending but for row at[1], one below row at[0] (a key no other row has)
+        dk = (7 + 2 * np.arange(m)).astype(np.int32)
+        dk[at[1]] = dk[at[0]] - 1
     else:      # "dups": ascending, one key twice
         dk = np.arange(7, 7 + m, dtype=np.int32)
         dk[m // 2] = dk[m // 2 - 1]
@@ -33,6 +42,9 @@ def _dim(m, kind, seed=3):
     if kind == "dups":      # (a whole row twice: which of two rows of one key a single-match probe finds is the reference's insertion order)
         for col in (names, flag, dw, dd):
             col[m // 2] = col[m // 2 - 1]
+    if kind == "dup_at":
+        for col in (names, flag, dw, dd):
+            col[at[1]] = col[at[0]]
     return P.Table("dim", [P.Column("dk", T.INT(), dk), P.Column("dname", T.CHAR(9), names), P.Column("dflag", T.CHAR(1), flag),
                            P.Column("dw", T.BIGINT(), dw), P.Column("dd", T.DATE(), dd)], m), dk
 
@@ -77,6 +89,20 @@ def test_bare_scan_build_in_key_order_is_read_in_place(gpu_ctx, kind, direct, si
     assert (NOTE in explain) == (direct is not None), explain
     if direct:
         assert direct in explain
+
+
+@pytest.mark.parametrize("single", [True, False])
+@pytest.mark.parametrize("at", [(0, 1), (STRIDE - 1, STRIDE), (STRIDE, STRIDE + 1)], ids=["first_rows", "across_the_stride", "last_rows"])
+@pytest.mark.parametrize("kind", ["dup_at", "descent_at"])
+def test_one_flaw_in_the_key_order_keeps_the_table_wherever_it_lies(gpu_ctx, kind, at, single):
+    """the in-place form rests on stats.strictlyAscending alone - nothing checks the keys again: one repeated key, or one key out of order,
+    in the first two rows, across the grid stride of the statistics kernel or in the last two rows must be seen"""
+    m = STRIDE + 2
+    assert at[1] == at[0] + 1 and at[1] < m and (STRIDE, STRIDE + 1) == (m - 2, m - 1)
+    dim, dk = _dim(m, kind, at=at)
+    assert len(np.unique(dk)) == (m - 1 if kind == "dup_at" else m) and int(np.sum(np.diff(dk.astype(np.int64)) <= 0)) == 1
+    explain = _run(gpu_ctx, _plan(dim, _fact(300_000, dk), single=single), executions=2)
+    assert NOTE not in explain, explain
 
 
 def test_a_selection_in_front_of_the_build_keeps_the_table(gpu_ctx):
