@@ -344,7 +344,8 @@ int   rsq_prim_rank_place(rsq_ctx* ctx, const uint32_t* blocks /* [n_blocks * 8]
  * result is copied from whichever of the two buffer pairs holds it; with n <= 1 nothing runs and the input is the answer. */
 int   rsq_prim_radix_sort_pairs(rsq_ctx* ctx, const uint64_t* keys /* [n] */, const uint32_t* vals /* [n] */, int64_t n, int32_t key_bits,
                                 uint64_t* keys_out /* [n] */, uint32_t* vals_out /* [n] */, uint32_t* notes);
-/* out[i] = min(in[0..i]): the running minimum of the device replay of the reference's hash table (k_scanmin_chunks / _totals / _apply). */
+/* out[i] = min(in[0..i]): the running minimum of the device replay of the reference's hash table (k_scanmin_chunks / _totals / _apply,
+ * built on the scan toolkit of resql_amd/csrc/scan_device.h). */
 int   rsq_prim_running_min(rsq_ctx* ctx, const int64_t* in /* [n] */, int64_t n, int64_t* out /* [n] */, uint32_t* notes);
 /* mergeGroupRows: n group rows [first row | n_tab table words | accumulators] of `stride` words merged by key.  Key k is row word
  * key_word[k] of type key_type[k] (rsq_type_tag); key_len[k] is 0 for a number, 1 for CHAR(1), the declared length for CHAR(n) /

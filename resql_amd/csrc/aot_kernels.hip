@@ -8,11 +8,9 @@
 #include <cstring>
 
 #include "engine_internal.h"
+#include "scan_device.h"
 
 namespace rsq {
-
-typedef long long i64;
-typedef unsigned long long u64;
 
 // ------------------------------------------------------------------------------------------------
 // statistics
@@ -789,15 +787,8 @@ __global__ void __launch_bounds__(256) k_compact_entries(const i64* __restrict__
             f[r] = s < cap ? first[s] : 0x7fffffffffffffffll;
             mine += f[r] != 0x7fffffffffffffffll ? 1u : 0u;
         }
-        // exclusive prefix of `mine` over the workgroup: wave scan (shuffles), then the four wave totals
-        unsigned incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned v = (unsigned)__shfl_up((int)incl, d, 64); if (lane >= d) incl += v; }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        unsigned before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const unsigned c = s_wave[w]; if (w < wave) before += c; total += c; }
+        unsigned total;
+        const unsigned before = block_scan<256, unsigned, ScanSum>(mine, s_wave, &total);      // the occupied slots in front of this thread's
         // where the chunk's rows go: one returning atomic per chunk on the row counter
         if (t == 0) s_base = total ? atomicAdd(count, total) : 0u;
         __syncthreads();
@@ -805,7 +796,7 @@ __global__ void __launch_bounds__(256) k_compact_entries(const i64* __restrict__
             // the occupied slots are sparse (a few per cent): gather them into an LDS list first so that the row copies run
             // with every lane busy — copying straight from the per-thread slots executed the (divergent) copy body once per
             // slot position of the wave, 13 of 16 times for Q3, each a chain of dependent loads and stores: 42 us
-            unsigned lp = before + incl - mine;
+            unsigned lp = before;
 #pragma unroll
             for (int r = 0; r < COMPACT_PER_THREAD; r++)
                 if (f[r] != 0x7fffffffffffffffll) s_list[lp++] = (unsigned)(r * 256 + t);
@@ -1327,32 +1318,14 @@ void selectTopCandidates(Context& ctx, const int64_t* rows, int stride, int keyW
 // the other and, inside a partition, workgroups in order; partStart[p] / partStart[P] are the partition bounds.
 // One workgroup: the matrix is small (workgroups x partitions words) and every column walk is coalesced across threads.
 // ------------------------------------------------------------------------------------------------
-// step 1, one workgroup per partition p: exclusive prefix of column p over the workgroups (block scan in LDS, chunks of
-// 1024 workgroups with a carry), the column total goes to totals[p]
-__global__ void __launch_bounds__(1024) k_part_within(unsigned* __restrict__ m, int nWG, int P, u64* __restrict__ totals) {
-    __shared__ u64 s[1024];          // 64-bit: the host rejects totals >= 2^32 and must see them unwrapped
-    __shared__ u64 carry;
-    const int p = blockIdx.x, t = threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nWG; base += 1024) {
-        const int wg = base + t;
-        const u64 c = wg < nWG ? (u64)m[(size_t)wg * P + p] : 0ull;
-        s[t] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {                  // Hillis-Steele inclusive scan
-            const u64 v = t >= d ? s[t - d] : 0ull;
-            __syncthreads();
-            s[t] += v;
-            __syncthreads();
-        }
-        const u64 before = carry;
-        if (wg < nWG) m[(size_t)wg * P + p] = (unsigned)(before + s[t] - c);
-        __syncthreads();
-        if (t == 1023) carry = before + s[1023];
-        __syncthreads();
-    }
-    if (t == 0) totals[p] = carry;
+// step 1, one workgroup per partition p: exclusive prefix of column p over the workgroups (batched_exclusive_scan: batches of
+// SCAN_BATCH workgroups with a carry), the column total goes to totals[p]
+__global__ void __launch_bounds__(SCAN_BATCH) k_part_within(unsigned* __restrict__ m, int nWG, int P, u64* __restrict__ totals) {
+    const int p = blockIdx.x;
+    // 64-bit: the host rejects totals >= 2^32 and must see them unwrapped
+    const u64 total = batched_exclusive_scan<u64, ScanSum>((i64)nWG, [&](i64 wg) { return (u64)m[(size_t)wg * P + p]; },
+                                                           [&](i64 wg, u64 before) { m[(size_t)wg * P + p] = (unsigned)before; });
+    if (threadIdx.x == 0) totals[p] = total;
 }
 // step 2, one workgroup: exclusive scan of the partition totals -> partStart[0..P], grand total
 __global__ void __launch_bounds__(1024) k_part_starts(const u64* __restrict__ totals, int P, unsigned* __restrict__ partStart, u64* total) {
@@ -1371,7 +1344,7 @@ __global__ void __launch_bounds__(1024) k_part_starts(const u64* __restrict__ to
 
 void partitionOffsets(Context& ctx, uint32_t* counts, int nWorkgroups, int nPartitions, uint64_t* totals, uint32_t* partStart, uint64_t* total) {
     if (nPartitions > 4096) throw Error(RSQ_ERR_UNSUPPORTED, "more than 4096 aggregation partitions");
-    hipLaunchKernelGGL(k_part_within, dim3((unsigned)nPartitions), dim3(1024), 0, ctx.stream, (unsigned*)counts, nWorkgroups, nPartitions, (u64*)totals);
+    hipLaunchKernelGGL(k_part_within, dim3((unsigned)nPartitions), dim3(SCAN_BATCH), 0, ctx.stream, (unsigned*)counts, nWorkgroups, nPartitions, (u64*)totals);
     hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(1024), 0, ctx.stream, (const u64*)totals, nPartitions, (unsigned*)partStart, (u64*)total);
     RSQ_HIP(hipGetLastError());
 }
@@ -1384,139 +1357,83 @@ void partitionOffsets(Context& ctx, uint32_t* counts, int nWorkgroups, int nPart
 // once and writes the offsets twice: 4 + 16 bytes per slot, bandwidth-bound like the rocPRIM scan it replaces.
 // `temp` holds the chunk totals and bases: scanTempBytes(n).
 // ------------------------------------------------------------------------------------------------
-#define SCAN_CHUNK 4096
-// (four sub-blocks of 1024 counts per chunk, a thread takes four neighbouring counts of each: one 16-byte load and two 16-byte stores per
+// (four sub-blocks of SCAN_BATCH counts per chunk, a thread takes four neighbouring counts of each: one 16-byte load and two 16-byte stores per
 // lane, unit stride across the wave.  A thread walking 16 consecutive counts - stores 128 bytes apart across the lanes - took 168 us for
 // the 30 M lane slots of a 60 M-row materialisation; this form: about a third.)
+// first of thread t's four counts of sub-block sb
+__device__ __forceinline__ i64 scan_subblock_index(int sb) { return (i64)blockIdx.x * SCAN_CHUNK + (i64)sb * SCAN_BATCH + (i64)threadIdx.x * 4; }
+// loads the thread's four counts behind i0 (zero beyond n)
+__device__ __forceinline__ void scan_subblock_load(const unsigned* __restrict__ counts, i64 n, i64 i0, unsigned (&c)[4]) {
+    c[0] = c[1] = c[2] = c[3] = 0u;
+    if (i0 + 3 < n) { const uint4 v = *reinterpret_cast<const uint4*>(counts + i0); c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w; }
+    else for (int j = 0; j < 4; j++) if (i0 + j < n) c[j] = counts[i0 + j];
+}
+// the four offsets behind r0: two 16-byte stores, element by element at the ragged end
+__device__ __forceinline__ void scan_subblock_store(u64* __restrict__ offs, i64 n, i64 i0, const unsigned (&c)[4], u64 r0) {
+    const u64 r1 = r0 + c[0], r2 = r1 + c[1], r3 = r2 + c[2];
+    if (i0 + 3 < n) {
+        ulonglong2* o = reinterpret_cast<ulonglong2*>(offs + i0);
+        o[0] = make_ulonglong2(r0, r1); o[1] = make_ulonglong2(r2, r3);
+    } else {
+        const u64 r[4] = {r0, r1, r2, r3};
+        for (int j = 0; j < 4; j++) if (i0 + j < n) offs[i0 + j] = r[j];
+    }
+}
+// (This kernel keeps its own ladder and wave-total stage, over the header's wave_shfl_up, where its neighbours call block_scan: through
+// block_scan the compiler computed the ladder's six shuffle addresses in front of it, 710 instructions and 42 VGPRs against 689 and 38, and
+// the kernel measured 0.2 us, 3 %, above its former self.  This body compiles to the former instructions one for one.)
 __global__ void __launch_bounds__(256) k_scan_chunks(const unsigned* __restrict__ counts, u64* __restrict__ offs, i64 n, u64* __restrict__ chunkTotal) {
     __shared__ u64 s_wave[2][4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     u64 carry = 0;
 #pragma unroll
-    for (int sb = 0; sb < 4; sb++) {
-        const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + (i64)sb * 1024 + (i64)t * 4;
-        unsigned c[4] = {0u, 0u, 0u, 0u};
-        if (i0 + 3 < n) { const uint4 v = *reinterpret_cast<const uint4*>(counts + i0); c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w; }
-        else for (int j = 0; j < 4; j++) if (i0 + j < n) c[j] = counts[i0 + j];
+    for (int sb = 0; sb < 4; sb++) {                      // (four counts in registers at a time: eight waves per SIMD)
+        const i64 i0 = scan_subblock_index(sb);
+        unsigned c[4];
+        scan_subblock_load(counts, n, i0, c);
         const u64 mine = (u64)c[0] + c[1] + c[2] + c[3];
         u64 incl = mine;
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u64 v = (u64)__shfl_up((long long)incl, d, 64); if (lane >= d) incl += v; }
+        for (int d = 1; d < 64; d <<= 1) { const u64 v = wave_shfl_up(incl, d); if (lane >= d) incl += v; }
         if (lane == 63) s_wave[sb & 1][wave] = incl;
         __syncthreads();                                  // (two sets of wave totals in turn: one barrier per sub-block)
         u64 before = 0, total = 0;
 #pragma unroll
         for (int w = 0; w < 4; w++) { const u64 x = s_wave[sb & 1][w]; if (w < wave) before += x; total += x; }
-        const u64 r0 = carry + before + incl - mine, r1 = r0 + c[0], r2 = r1 + c[1], r3 = r2 + c[2];
-        if (i0 + 3 < n) {
-            ulonglong2* o = reinterpret_cast<ulonglong2*>(offs + i0);
-            o[0] = make_ulonglong2(r0, r1); o[1] = make_ulonglong2(r2, r3);
-        } else {
-            const u64 r[4] = {r0, r1, r2, r3};
-            for (int j = 0; j < 4; j++) if (i0 + j < n) offs[i0 + j] = r[j];
-        }
+        scan_subblock_store(offs, n, i0, c, carry + before + incl - mine);
         carry += total;
     }
     if (t == 0) chunkTotal[blockIdx.x] = carry;
 }
-// The same scan in ONE launch, offsets absolute from the start: the chunks' totals travel through chain[chunk] = (value << 2) | state
-// (1: the chunk's own total, 2: the total of all chunks up to and including it) by decoupled look-back, a wave reading 64 predecessors
-// per round trip - as in k_rank_blocks_chained below.  Workgroups are dispatched in the order of their index, so whatever a chunk
-// waits for is running or done; a wave that nevertheless waits longer than 1 ms sets bit 512 of *stuck and leaves (the host repeats
-// the scan with the three launches).  `chain` must be zero before the launch.  Saves the pass that adds the chunk bases (87 us of
-// reading and re-writing the 240 MB of offsets of a 60 M-row materialisation) and the single-workgroup scan of the totals.
+// The same scan in ONE launch, offsets absolute from the start: the chunks' totals travel through chain[chunk] by decoupled look-back
+// (scan_device.h look_back) - as in k_rank_blocks_chained below.  A look-back that waits longer than 1 ms sets bit 512 of *stuck and
+// leaves (the host repeats the scan with the three launches).  `chain` must be zero before the launch.  Saves the pass that adds the
+// chunk bases (87 us of reading and re-writing the 240 MB of offsets of a 60 M-row materialisation) and the single-workgroup scan of
+// the totals.
 __global__ void __launch_bounds__(256) k_scan_chained(const unsigned* __restrict__ counts, u64* __restrict__ offs, i64 n, u64* __restrict__ chain,
                                                       unsigned* __restrict__ stuck) {
     __shared__ u64 s_wave[2][4];
     __shared__ u64 s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned c[4][4];
     u64 loc[4];
     u64 carry = 0;
 #pragma unroll
     for (int sb = 0; sb < 4; sb++) {
-        const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + (i64)sb * 1024 + (i64)t * 4;
-        c[sb][0] = c[sb][1] = c[sb][2] = c[sb][3] = 0u;
-        if (i0 + 3 < n) { const uint4 v = *reinterpret_cast<const uint4*>(counts + i0); c[sb][0] = v.x; c[sb][1] = v.y; c[sb][2] = v.z; c[sb][3] = v.w; }
-        else for (int j = 0; j < 4; j++) if (i0 + j < n) c[sb][j] = counts[i0 + j];
-        const u64 mine = (u64)c[sb][0] + c[sb][1] + c[sb][2] + c[sb][3];
-        u64 incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u64 v = (u64)__shfl_up((long long)incl, d, 64); if (lane >= d) incl += v; }
-        if (lane == 63) s_wave[sb & 1][wave] = incl;
-        __syncthreads();
-        u64 before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const u64 x = s_wave[sb & 1][w]; if (w < wave) before += x; total += x; }
-        loc[sb] = carry + before + incl - mine;
+        u64 total;
+        scan_subblock_load(counts, n, scan_subblock_index(sb), c[sb]);
+        loc[sb] = carry + block_scan<256, u64, ScanSum>((u64)c[sb][0] + c[sb][1] + c[sb][2] + c[sb][3], s_wave[sb & 1], &total);
         carry += total;
     }
-    if (t < 64) {
-        const u64 total = carry;
-        u64 base = 0;
-        if (blockIdx.x == 0) { if (lane == 0) __hip_atomic_store(&chain[0], (total << 2) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        else {
-            if (lane == 0) __hip_atomic_store(&chain[blockIdx.x], (total << 2) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const long long t0 = wall_clock64();
-            i64 hi = (i64)blockIdx.x - 1;
-            for (;;) {
-                const i64 idx = hi - lane;
-                const u64 v = idx >= 0 ? __hip_atomic_load(&chain[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 2ull;      // (in front of chunk 0: nothing, inclusive)
-                const u64 ready = __ballot((v & 3ull) != 0ull), incl = __ballot((v & 3ull) == 2ull);
-                u64 take = 0; bool done = false, moved = false;
-                if (incl) {
-                    const int f = __ffsll((long long)incl) - 1;
-                    const u64 below = (1ull << f) - 1ull;
-                    if ((ready & below) == below) { take = lane <= f ? v >> 2 : 0ull; done = true; }
-                } else if (ready == ~0ull) { take = v >> 2; moved = true; }
-                if (done || moved) {
-#pragma unroll
-                    for (int m = 32; m >= 1; m >>= 1) take += (u64)__shfl_xor((long long)take, m, 64);
-                    base += take;
-                    if (done) break;
-                    hi -= 64;
-                    continue;
-                }
-                if (wall_clock64() - t0 > 100000ll) { if (lane == 0) atomicOr(stuck, 512u); base = 0; break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0) __hip_atomic_store(&chain[blockIdx.x], ((base + total) << 2) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) s_base = base;
+    if (threadIdx.x < 64) {
+        const u64 base = look_back<u64>(chain, (int)blockIdx.x, carry, stuck, 512u);
+        if (threadIdx.x == 0) s_base = base;
     }
     __syncthreads();
-    const u64 base = s_base;
 #pragma unroll
-    for (int sb = 0; sb < 4; sb++) {
-        const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + (i64)sb * 1024 + (i64)t * 4;
-        const u64 r0 = base + loc[sb], r1 = r0 + c[sb][0], r2 = r1 + c[sb][1], r3 = r2 + c[sb][2];
-        if (i0 + 3 < n) {
-            ulonglong2* o = reinterpret_cast<ulonglong2*>(offs + i0);
-            o[0] = make_ulonglong2(r0, r1); o[1] = make_ulonglong2(r2, r3);
-        } else {
-            const u64 r[4] = {r0, r1, r2, r3};
-            for (int j = 0; j < 4; j++) if (i0 + j < n) offs[i0 + j] = r[j];
-        }
-    }
+    for (int sb = 0; sb < 4; sb++) scan_subblock_store(offs, n, scan_subblock_index(sb), c[sb], s_base + loc[sb]);
 }
-__global__ void __launch_bounds__(1024) k_scan_chunk_totals(const u64* __restrict__ chunkTotal, i64 nChunks, u64* __restrict__ chunkBase) {
-    __shared__ u64 s[1024];
-    u64 carry = 0;
-    for (i64 base = 0; base < nChunks; base += 1024) {
-        const i64 i = base + threadIdx.x;
-        const u64 v = i < nChunks ? chunkTotal[i] : 0ull;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const u64 x = threadIdx.x >= (unsigned)off ? s[threadIdx.x - off] : 0ull;
-            __syncthreads();
-            s[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (i < nChunks) chunkBase[i] = carry + s[threadIdx.x] - v;
-        carry += s[1023];
-        __syncthreads();
-    }
+__global__ void __launch_bounds__(SCAN_BATCH) k_scan_chunk_totals(const u64* __restrict__ chunkTotal, i64 nChunks, u64* __restrict__ chunkBase) {
+    batched_exclusive_scan<u64, ScanSum>(nChunks, [&](i64 i) { return chunkTotal[i]; }, [&](i64 i, u64 before) { chunkBase[i] = before; });
 }
 __global__ void __launch_bounds__(256) k_scan_add_base(u64* __restrict__ offs, i64 n, const u64* __restrict__ chunkBase) {
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) offs[i] += chunkBase[i / SCAN_CHUNK];
@@ -1543,7 +1460,7 @@ void exclusiveScanCounts(Context& ctx, const uint32_t* counts, uint64_t* offs, i
     u64* chunkTotal = (u64*)temp;
     u64* chunkBase = chunkTotal + nChunks;
     hipLaunchKernelGGL(k_scan_chunks, dim3((unsigned)nChunks), dim3(256), 0, ctx.stream, (const unsigned*)counts, (u64*)offs, (i64)n, chunkTotal);
-    hipLaunchKernelGGL(k_scan_chunk_totals, dim3(1), dim3(1024), 0, ctx.stream, (const u64*)chunkTotal, nChunks, chunkBase);
+    hipLaunchKernelGGL(k_scan_chunk_totals, dim3(1), dim3(SCAN_BATCH), 0, ctx.stream, (const u64*)chunkTotal, nChunks, chunkBase);
     const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(4096, (n + 255) / 256));
     hipLaunchKernelGGL(k_scan_add_base, dim3(grid), dim3(256), 0, ctx.stream, (u64*)offs, (i64)n, (const u64*)chunkBase);
     RSQ_HIP(hipGetLastError());
@@ -1558,11 +1475,9 @@ void exclusiveScanCounts(Context& ctx, const uint32_t* counts, uint64_t* offs, i
 #define RANK_CHUNK_BLOCKS RSQ_RANK_CHUNK_BLOCKS          /* 32-byte blocks per workgroup (engine.h): 1024 — with 4096 a 60 M-bit bitmap
                                                            gave 66 workgroups to 256 CUs: 10.6 us instead of ~4 */
 #define RANK_PT (RANK_CHUNK_BLOCKS / 256)          /* blocks per thread */
-// blocks are [rank word | 7 bitmap words]; this pass writes every block's rank relative to its chunk
-__global__ void __launch_bounds__(256) k_rank_blocks(unsigned* __restrict__ bm, i64 nBlocks, unsigned* __restrict__ chunkTotal) {
-    __shared__ unsigned s_tot[256];
-    const i64 b0 = (i64)blockIdx.x * RANK_CHUNK_BLOCKS + (i64)threadIdx.x * RANK_PT;
-    unsigned c[RANK_PT];
+// blocks are [rank word | 7 bitmap words]
+// the set bits of the thread's RANK_PT blocks, block by block in c; returns their sum
+__device__ __forceinline__ unsigned rank_block_counts(const unsigned* __restrict__ bm, i64 b0, i64 nBlocks, unsigned (&c)[RANK_PT]) {
     unsigned mine = 0;
 #pragma unroll
     for (int j = 0; j < RANK_PT; j++) {
@@ -1574,18 +1489,21 @@ __global__ void __launch_bounds__(256) k_rank_blocks(unsigned* __restrict__ bm, 
         }
         c[j] = n; mine += n;
     }
-    s_tot[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {                  // inclusive scan of the thread totals
-        unsigned v = threadIdx.x >= (unsigned)off ? s_tot[threadIdx.x - off] : 0u;
-        __syncthreads();
-        s_tot[threadIdx.x] += v;
-        __syncthreads();
-    }
-    unsigned run = s_tot[threadIdx.x] - mine;
+    return mine;
+}
+// the rank words of those blocks: `run` keys in front of the first
+__device__ __forceinline__ void rank_block_write(unsigned* __restrict__ bm, i64 b0, i64 nBlocks, const unsigned (&c)[RANK_PT], unsigned run) {
 #pragma unroll
     for (int j = 0; j < RANK_PT; j++) { if (b0 + j < nBlocks) bm[(b0 + j) * 8] = run; run += c[j]; }
-    if (threadIdx.x == 255) chunkTotal[blockIdx.x] = s_tot[255];
+}
+// this pass writes every block's rank relative to its chunk
+__global__ void __launch_bounds__(256) k_rank_blocks(unsigned* __restrict__ bm, i64 nBlocks, unsigned* __restrict__ chunkTotal) {
+    __shared__ unsigned s_wave[4];
+    const i64 b0 = (i64)blockIdx.x * RANK_CHUNK_BLOCKS + (i64)threadIdx.x * RANK_PT;
+    unsigned c[RANK_PT], total;
+    const unsigned mine = rank_block_counts(bm, b0, nBlocks, c);
+    rank_block_write(bm, b0, nBlocks, c, block_scan<256, unsigned, ScanSum>(mine, s_wave, &total));
+    if (threadIdx.x == 0) chunkTotal[blockIdx.x] = total;
 }
 
 // the rank words become absolute (chunk base added): a probe then needs nothing but the block it tested
@@ -1609,83 +1527,28 @@ __global__ void __launch_bounds__(256) k_rank_absolute(unsigned* __restrict__ bm
     for (i64 b = b0 + threadIdx.x; b < b0 + RANK_CHUNK_BLOCKS && b < nBlocks; b += blockDim.x) bm[b * 8] += base;
 }
 
-// The whole index in ONE launch (round 3): the chunks' totals travel through `chain[chunk]` (below) and a workgroup writes its
+// The whole index in ONE launch (round 3): the chunks' totals travel through `chain[chunk]` (scan_device.h look_back) and a workgroup writes its
 // rank words absolute from the start.  The grid is at most 1171 workgroups of 256 threads (a key domain of 2^28 bits), fewer than the chip holds at a time,
-// so a predecessor is always running; a workgroup that nevertheless waits longer than ~1 ms raises `*stuck` and leaves (the host
+// so a predecessor is always running; a workgroup that nevertheless waits longer than ~1 ms raises bit 128 of `*stuck` and leaves (the host
 // then repeats the index with the two-launch form above — never a hang).  `chain` must be zero before the launch.
 __global__ void __launch_bounds__(256) k_rank_blocks_chained(unsigned* __restrict__ bm, i64 nBlocks, unsigned* __restrict__ chain, int nChunks,
                                                              unsigned* __restrict__ chunkBase /* [nChunks + 1] */, unsigned* __restrict__ stuck) {
-    __shared__ unsigned s_tot[256];
+    __shared__ unsigned s_wave[4];
     __shared__ unsigned s_base;
     const i64 b0 = (i64)blockIdx.x * RANK_CHUNK_BLOCKS + (i64)threadIdx.x * RANK_PT;
-    unsigned c[RANK_PT];
-    unsigned mine = 0;
-#pragma unroll
-    for (int j = 0; j < RANK_PT; j++) {
-        unsigned n = 0;
-        if (b0 + j < nBlocks) {
-            const uint4* w = reinterpret_cast<const uint4*>(bm + (b0 + j) * 8);
-            const uint4 lo = w[0], hi = w[1];
-            n = __popc(lo.y) + __popc(lo.z) + __popc(lo.w) + __popc(hi.x) + __popc(hi.y) + __popc(hi.z) + __popc(hi.w);
-        }
-        c[j] = n; mine += n;
-    }
-    s_tot[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {                  // inclusive scan of the thread totals
-        unsigned v = threadIdx.x >= (unsigned)off ? s_tot[threadIdx.x - off] : 0u;
-        __syncthreads();
-        s_tot[threadIdx.x] += v;
-        __syncthreads();
-    }
+    unsigned c[RANK_PT], total;
+    const unsigned mine = rank_block_counts(bm, b0, nBlocks, c);
+    const unsigned before = block_scan<256, unsigned, ScanSum>(mine, s_wave, &total);
     if (threadIdx.x < 64) {
-        // chain word = (value << 2) | state: 1 = this chunk's own total, 2 = the total of all chunks up to and including it.
-        // A chunk publishes its own total at once and then looks BACK over its predecessors, adding own totals until it meets an
-        // inclusive one (decoupled look-back): no chunk waits for a chain of 260 hand-overs, which a plain "wait for the chunk
-        // before me" turned into 130 us of serial latency on TPC-H Q3's 60 M-bit orders bitmap.  The look-back is done by one WAVE,
-        // lane l reading the l-th predecessor: 64 chain words per round trip (one thread walking them one by one: 19 us for 262 chunks).
-        const int lane = (int)threadIdx.x;
-        const unsigned total = s_tot[255];
-        unsigned base = 0;
-        if (blockIdx.x == 0) { if (lane == 0) __hip_atomic_store(&chain[0], (total << 2) | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        else {
-            if (lane == 0) __hip_atomic_store(&chain[blockIdx.x], (total << 2) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const long long t0 = wall_clock64();
-            int hi = (int)blockIdx.x - 1;                 // the nearest predecessor not yet accounted for
-            for (;;) {
-                const int idx = hi - lane;
-                // (in front of chunk 0: nothing, inclusive)
-                const unsigned v = idx >= 0 ? __hip_atomic_load(&chain[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 2u;
-                const u64 ready = __ballot((v & 3u) != 0u), incl = __ballot((v & 3u) == 2u);
-                unsigned take = 0; bool done = false, moved = false;
-                if (incl) {
-                    const int f = __ffsll((long long)incl) - 1;               // the nearest inclusive total
-                    const u64 below = (1ull << f) - 1ull;
-                    if ((ready & below) == below) { take = lane <= f ? v >> 2 : 0u; done = true; }
-                } else if (ready == ~0ull) { take = v >> 2; moved = true; }           // 64 own totals: add them, look further back
-                if (done || moved) {
-#pragma unroll
-                    for (int m = 32; m >= 1; m >>= 1) take += (unsigned)__shfl_xor((int)take, m, 64);
-                    base += take;
-                    if (done) break;
-                    hi -= 64;
-                    continue;
-                }
-                if (wall_clock64() - t0 > 100000ll) { if (lane == 0) atomicOr(stuck, 128u); base = 0; break; }          // 100 MHz clock: 1 ms
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0) __hip_atomic_store(&chain[blockIdx.x], ((base + total) << 2) | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) {
+        const unsigned base = look_back<unsigned>(chain, (int)blockIdx.x, total, stuck, 128u);
+        if (threadIdx.x == 0) {
             chunkBase[blockIdx.x] = base;
             if ((int)blockIdx.x == nChunks - 1) chunkBase[nChunks] = base + total;
             s_base = base;
         }
     }
     __syncthreads();
-    unsigned run = s_base + s_tot[threadIdx.x] - mine;
-#pragma unroll
-    for (int j = 0; j < RANK_PT; j++) { if (b0 + j < nBlocks) bm[(b0 + j) * 8] = run; run += c[j]; }
+    rank_block_write(bm, b0, nBlocks, c, s_base + before);
 }
 
 void rankTableIndex(Context& ctx, uint32_t* bitmap, int64_t nBlocks, uint32_t* chunkTotal, uint32_t* chunkBase) {

@@ -25,11 +25,10 @@
 #include <vector>
 
 #include "engine.h"
+#include "scan_device.h"
 
 namespace rsq {
 
-typedef long long i64;
-typedef unsigned long long u64;
 typedef unsigned int u32;
 typedef unsigned char u8;
 
@@ -544,50 +543,23 @@ __global__ void __launch_bounds__(256) k_rp_excess(const u64* __restrict__ start
     for (u64 s = blockIdx.x * (u64)blockDim.x + threadIdx.x; s < 2 * N; s += (u64)gridDim.x * blockDim.x)
         S[s] = (i64)start[s < N ? s : s - N] + (s >= N ? cnt : 0) - (i64)s;
 }
-// inclusive running minimum of an i64 array, three launches like the sum scan of aot_kernels.hip (chunks of 4096)
-#define SM_CHUNK 4096
+// inclusive running minimum of an i64 array, three launches like the sum scan of aot_kernels.hip (chunks of SM_CHUNK, scan_device.h)
 __global__ void __launch_bounds__(256) k_scanmin_chunks(i64* __restrict__ v, i64 n, i64* __restrict__ chunkMin) {
     __shared__ i64 s_wave[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const i64 b0 = (i64)blockIdx.x * SM_CHUNK + (i64)t * 16;
-    i64 c[16];
-    i64 mine = 0x7fffffffffffffffll;
+    const i64 b0 = (i64)blockIdx.x * SM_CHUNK + (i64)threadIdx.x * SM_PER_THREAD;
+    i64 c[SM_PER_THREAD];
+    i64 mine = ScanMin::identity();
 #pragma unroll
-    for (int j = 0; j < 16; j++) { c[j] = b0 + j < n ? v[b0 + j] : 0x7fffffffffffffffll; mine = c[j] < mine ? c[j] : mine; c[j] = mine; }      // c[j] = thread-local inclusive min
-    i64 incl = mine;
+    for (int j = 0; j < SM_PER_THREAD; j++) { c[j] = b0 + j < n ? v[b0 + j] : ScanMin::identity(); mine = ScanMin::apply(c[j], mine); c[j] = mine; }      // c[j] = thread-local inclusive min
+    i64 total;
+    const i64 excl = block_scan<256, i64, ScanMin>(mine, s_wave, &total);      // min of everything in front of this thread within the chunk
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const i64 o = __shfl_up(incl, d, 64); if (lane >= d) incl = o < incl ? o : incl; }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    i64 before = 0x7fffffffffffffffll;
-    for (int w = 0; w < wave; w++) before = s_wave[w] < before ? s_wave[w] : before;
-    const i64 up = __shfl_up(incl, 1, 64);
-    const i64 excl = lane == 0 ? before : (up < before ? up : before);      // min of everything in front of this thread within the chunk
-#pragma unroll
-    for (int j = 0; j < 16; j++) if (b0 + j < n) v[b0 + j] = c[j] < excl ? c[j] : excl;
-    if (t == 255) { i64 m = incl; for (int w = 0; w < 4; w++) m = s_wave[w] < m ? s_wave[w] : m; chunkMin[blockIdx.x] = m; }
+    for (int j = 0; j < SM_PER_THREAD; j++) if (b0 + j < n) v[b0 + j] = ScanMin::apply(c[j], excl);
+    if (threadIdx.x == 0) chunkMin[blockIdx.x] = total;
 }
-__global__ void __launch_bounds__(1024) k_scanmin_totals(i64* __restrict__ chunkMin, i64 nChunks) {
+__global__ void __launch_bounds__(SCAN_BATCH) k_scanmin_totals(i64* __restrict__ chunkMin, i64 nChunks) {
     // exclusive running minimum of the chunk minima, in place (one workgroup; a few thousand chunks at most)
-    __shared__ i64 s[1024];
-    i64 carry = 0x7fffffffffffffffll;
-    for (i64 base = 0; base < nChunks; base += 1024) {
-        const i64 i = base + threadIdx.x;
-        const i64 x = i < nChunks ? chunkMin[i] : 0x7fffffffffffffffll;
-        s[threadIdx.x] = x;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const i64 o = threadIdx.x >= (unsigned)off ? s[threadIdx.x - off] : 0x7fffffffffffffffll;
-            __syncthreads();
-            if (o < s[threadIdx.x]) s[threadIdx.x] = o;
-            __syncthreads();
-        }
-        const i64 prev = threadIdx.x ? s[threadIdx.x - 1] : 0x7fffffffffffffffll;
-        if (i < nChunks) chunkMin[i] = prev < carry ? prev : carry;
-        const i64 last = s[1023];
-        __syncthreads();
-        carry = last < carry ? last : carry;
-    }
+    batched_exclusive_scan<i64, ScanMin>(nChunks, [&](i64 i) { return chunkMin[i]; }, [&](i64 i, i64 before) { chunkMin[i] = before; });
 }
 __global__ void __launch_bounds__(256) k_scanmin_apply(i64* __restrict__ v, i64 n, const i64* __restrict__ chunkBase) {
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
@@ -602,7 +574,7 @@ void runningMinInPlace(Context& ctx, int64_t* v, int64_t n, int64_t* chunkMin) {
     const i64 nChunks = (n + SM_CHUNK - 1) / SM_CHUNK;
     const unsigned applyGrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)n + 255) / 256));
     hipLaunchKernelGGL(k_scanmin_chunks, dim3((unsigned)nChunks), dim3(256), 0, ctx.stream, (i64*)v, (i64)n, (i64*)chunkMin);
-    hipLaunchKernelGGL(k_scanmin_totals, dim3(1), dim3(1024), 0, ctx.stream, (i64*)chunkMin, nChunks);
+    hipLaunchKernelGGL(k_scanmin_totals, dim3(1), dim3(SCAN_BATCH), 0, ctx.stream, (i64*)chunkMin, nChunks);
     hipLaunchKernelGGL(k_scanmin_apply, dim3(applyGrid), dim3(256), 0, ctx.stream, (i64*)v, (i64)n, (const i64*)chunkMin);
 }
 // one thread per slot; a cluster is replayed by the thread of its first slot

@@ -246,7 +246,8 @@ void fillBatchAsync(Context& ctx, const FillItem* items, int count);
 // their key
 void rankTableIndex(Context& ctx, uint32_t* bitmap, int64_t nBlocks, uint32_t* chunkTotal, uint32_t* chunkBase);
 // the same index in one launch: chunk totals chained through `chain` (the chunkTotal scratch, zero before the launch); a workgroup
-// that waits too long raises bit 128 of the device error word and the caller repeats with rankTableIndex
+// that waits too long raises bit 128 of the device error word and the caller repeats with rankTableIndex (the look-back is
+// scan_device.h look_back, the one exclusiveScanCountsChained uses)
 void rankTableIndexChained(Context& ctx, uint32_t* bitmap, int64_t nBlocks, uint32_t* chain, uint32_t* chunkBase);
 void rankTablePlace(Context& ctx, const int64_t* temp, const uint32_t* used, uint32_t nWaves, uint32_t region, const uint32_t* nRecords, int nWords,
                     const uint32_t* bitmap, int64_t bmMin, int64_t bmBits, const uint32_t* chunkBase, int64_t nBlocks, int64_t* words,
@@ -353,7 +354,8 @@ void rowTailResultRows(Context& ctx, const int64_t* rows, int stride, const uint
 // the replay of the reference's aggregation hash table on the device (devtail.hip): level sizes on the host, everything else enqueued
 bool replayLevels(uint64_t n, uint64_t minSize, std::vector<std::pair<uint64_t, uint64_t>>& levels);
 size_t replayDeviceBytes(uint64_t n, uint64_t nMax);
-// the inclusive running minimum the replay takes its carries from (k_scanmin_*): v[i] = min(v[0..i]) in place, three launches on ctx.stream
+// the inclusive running minimum the replay takes its carries from (k_scanmin_*, on scan_device.h's block_scan and
+// batched_exclusive_scan): v[i] = min(v[0..i]) in place, three launches on ctx.stream
 size_t runningMinTempBytes(int64_t n);
 void runningMinInPlace(Context& ctx, int64_t* v, int64_t n, int64_t* chunkMin /* runningMinTempBytes(n) */);
 void replayEmissionOrderDevice(Context& ctx, const uint64_t* hashes, uint64_t n, const std::vector<std::pair<uint64_t, uint64_t>>& levels, void* work, uint32_t* order);

@@ -10,10 +10,10 @@ single-workgroup scan of the chunk totals; a bitmap block's first and last word 
 every vectorised reference against a plain loop before a kernel is involved."""
 import numpy as np
 
-# The kernels' geometry, in one place.  The host test reads the three definitions in the source and compares.
-SCAN_CHUNK = 4096             # counts per workgroup of the scan:                            aot_kernels.hip  #define SCAN_CHUNK 4096
-SCAN_BATCH = 1024             # counts per sub-block of a chunk (k_scan_chunks: sb * 1024), and chunk totals per batch of
-#                               k_scan_chunk_totals (base += 1024):                          aot_kernels.hip, literals in both kernels
+# The kernels' geometry, in one place.  The host test reads the definitions in the source and compares.
+SCAN_CHUNK = 4096             # counts per workgroup of the scan:                            scan_device.h  #define SCAN_CHUNK 4096
+SCAN_BATCH = 1024             # counts per sub-block of a chunk (k_scan_chunks), and values per batch of the single-workgroup scans
+#                               (batched_exclusive_scan: k_scan_chunk_totals, k_scanmin_totals):  scan_device.h  #define SCAN_BATCH 1024
 RANK_CHUNK_BLOCKS = 1024      # 32-byte bitmap blocks per workgroup of the rank index:       engine.h  #define RSQ_RANK_CHUNK_BLOCKS 1024
 BLOCK_WORDS = 8               # a bitmap block: [rank word | 7 bitmap words]
 BLOCK_BITS = 32 * (BLOCK_WORDS - 1)
@@ -236,8 +236,9 @@ def place_cases():
 # rsq_prim_running_min, rsq_prim_merge_group_rows and rsq_prim_topk_select.  Integer operations all four: every reference is exact.
 # =====================================================================================================================================
 RS_TILE = 2048                # pairs per workgroup of a sort pass, taken in rounds of 256:   devtail.hip  #define RS_TILE 2048
-SM_CHUNK = 4096               # values per workgroup of the running minimum, 16 per thread:   devtail.hip  #define SM_CHUNK 4096
-SM_BATCH = 1024               # chunk minima per batch of k_scanmin_totals (base += 1024):    devtail.hip, literal in the kernel
+SM_CHUNK = 4096               # values per workgroup of the running minimum:                  scan_device.h  #define SM_CHUNK 4096
+SM_PER_THREAD = 16            # ... consecutive ones per thread:                              scan_device.h  #define SM_PER_THREAD 16
+SM_BATCH = SCAN_BATCH         # chunk minima per batch of k_scanmin_totals: the one batch size of batched_exclusive_scan (scan_device.h)
 TOPK_BINS = 2048              # bins of one histogram (an 11-bit digit):                      aot_kernels.hip  enum { TOPK_PASSES = 6, TOPK_BINS = 2048 }
 TOPK_PASSES = 6               # five 11-bit digits and a last one of 9 bits (topk_shift / topk_bits)
 NOTE_MERGE_FULL = 2           # k_gm_insert: "Hash table full" (a table of >= 2 n slots: not reached)

@@ -18,17 +18,17 @@ SRC = os.path.join(ROOT, "resql_amd", "csrc")
 
 def test_constants_are_the_sources():
     aot = open(os.path.join(SRC, "aot_kernels.hip")).read()
-    assert int(re.search(r"^#define SCAN_CHUNK (\d+)", aot, re.M).group(1)) == pc.SCAN_CHUNK
-    assert f"(i64)sb * {pc.SCAN_BATCH} " in aot and f"base += {pc.SCAN_BATCH})" in aot
+    scan = open(os.path.join(SRC, "scan_device.h")).read()
+    define = lambda text, name: int(re.search(rf"^#define {name} (\d+)", text, re.M).group(1))
+    assert define(scan, "SCAN_CHUNK") == pc.SCAN_CHUNK
+    assert define(scan, "SCAN_BATCH") == pc.SCAN_BATCH == pc.SM_BATCH          # one batch size for every single-workgroup scan
     assert pc.SCAN_CHUNK == 4 * pc.SCAN_BATCH          # four sub-blocks per chunk
     eng = open(os.path.join(SRC, "engine.h")).read()
-    assert int(re.search(r"^#define RSQ_RANK_CHUNK_BLOCKS (\d+)", eng, re.M).group(1)) == pc.RANK_CHUNK_BLOCKS == engine.RANK_CHUNK_BLOCKS
+    assert define(eng, "RSQ_RANK_CHUNK_BLOCKS") == pc.RANK_CHUNK_BLOCKS == engine.RANK_CHUNK_BLOCKS
     tail = open(os.path.join(SRC, "devtail.hip")).read()
-    assert int(re.search(r"^#define RS_TILE (\d+)", tail, re.M).group(1)) == pc.RS_TILE
-    assert int(re.search(r"^#define SM_CHUNK (\d+)", tail, re.M).group(1)) == pc.SM_CHUNK
-    totals = tail[tail.index("void __launch_bounds__(1024) k_scanmin_totals"):tail.index("void __launch_bounds__(256) k_scanmin_apply")]
-    assert f"base += {pc.SM_BATCH})" in totals and f"s[{pc.SM_BATCH}]" in totals
-    assert "for (int j = 0; j < 16; j++)" in tail and pc.SM_CHUNK == 256 * 16          # 16 values per thread, 1024 per wave
+    assert define(tail, "RS_TILE") == pc.RS_TILE
+    assert define(scan, "SM_CHUNK") == pc.SM_CHUNK
+    assert define(scan, "SM_PER_THREAD") == pc.SM_PER_THREAD == 16 and pc.SM_CHUNK == 256 * 16          # 16 values per thread, 1024 per wave
     m = re.search(r"enum \{ TOPK_PASSES = (\d+), TOPK_BINS = (\d+) \}", aot)
     assert (int(m.group(1)), int(m.group(2))) == (pc.TOPK_PASSES, pc.TOPK_BINS)
     assert 5 * 11 + 9 == 64 and pc.TOPK_BINS == 1 << 11          # topk_shift / topk_bits: five 11-bit digits and one of 9

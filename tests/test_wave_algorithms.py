@@ -71,7 +71,7 @@ def test_combined_bit_sets_set_exactly_the_requested_bits():
 
 
 def look_back(chain, i, total):
-    """the wave look-back of k_rank_blocks_chained / k_scan_chained for chunk i as a generator: every `yield` is one round trip
+    """the wave look-back of k_rank_blocks_chained / k_scan_chained (resql_amd/csrc/scan_device.h look_back) for chunk i as a generator: every `yield` is one round trip
     (64 chain words read at once); returns the exclusive base and publishes the inclusive total"""
     if i == 0:
         chain[0] = (total << 2) | 2
