@@ -98,8 +98,14 @@ typedef struct rsq_config {
  * pair merge in any order, so the result is the same bytes for every S.  A join whose pairs are materialised, or fill a hash join's
  * build side, keeps S = 1: their output positions follow the scan order.
  * RSQ_ENGINE_DERIVED_MULTI (off by default) lets a multi-GPU handle (rsq_multi_config.base) run plans with derived aggregations; see
- * rsq_multi_* below.  It is a setting of multi-GPU handles only: rsq_ctx_create refuses it (one context runs such plans without it). */
-enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u, RSQ_ENGINE_DERIVED_MULTI = 8u };
+ * rsq_multi_* below.  It is a setting of multi-GPU handles only: rsq_ctx_create refuses it (one context runs such plans without it).
+ * RSQ_ENGINE_DICT_MULTI (off by default; a setting of multi-GPU handles only, like the one above) gives the shards of a table ONE
+ * dictionary per dictionary-coded string column (the union of the shards' dictionaries, rsq_table_unify_shard_dictionaries) when a
+ * statement is compiled, so that a GROUP BY over such a column is a dense table keyed by the code on every shard and merges as dense
+ * partial tables.  Without it such a statement keeps the hash form across shards.  It has an effect only where the dictionary images
+ * are on (RSQ_DICT_SCANS). */
+enum rsq_engine_flags { RSQ_ENGINE_DRIVER_ALLOC = 1u, RSQ_ENGINE_NO_PLAN_MEMO = 2u, RSQ_ENGINE_NESTED_LOOPS = 4u, RSQ_ENGINE_DERIVED_MULTI = 8u,
+                        RSQ_ENGINE_DICT_MULTI = 16u };
 
 /* Semantics switches.  The default (0) computes what the reference's SOURCE specifies; a bit selects what its asmjit back end
  * actually executes where the two differ, for a drop-in host that must return the JIT's own answers:
@@ -223,6 +229,17 @@ int64_t rsq_table_stats_bytes(const rsq_table* t);
 int  rsq_table_stats_export(const rsq_table* t, void* buf, int64_t bytes);
 int  rsq_table_unify_shard_stats(rsq_table* t, const void* blobs, int32_t n_shards, int64_t blob_bytes);
 int64_t rsq_table_total_rows(const rsq_table* t);
+/* The dictionary counterpart, for shards that live in ONE process (on any contexts and devices): column by column over the n_shards
+ * instances of a table (one schema, else RSQ_ERR_INVALID).  Where every shard with rows holds a dictionary image of the column and the
+ * union of their entries has at most 256 values, every shard receives the union (bytewise order) and its codes are rewritten in place;
+ * every other column stays exactly as it is.  A shard whose dictionary or codes changed refuses the statements compiled before, as after
+ * rsq_table_append; shards that hold the union already are left alone, so a second call changes nothing.  rsq_multi_query_compile
+ * calls it for every sharded table of a handle with RSQ_ENGINE_DICT_MULTI. */
+int  rsq_table_unify_shard_dictionaries(rsq_table* const* shards, int32_t n_shards);
+/* Measurement: the device time (ms) of one pass over a dictionary-coded column of a device table.  which 0: the recode pass that
+ * installs a union (here under the identity map); which 1: encoding the wide column anew with the column's dictionary, which the recode
+ * pass replaces.  The codes are left as they were. */
+int  rsq_table_time_dictionary_pass(rsq_table* t, const char* column, int32_t which, double* ms);
 /* Copy one device column back (tests). */
 int  rsq_table_read_column(rsq_ctx* ctx, const rsq_table* t, const char* name, void* host_dst, size_t bytes);
 void rsq_table_destroy(rsq_table* t);
@@ -523,6 +540,8 @@ int  rsq_multi_query_report(const rsq_multi_query* q, rsq_report* out, double* s
 double rsq_multi_query_collective_ms(const rsq_multi_query* q);
 /* which merge the query takes and why (dense partial tables / ordered merge of LIMIT-ed rows / general merge), for logs and tests */
 const char* rsq_multi_query_merge_name(const rsq_multi_query* q);
+/* rsq_query_explain of one shard's statement (NULL: no such shard). */
+const char* rsq_multi_query_explain(const rsq_multi_query* q, int32_t shard);
 void rsq_multi_query_destroy(rsq_multi_query* q);
 
 /* Sustained read-only streaming bandwidth of this GPU (grid-stride int64 sum over `bytes` of

@@ -259,6 +259,7 @@ static void dropDictImage(Context& ctx, TableColumn& c) {
 // moved or dropped bumps t.layoutVersion AT ONCE (a statement compiled before holds its address), whatever happens afterwards.
 static void buildDictImages(Context& ctx, Table& t) {
     unsigned* dFlag = nullptr;
+    for (auto& c : t.cols) c.dictShared = false;          // (this instance's own dictionary again: the next multi-GPU compile unifies anew)
     auto drop = [&](TableColumn& c) { if (c.dictPtr || c.codePtr) t.layoutVersion++; dropDictImage(ctx, c); };
     try {
         for (auto& c : t.cols) {
@@ -302,6 +303,159 @@ static void buildDictImages(Context& ctx, Table& t) {
         throw;
     }
     if (dFlag) ctx.free(dFlag);
+}
+
+// codes[r] = lut[codes[r]] for r < n, in place: a dictionary that became the union of the shards' dictionaries moves every old rank to
+// its rank in the union (unifyShardDictionaries).  The 256-byte map sits in LDS; a lane loads, maps and stores 16 codes at a time (the
+// code buffer is a multiple of 16 bytes long), and the bytes behind row n in the last vector keep their value.
+__device__ inline unsigned recode4(unsigned w, const unsigned char* s) {
+    return (unsigned)s[w & 255u] | ((unsigned)s[(w >> 8) & 255u] << 8) | ((unsigned)s[(w >> 16) & 255u] << 16) | ((unsigned)s[w >> 24] << 24);
+}
+__global__ void __launch_bounds__(256) k_dict_recode(unsigned char* __restrict__ codes, i64 n, const unsigned char* __restrict__ lut) {
+    __shared__ unsigned char s[256];
+    s[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    uint4* v = (uint4*)codes;
+    const i64 whole = n >> 4, all = (n + 15) >> 4;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < all; i += (i64)gridDim.x * 256) {
+        const uint4 x = v[i];
+        uint4 y = make_uint4(recode4(x.x, s), recode4(x.y, s), recode4(x.z, s), recode4(x.w, s));
+        if (i == whole) {          // the last, partial vector: n & 15 rows
+            const int rows = (int)(n & 15);
+            auto keep = [rows](unsigned was, unsigned now, int at) {
+                const int valid = rows - at;
+                const unsigned m = valid >= 4 ? ~0u : valid <= 0 ? 0u : (1u << (8 * valid)) - 1u;
+                return (now & m) | (was & ~m);
+            };
+            y = make_uint4(keep(x.x, y.x, 0), keep(x.y, y.y, 4), keep(x.z, y.z, 8), keep(x.w, y.w, 12));
+        }
+        v[i] = y;
+    }
+}
+
+void unifyShardDictionaries(const std::vector<Table*>& shards, bool replicated) {
+    if (shards.empty()) failInvalid("shard dictionaries: no tables");
+    for (Table* t : shards) if (!t || !t->ctx) failInvalid("shard dictionaries: null table");
+    const Table& t0 = *shards[0];
+    for (size_t s = 1; s < shards.size(); s++) {
+        const Table& t = *shards[s];
+        bool same = t.cols.size() == t0.cols.size();
+        for (size_t i = 0; same && i < t.cols.size(); i++) same = t.cols[i].type.tag == t0.cols[i].type.tag && columnWidth(t.cols[i].type) == columnWidth(t0.cols[i].type);
+        if (!same) failInvalid("shard dictionaries: table " + t.name + " has another schema on shard " + std::to_string(s));
+    }
+    for (size_t ci = 0; ci < t0.cols.size(); ci++) {
+        const size_t W = (size_t)columnWidth(t0.cols[ci].type);
+        auto mark = [&](bool on) { for (Table* t : shards) t->cols[ci].dictShared = on; };
+        if (replicated) {
+            // copies of one table: nothing is rewritten, the dictionaries agree or they do not
+            const TableColumn& c0 = t0.cols[ci];
+            bool agree = c0.dictN > 0;
+            for (Table* t : shards) agree = agree && t->cols[ci].dictN == c0.dictN && t->cols[ci].dict == c0.dict;
+            mark(agree);
+            continue;
+        }
+        // the union of the entries, in memcmp order (std::string compares its bytes as unsigned chars) - where every shard with rows has a dictionary
+        std::set<std::string> uni;
+        bool all = t0.cols[ci].type.isString(), any = false;
+        for (Table* t : shards) {
+            const TableColumn& c = t->cols[ci];
+            if (t->nRows <= 0) continue;          // (an empty shard says nothing about the values)
+            if (c.dictN <= 0 || c.dict.size() != (size_t)c.dictN * W) { all = false; break; }
+            any = true;
+            for (int e = 0; e < c.dictN; e++) uni.insert(std::string((const char*)c.dict.data() + (size_t)e * W, W));
+        }
+        if (!all || !any || uni.size() > (size_t)DICT_MAX) { mark(false); continue; }
+        const int N = (int)uni.size();
+        std::vector<uint8_t> dict;
+        for (const std::string& v : uni) dict.insert(dict.end(), v.begin(), v.end());
+        std::vector<Table*> touched;
+        std::vector<std::pair<Context*, void*>> luts;
+        try {
+            for (Table* t : shards) {
+                TableColumn& c = t->cols[ci];
+                if (c.dictN == N && c.dict == dict) continue;          // holds the union already: not a byte, not a version moves
+                Context& ctx = *t->ctx;
+                touched.push_back(t);
+                t->layoutVersion++;          // (statements compiled before hold the old entry count, the old meaning of a code and the old entries)
+                t->bumpVersion();
+                if (ctx.device >= 0) {
+                    RSQ_HIP(hipSetDevice(ctx.device));
+                    unsigned char lut[256] = {0};          // old rank -> rank in the union
+                    for (int e = 0; e < c.dictN; e++)
+                        lut[e] = (unsigned char)std::distance(uni.begin(), uni.find(std::string((const char*)c.dict.data() + (size_t)e * W, W)));
+                    const size_t dbytes = (size_t)DICT_MAX * W + 16;
+                    if (!c.dictPtr) {          // a shard without rows: the union and no codes (one empty vector, so that its scans are coded like its siblings')
+                        c.codeBytes = std::max<size_t>(16, ((size_t)t->nRows + 15) & ~(size_t)15);
+                        c.dictPtr = ctx.allocRaw(dbytes); ctx.columnImageBytes += dbytes;
+                        c.codePtr = ctx.allocRaw(c.codeBytes); ctx.columnImageBytes += c.codeBytes;
+                        RSQ_HIP(hipMemsetAsync(c.codePtr, 0, c.codeBytes, ctx.stream));
+                    }
+                    RSQ_HIP(hipMemsetAsync(c.dictPtr, 0, dbytes, ctx.stream));
+                    RSQ_HIP(hipMemcpyAsync(c.dictPtr, dict.data(), dict.size(), hipMemcpyHostToDevice, ctx.stream));
+                    if (t->nRows > 0) {
+                        void* dLut = ctx.alloc(256);
+                        luts.emplace_back(&ctx, dLut);
+                        RSQ_HIP(hipMemcpyAsync(dLut, lut, 256, hipMemcpyHostToDevice, ctx.stream));
+                        const i64 vectors = ((i64)t->nRows + 15) >> 4;
+                        hipLaunchKernelGGL(k_dict_recode, dim3((unsigned)std::min<i64>(2048, (vectors + 255) / 256)), dim3(256), 0, ctx.stream,
+                                           (unsigned char*)c.codePtr, (i64)t->nRows, (const unsigned char*)dLut);
+                        RSQ_HIP(hipGetLastError());
+                    }
+                    RSQ_HIP(hipStreamSynchronize(ctx.stream));          // (lut and dict are this frame's)
+                }
+                c.dictN = N; c.dict = dict;          // (a compile-only context has these alone)
+            }
+        } catch (...) {
+            // no half-unified column stays: where this column's images were touched they go (the column scans wide there)
+            for (Table* t : touched) {
+                if (t->ctx->device >= 0) { (void)hipSetDevice(t->ctx->device); (void)hipStreamSynchronize(t->ctx->stream); }
+                dropDictImage(*t->ctx, t->cols[ci]);
+                t->layoutVersion++;
+            }
+            for (auto& l : luts) l.first->free(l.second);
+            mark(false);
+            throw;
+        }
+        for (auto& l : luts) l.first->free(l.second);
+        mark(true);
+    }
+}
+
+// measurement (tools/dict_group_bench.py --recode): one pass over a coded column, timed by events on the context's stream.  which 0:
+// k_dict_recode under the identity map; 1: k_dict_encode over the wide column with the column's own dictionary - what installing a union
+// would cost without the recode pass.  Either way the codes end as they were.
+double timeDictPass(Context& ctx, Table& t, int col, int which) {
+    TableColumn& c = t.cols[(size_t)col];
+    if (ctx.device < 0 || c.dictN <= 0 || !c.codePtr || !c.dictPtr || t.nRows <= 0) failInvalid("column " + c.name + " of table " + t.name + " has no dictionary codes on a device");
+    if (which != 0 && which != 1) failInvalid("dictionary pass: 0 (recode) or 1 (encode)");
+    RSQ_HIP(hipSetDevice(ctx.device));
+    unsigned char ident[256];
+    for (int i = 0; i < 256; i++) ident[i] = (unsigned char)i;
+    unsigned char* dLut = (unsigned char*)ctx.alloc(256 + 16);
+    unsigned* dFlag = (unsigned*)(dLut + 256);
+    float ms = 0;
+    unsigned notFound = 0;
+    try {
+        RSQ_HIP(hipMemcpyAsync(dLut, ident, 256, hipMemcpyHostToDevice, ctx.stream));
+        RSQ_HIP(hipMemsetAsync(dFlag, 0, sizeof(unsigned), ctx.stream));
+        RSQ_HIP(hipEventRecord(ctx.ev0, ctx.stream));
+        if (which == 0) {
+            const i64 vectors = ((i64)t.nRows + 15) >> 4;
+            hipLaunchKernelGGL(k_dict_recode, dim3((unsigned)std::min<i64>(2048, (vectors + 255) / 256)), dim3(256), 0, ctx.stream, (unsigned char*)c.codePtr, (i64)t.nRows,
+                               (const unsigned char*)dLut);
+        } else {
+            hipLaunchKernelGGL(k_dict_encode, dim3((unsigned)std::min<int64_t>(2048, (t.nRows + 255) / 256)), dim3(256), 0, ctx.stream, (const unsigned char*)c.dptr, (i64)t.nRows,
+                               columnWidth(c.type), (const unsigned char*)c.dictPtr, c.dictN, (unsigned char*)c.codePtr, dFlag);
+        }
+        RSQ_HIP(hipGetLastError());
+        RSQ_HIP(hipEventRecord(ctx.ev1, ctx.stream));
+        RSQ_HIP(hipMemcpyAsync(&notFound, dFlag, sizeof notFound, hipMemcpyDeviceToHost, ctx.stream));
+        RSQ_HIP(hipStreamSynchronize(ctx.stream));
+        RSQ_HIP(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1));
+    } catch (...) { (void)hipStreamSynchronize(ctx.stream); ctx.free(dLut); throw; }
+    ctx.free(dLut);
+    if (notFound) throw Error(RSQ_ERR_DEVICE, "dictionary pass over table " + t.name + ": a row holds a value that is not in the column's dictionary");
+    return (double)ms;
 }
 
 template <typename T, typename N>

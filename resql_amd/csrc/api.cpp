@@ -71,9 +71,11 @@ rsq_config readConfig(const rsq_config* cfg, bool multiBase) {
     c.struct_size = (uint32_t)sizeof(rsq_config);
     if (c.emission_order != RSQ_EMIT_REFERENCE && c.emission_order != RSQ_EMIT_ANY) failInvalid("rsq_config.emission_order must be RSQ_EMIT_REFERENCE (0) or RSQ_EMIT_ANY (1)");
     if (c.compat_flags & ~(uint32_t)RSQ_COMPAT_JIT_INT16_CAST) failInvalid("rsq_config.compat_flags has bits this library does not know");
-    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO | RSQ_ENGINE_NESTED_LOOPS | RSQ_ENGINE_DERIVED_MULTI)) failInvalid("rsq_config.engine_flags has bits this library does not know");
+    if (c.engine_flags & ~(uint32_t)(RSQ_ENGINE_DRIVER_ALLOC | RSQ_ENGINE_NO_PLAN_MEMO | RSQ_ENGINE_NESTED_LOOPS | RSQ_ENGINE_DERIVED_MULTI | RSQ_ENGINE_DICT_MULTI)) failInvalid("rsq_config.engine_flags has bits this library does not know");
     if ((c.engine_flags & RSQ_ENGINE_DERIVED_MULTI) && !multiBase)
         failInvalid("rsq_config.engine_flags has RSQ_ENGINE_DERIVED_MULTI, a setting of multi-GPU handles (rsq_multi_config.base) only");
+    if ((c.engine_flags & RSQ_ENGINE_DICT_MULTI) && !multiBase)
+        failInvalid("rsq_config.engine_flags has RSQ_ENGINE_DICT_MULTI, a setting of multi-GPU handles (rsq_multi_config.base) only");
     if (c.nested_loops_max_pairs < 0) failInvalid("rsq_config.nested_loops_max_pairs is negative (0: the default of 2^36 pairs)");
     if (c.nested_loops_max_pairs == 0) c.nested_loops_max_pairs = (int64_t)1 << 36;
     if (c.nested_loops_inner_slices < 0 || c.nested_loops_inner_slices > 4096)
@@ -201,6 +203,24 @@ int rsq_table_stats_export(const rsq_table* t, void* buf, int64_t bytes) {
 int rsq_table_unify_shard_stats(rsq_table* t, const void* blobs, int32_t n_shards, int64_t blob_bytes) {
     if (!t || !blobs || blob_bytes < 0) return RSQ_ERR_INVALID;
     return guarded(T(t)->ctx, [&] { unifyShardStats(*T(t), blobs, n_shards, (size_t)blob_bytes); });
+}
+int rsq_table_unify_shard_dictionaries(rsq_table* const* shards, int32_t n_shards) {
+    if (!shards || n_shards < 1) return RSQ_ERR_INVALID;
+    for (int32_t i = 0; i < n_shards; i++) if (!shards[i] || !T(shards[i])->ctx) return RSQ_ERR_INVALID;
+    // (the message goes to the first shard's context)
+    return guarded(T(shards[0])->ctx, [&] {
+        std::vector<Table*> ts;
+        for (int32_t i = 0; i < n_shards; i++) ts.push_back(T(shards[i]));
+        unifyShardDictionaries(ts);
+    });
+}
+int rsq_table_time_dictionary_pass(rsq_table* t, const char* column, int32_t which, double* ms) {
+    if (!t || !column || !ms || !T(t)->ctx) return RSQ_ERR_INVALID;
+    return guarded(T(t)->ctx, [&] {
+        const int ci = T(t)->findCol(column);
+        if (ci < 0) failInvalid(std::string("no such column: ") + column);
+        *ms = timeDictPass(*T(t)->ctx, *T(t), ci, which);
+    });
 }
 int64_t rsq_table_total_rows(const rsq_table* t) { return t ? reinterpret_cast<const Table*>(t)->totalRows() : -1; }
 

@@ -97,13 +97,17 @@ bool Walker::tryDenseKeys(OpNode* o) {
             if (!og) return no(key + "its bytes do not stand in a dictionary image");
             if (!repeatedKeysAbove.empty()) return no(key + "the build keys of " + repeatedKeysAbove + " repeat, and a row with several matches has no first group");
             if (underNestedLoops()) return no(key + "under a nested-loops join");
-            if (q.ctx.shardCompile) return no(key + "the statement runs on several shards");
-            if (t->nRowsTotal >= 0 || og->table->nRowsTotal >= 0) return no(key + (t->nRowsTotal >= 0 ? t->name : og->table->name) + " is a shard of a larger table");
-            if (std::find(q.tables.begin(), q.tables.end(), og->table) == q.tables.end()) return no(key + og->table->name + " is not a table of this statement");
+            // Across shards (RSQ_ENGINE_DICT_MULTI): the scan's table is a unified shard - every shard scans rows of its own - and all instances
+            // of the origin hold one dictionary (TableColumn::dictShared: a replicated table whose copies agree, or unified shards), so a rank
+            // is the same value on every shard and the dense tables merge.
             const TableColumn& c = og->table->cols[(size_t)og->col];
+            const bool acrossShards = t->nRowsTotal >= 0 && c.dictShared;
+            if (q.ctx.shardCompile && !acrossShards) return no(key + "the statement runs on several shards");
+            if ((t->nRowsTotal >= 0 || og->table->nRowsTotal >= 0) && !acrossShards) return no(key + (t->nRowsTotal >= 0 ? t->name : og->table->name) + " is a shard of a larger table");
+            if (std::find(q.tables.begin(), q.tables.end(), og->table) == q.tables.end()) return no(key + og->table->name + " is not a table of this statement");
             if (c.dictN <= 0 || c.type.len != og->len || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no(key + "its bytes do not stand in a dictionary image");
             DenseKey k; k.expr = g; k.type = c.type;
-            k.coded = true; k.scanCol = -1; k.originTable = og->table; k.originCol = og->col; k.card = c.dictN; k.dict = c.dict;
+            k.coded = true; k.scanCol = -1; k.originTable = og->table; k.originCol = og->col; k.card = c.dictN; k.dict = c.dict; k.shared = c.dictShared;
             k.spaceEquivalent = dictSpaceEquivalent(c);
             if (total > (int64_t)(1 << 24) / k.card) return no(key + "more than 2^24 groups");
             total *= k.card;
@@ -120,10 +124,13 @@ bool Walker::tryDenseKeys(OpNode* o) {
             // hold other dictionaries (their dense layouts would not line up), and not in any compile of a statement that runs on several
             // shards (Context::shardCompile: a table every shard holds alike has no nRowsTotal, and the shards' results are merged group by
             // group, which wants hash aggregations).  Every other string key: generic hash aggregation (bytes as key words)
+            // The exception (RSQ_ENGINE_DICT_MULTI): a unified shard whose siblings all hold this very dictionary (TableColumn::dictShared) -
+            // its codes are the ranks of the whole table's values, and the shards' dense tables merge like those of a byte-set key.
             int sc = -1;
             for (size_t p = 0; p < pipe.cols.size(); p++) if (pipe.cols[p] == ci) sc = (int)p;
-            if (!coded(sc) || t->nRowsTotal >= 0 || q.ctx.shardCompile || c.dictN <= 0 || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no();
-            k.coded = true; k.scanCol = sc; k.card = c.dictN; k.dict = c.dict;
+            const bool acrossShards = t->nRowsTotal >= 0 && c.dictShared;
+            if (!coded(sc) || ((t->nRowsTotal >= 0 || q.ctx.shardCompile) && !acrossShards) || c.dictN <= 0 || c.dict.size() != (size_t)c.dictN * (size_t)c.type.len) return no();
+            k.coded = true; k.scanCol = sc; k.card = c.dictN; k.dict = c.dict; k.shared = c.dictShared;
             k.spaceEquivalent = dictSpaceEquivalent(c);
             if (total > (int64_t)(1 << 24) / k.card) return no();
             total *= k.card;

@@ -36,6 +36,7 @@ struct DenseKey {
     const Table* originTable = nullptr;
     int originCol = -1;
     std::vector<uint8_t> dict;
+    bool shared = false;             // ... and every shard holds that dictionary (engine.h TableColumn::dictShared): the table merges with the shards'
     bool spaceEquivalent = false;    // coded CHAR(n): two entries are equal up to trailing spaces - one group to the reference (tail.cpp mergeEqualGroups)
 };
 inline bool anyCodedKey(const std::vector<DenseKey>& keys) { for (auto& k : keys) if (k.coded) return true; return false; }

@@ -201,7 +201,13 @@ bool denseMode(const Query& q) {
 // A dense table that other ranks' tables may be merged into: not one keyed by a dictionary code.  The dictionary is this process's own
 // (another rank's holds other values under the same codes), so the partial entry points - execute_partial*, partial_layout, bind_partial,
 // merge_gathered, finalize* - answer such a statement as they answer the hash aggregation it was before the codes became ranks.
-static bool partialCapable(const Query& q) { return denseMode(q) && !anyCodedKey(q.denseKeys); }
+// Unless every coded key's dictionary is the one all shards hold (DenseKey::shared, unifyShardDictionaries): then a rank is the same value
+// everywhere, and the table merges like any other (rsq_multi_query_compile compares the shards' dictionaries once more: queryPartialLayoutText).
+static bool partialCapable(const Query& q) {
+    if (!denseMode(q)) return false;
+    for (auto& k : q.denseKeys) if (k.coded && !k.shared) return false;
+    return true;
+}
 
 // Device-resident identity image of the dense aggregate table (0 for sums, +/-inf for min/max) and a pinned
 // host buffer for the read-back: one execute is then {D2D init, kernel(s), D2H} on one stream with a single
@@ -1940,7 +1946,16 @@ std::string queryPartialLayoutText(const Query& q) {
     size_t at = q.explainText.find("partial table:");
     if (at == std::string::npos) return "";
     size_t end = q.explainText.find('\n', at);
-    return q.explainText.substr(at, end == std::string::npos ? std::string::npos : end - at);
+    std::string text = q.explainText.substr(at, end == std::string::npos ? std::string::npos : end - at);
+    // ... and what explain leaves out: the entries behind a coded key's ranks, as their count and a 64-bit digest of their bytes (shards whose
+    // dictionaries differ must never merge their tables cell by cell)
+    for (auto& k : q.denseKeys)
+        if (k.coded) {
+            char hex[17];
+            snprintf(hex, sizeof hex, "%016llx", (unsigned long long)fnv1a64(std::string(k.dict.begin(), k.dict.end())));
+            text += " dictionary " + k.expr->symbol + "=" + std::to_string((long long)k.card) + ":" + hex;
+        }
+    return text;
 }
 const char* querySource(const Query& q) { return q.allSource.c_str(); }
 const char* queryExplain(const Query& q) { return q.explainText.c_str(); }

@@ -66,6 +66,10 @@ struct TableColumn {
     void* dictPtr = nullptr;
     void* codePtr = nullptr;
     size_t codeBytes = 0;
+    // every sibling instance of this table (the shards of one table, or its copies on the shards) holds this byte-identical dictionary:
+    // set by unifyShardDictionaries (aot_kernels.hip), cleared by whatever rebuilds the images.  Only then does a code mean the same
+    // value on every shard, and a dense table keyed by it merges with the siblings' (codegen_agg.cpp tryDenseKeys, engine.cpp partialCapable).
+    bool dictShared = false;
 };
 
 // the width of a column's narrow image: a pure function of its type, ownership and statistics (0 = none)
@@ -211,7 +215,8 @@ struct Context {
     bool planMemoOff = false;
     // set by rsq_multi_query_compile around the compiles of a statement that runs on more than one shard: no dense group ids from dictionary
     // codes there (codegen_agg.cpp tryDenseKeys) - a table the shards hold alike is not unified (nRowsTotal stays -1), and the group-level
-    // merge of the shards' results takes hash aggregations, not dense tables keyed by one context's dictionary
+    // merge of the shards' results takes hash aggregations, not dense tables keyed by one context's dictionary.  The exception: a unified
+    // shard scanned for a key whose dictionary all shards share (TableColumn::dictShared, RSQ_ENGINE_DICT_MULTI)
     bool shardCompile = false;
 };
 
@@ -382,6 +387,13 @@ bool shardGroupsDisjoint(const std::vector<Query*>& parts, std::string& why);   
 size_t tableStatsBytes(const Table& t);
 void exportTableStats(const Table& t, void* buf, size_t bytes);
 void unifyShardStats(Table& t, const void* blobs, int nShards, size_t blobBytes);
+// shard dictionaries (aot_kernels.hip): the instances of one table in one process, on any contexts.  Column by column: where every instance
+// with rows holds a dictionary and the union of their entries has at most 256 values, every instance receives the union (memcmp order) and
+// its codes are recoded in place (k_dict_recode); the column is marked TableColumn::dictShared everywhere.  Any other column stays as it
+// is.  An instance that changed has its layoutVersion bumped; instances that hold the union already are left alone (a second call changes
+// nothing).  replicated: the instances are copies of one table - nothing is rewritten, a column is marked where all dictionaries agree.
+void unifyShardDictionaries(const std::vector<Table*>& shards, bool replicated = false);
+double timeDictPass(Context& ctx, Table& t, int col, int which);      // device ms of one recode (0) / encode (1) pass over a coded column; the codes stay
 bool queryOrderedWithLimit(const Query& q);             // ORDER BY ... LIMIT k at the root
 bool queryHasDerived(const Query& q);                   // the plan has a derived aggregation (engine_internal.h DerivedState)
 [[noreturn]] void refuseDerived(const Query& q, const std::string& what);      // RSQ_ERR_UNSUPPORTED naming the plan's derived aggregation

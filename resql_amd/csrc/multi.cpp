@@ -570,6 +570,14 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             for (int t = 0; t < n_tables; t++)
                 if (blobBytes[(size_t)t])
                     for (int i = 0; i < n; i++) unifyShardStats(*tab(i, t), allBlobs[(size_t)t].data(), n, blobBytes[(size_t)t]);
+            // ... and with RSQ_ENGINE_DICT_MULTI one dictionary per coded column (engine.h unifyShardDictionaries): the shards of a table receive
+            // the union of their dictionaries, the copies of a replicated table are compared.  Nothing moves where the shards hold it already.
+            if ((m->ctxs[0]->cfg.engine_flags & RSQ_ENGINE_DICT_MULTI) && sw::dictScansEnabled())
+                for (int t = 0; t < n_tables; t++) {
+                    std::vector<Table*> inst;
+                    for (int i = 0; i < n; i++) inst.push_back(tab(i, t));
+                    unifyShardDictionaries(inst, !sharded[(size_t)t]);
+                }
         }
         // (more than one shard: every compile below keeps string group keys on the hash form - Context::shardCompile)
         struct ShardCompile {
@@ -779,6 +787,11 @@ int rsq_multi_query_report(const rsq_multi_query* mq, rsq_report* out, double* s
 double rsq_multi_query_collective_ms(const rsq_multi_query* mq) { return mq ? mq->collectiveMs : 0; }
 
 const char* rsq_multi_query_merge_name(const rsq_multi_query* mq) { return mq ? mq->mergeText.c_str() : ""; }
+
+const char* rsq_multi_query_explain(const rsq_multi_query* mq, int32_t shard) {
+    if (!mq || shard < 0 || shard >= (int32_t)mq->qs.size()) return nullptr;
+    return queryExplain(*mq->qs[(size_t)shard]);
+}
 
 void rsq_multi_query_destroy(rsq_multi_query* mq) { delete mq; }
 

@@ -61,7 +61,7 @@ class rsq_multi_config(C.Structure):
 MERGE_AUTO, MERGE_RCCL, MERGE_PEER_COPY = 0, 1, 2
 EMIT_REFERENCE, EMIT_ANY = 0, 1
 COMPAT_JIT_INT16_CAST = 1      # rsq_compat: TYPECAST INT -> BIGINT as the reference's asmjit JIT executes it (low 16 bits)
-ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS, ENGINE_DERIVED_MULTI = 1, 2, 4, 8      # rsq_engine_flags
+ENGINE_DRIVER_ALLOC, ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS, ENGINE_DERIVED_MULTI, ENGINE_DICT_MULTI = 1, 2, 4, 8, 16      # rsq_engine_flags
 
 
 class EngineError(RuntimeError):
@@ -114,6 +114,8 @@ def lib():
         L.rsq_table_stats_bytes.argtypes = [vp]
         L.rsq_table_stats_export.argtypes = [vp, vp, i64]
         L.rsq_table_unify_shard_stats.argtypes = [vp, vp, i32, i64]
+        L.rsq_table_unify_shard_dictionaries.argtypes = [C.POINTER(vp), i32]
+        L.rsq_table_time_dictionary_pass.argtypes = [vp, C.c_char_p, i32, C.POINTER(C.c_double)]
         L.rsq_table_total_rows.restype = i64
         L.rsq_table_total_rows.argtypes = [vp]
         L.rsq_table_destroy.argtypes = [vp]
@@ -186,6 +188,8 @@ def lib():
         L.rsq_multi_table_generate_on_key.argtypes = [vp, i32, i64, C.c_double, i64, C.c_uint64, C.c_char_p, C.POINTER(vp)]
         L.rsq_multi_query_merge_name.restype = C.c_char_p
         L.rsq_multi_query_merge_name.argtypes = [vp]
+        L.rsq_multi_query_explain.restype = C.c_char_p
+        L.rsq_multi_query_explain.argtypes = [vp, i32]
         L.rsq_multi_query_compile.argtypes = [vp, C.POINTER(P.rsq_plan_desc), C.POINTER(vp), i32, C.POINTER(vp)]
         L.rsq_multi_query_execute.argtypes = [vp]
         L.rsq_multi_query_result.argtypes = [vp, C.POINTER(P.rsq_result_view)]
@@ -200,7 +204,7 @@ def lib():
 EXPORTED_SYMBOLS = [
     "rsq_ctx_create", "rsq_ctx_destroy", "rsq_last_error", "rsq_table_create", "rsq_table_create_device",
     "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
-    "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_total_rows",
+    "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_unify_shard_dictionaries", "rsq_table_time_dictionary_pass", "rsq_table_total_rows",
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_nested_loops_slices", "rsq_nested_loops_slices", "rsq_query_source", "rsq_query_explain",
@@ -211,7 +215,7 @@ EXPORTED_SYMBOLS = [
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_destroy",
     "rsq_multi_create", "rsq_multi_destroy", "rsq_multi_last_error", "rsq_multi_devices", "rsq_multi_ctx", "rsq_multi_merge_name",
-    "rsq_multi_shard_rows", "rsq_multi_table_generate", "rsq_multi_table_generate_on_key", "rsq_multi_query_merge_name", "rsq_multi_query_compile", "rsq_multi_query_execute",
+    "rsq_multi_shard_rows", "rsq_multi_table_generate", "rsq_multi_table_generate_on_key", "rsq_multi_query_merge_name", "rsq_multi_query_explain", "rsq_multi_query_compile", "rsq_multi_query_execute",
     "rsq_multi_query_result", "rsq_multi_query_report", "rsq_multi_query_collective_ms", "rsq_multi_query_destroy",
 ]
 
@@ -221,6 +225,15 @@ NLJ_MIN_SLICE_ROWS = 512      # include/resql_hip.h RSQ_NLJ_MIN_SLICE_ROWS: the 
 def nested_loops_slices(base_workgroups: int, max_workgroups: int, inner_rows: int, configured: int = 0) -> int:
     """rsq_nested_loops_slices: the slices a launch with these workgroup counts cuts the inner rows of a nested-loops join into"""
     return lib().rsq_nested_loops_slices(base_workgroups, max_workgroups, inner_rows, configured)
+
+
+def unify_shard_dictionaries(tables: Sequence["DeviceTable"]) -> None:
+    """one dictionary per dictionary-coded column for the shards of ONE table held in this process (rsq_table_unify_shard_dictionaries):
+    the union of the shards' entries where it has at most 256 values, codes rewritten in place; other columns stay as they are"""
+    if not tables:
+        raise ValueError("unify_shard_dictionaries: no tables")
+    arr = (C.c_void_p * len(tables))(*[t.h for t in tables])
+    tables[0].ctx._check(lib().rsq_table_unify_shard_dictionaries(arr, len(tables)))
 
 
 GEN_LINEITEM, GEN_ORDERS, GEN_CUSTOMER, GEN_SYNTHETIC = 0, 1, 2, 3
@@ -536,6 +549,12 @@ class DeviceTable:
         joined = b"".join(blobs)
         self.ctx._check(self.ctx._L.rsq_table_unify_shard_stats(self.h, joined, len(blobs), len(blobs[0]) if blobs else 0))
 
+    def time_dictionary_pass(self, name: str, which: int) -> float:
+        """device ms of one pass over a coded column: which 0 the recode pass (identity map), 1 encoding the wide column anew; the codes stay"""
+        ms = C.c_double(0)
+        self.ctx._check(self.ctx._L.rsq_table_time_dictionary_pass(self.h, name.encode(), which, C.byref(ms)))
+        return ms.value
+
     def read_column(self, name: str, dtype, count: Optional[int] = None) -> np.ndarray:
         n = self.n_rows if count is None else count
         out = np.empty(n, dtype=dtype)
@@ -711,7 +730,8 @@ class MultiContext:
     def __init__(self, devices: Sequence[int], merge: int = MERGE_AUTO, cache_dir: Optional[str] = None, emission_order: int = 0,
                  compat_flags: int = 0, engine_flags: int = 0, nested_loops_max_pairs: int = 0, nested_loops_inner_slices: int = 0):
         """engine_flags, nested_loops_max_pairs, nested_loops_inner_slices: as for Context, on every shard (ENGINE_DERIVED_MULTI, for these handles only, runs derived
-        aggregations across the shards; ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
+        aggregations across the shards; ENGINE_DICT_MULTI, likewise, gives the shards of a table one dictionary per coded column, so that a
+        GROUP BY over it merges as dense partial tables; ENGINE_NESTED_LOOPS splits a nested-loops join's pairs
         by its outer side's rows; the budget bounds the whole statement's pairs)"""
         self._L = lib()
         self._devs = (C.c_int32 * len(devices))(*devices)
@@ -806,6 +826,13 @@ class MultiQuery:
     @property
     def merge_name(self) -> str:
         return self.m._L.rsq_multi_query_merge_name(self.h).decode()
+
+    def explain(self, shard: int = 0) -> str:
+        """the explain text of one shard's statement"""
+        s = self.m._L.rsq_multi_query_explain(self.h, shard)
+        if s is None:
+            raise IndexError(f"no shard {shard}")
+        return s.decode()
 
     @property
     def collective_ms(self) -> float:

@@ -19,7 +19,19 @@ usage: python tools/dict_group_bench.py [SF] --join-keys --parent-tree DIR [--ru
 Dense group ids for a string from a join's build side (RSQ_DICT_SCANS=2): TPC-H Q5, whose n_name reaches lineitem's aggregation through
 the supplier's table, and Q12 as the control (its key is lineitem's own column: 1 and 2 give it one kernel).  One worker per build
 loads the six tables Q5 reads with the images on and compiles both statements under RSQ_DICT_SCANS = 0, 1 and 2 (the parent: 0 and 1);
-all stay resident and the runs alternate between builds and switches.  Every answer is compared with tests/golden/ref_full_<q>_sf<SF>.tbl."""
+all stay resident and the runs alternate between builds and switches.  Every answer is compared with tests/golden/ref_full_<q>_sf<SF>.tbl.
+
+usage: python tools/dict_group_bench.py [SF] --shards N[,N...] [--runs N] [--repeat N] [--out FILE] [--sha SHA]
+One dictionary across shards (ENGINE_DICT_MULTI): TPC-H Q12 and Q5 over N shard contexts on ONE GPU (MultiContext([0] * N)), lineitem
+sharded by rows and every other table replicated, RSQ_DICT_SCANS=2.  Two handles of this build stay resident, one with the flag and one
+without (the parent commit's behaviour), and the runs alternate between them.  Per handle and statement: the merge the statement takes,
+whether the answer is tests/golden/ref_full_<q>_sf<SF>.tbl, and median [min, max] of execution, kernel and collective time.  N contexts
+on one device take turns on it: the figures compare the kernel form and the merge form, they say nothing about scaling.
+
+usage: python tools/dict_group_bench.py [SF] --recode [--runs N] [--out FILE] [--sha SHA]
+The recode pass that installs a union dictionary (k_dict_recode) against what it replaces, encoding the wide column anew
+(k_dict_encode), over lineitem's l_shipmode at scale factor SF: device time by events, one process, the two alternating.  --recode and
+--shards may be given together: the tables are generated once."""
 import json
 import os
 import statistics
@@ -169,6 +181,92 @@ def join_keys(sf, runs, repeat, emit, parent_tree):
             p.wait()
 
 
+def shards_mode(sf, n, runs, repeat, emit, db):
+    os.environ["RSQ_DICT_SCANS"] = "2"
+    from resql_amd import engine, plan as P, tpch_full
+    names = sorted(db)
+    li = db["lineitem"]
+    emit({"note": f"{n} shard contexts on one device take turns on it: these figures compare the kernel form and the merge form of the two "
+                  "settings, not scaling", "sf": sf, "shards": n})
+    handles, qs = {}, {}
+    try:
+        for flag in ("off", "on"):
+            m = engine.MultiContext([0] * n, engine_flags=engine.ENGINE_DICT_MULTI if flag == "on" else 0)
+            per = []
+            for i, sh in enumerate(m.shards):
+                r0, nr = m.shard_rows(li.n_rows, i)
+                part = P.Table("lineitem", [P.Column(c.name, c.type, None if c.data is None else c.data[r0:r0 + nr]) for c in li.columns], nr)
+                tabs = [sh.table(part if k == "lineitem" else db[k]) for k in names]
+                tabs[names.index("lineitem")].set_row0(r0)
+                per.append(tabs)
+            # the plan is made over shard 0's tables: lineitem's shards size like the whole table from the start (the compile would unify
+            # them anyway), or a quarter of lineitem is no larger than orders and the planner turns Q12's join round
+            shards = [tabs[names.index("lineitem")] for tabs in per]
+            blobs = [t.stats_blob() for t in shards]
+            for t in shards:
+                t.unify_shard_stats(blobs)
+            handles[flag] = (m, per)
+            print(f"[{flag}] tables loaded", file=sys.stderr, flush=True)
+        for name in ("q12", "q5"):
+            gold = os.path.join(HERE, "tests", "golden", f"ref_full_{name}_sf{sf:g}.tbl")
+            want = open(gold, encoding="latin1").read() if os.path.exists(gold) else None
+            m0, per0 = handles["off"]
+            plan = m0.shards[0].sql_plan(tpch_full.QUERIES[name], per0[0], [db[k] for k in names])
+            for flag, (m, per) in handles.items():
+                q = m.compile(plan, per)
+                for _ in range(3):
+                    q.execute()
+                qs[(name, flag)] = q
+                text = q.result().text
+                emit({"statement": name, "sf": sf, "shards": n, "ENGINE_DICT_MULTI": flag, "merge": q.merge_name,
+                      "aggregation": [s for l in q.explain(0).splitlines() if l.startswith("pipeline") for s in l.split(" -> ") if "aggregation" in s],
+                      "equals_reference_answer": None if want is None else text == want})
+        series = {k: [] for k in qs}
+        for run in range(1, runs + 1):
+            for key in (sorted(qs) if run % 2 else sorted(qs, reverse=True)):     # (alternating, and alternating who goes first)
+                q, ex, ke, co = qs[key], [], [], []
+                for _ in range(repeat):
+                    q.execute()
+                    r = q.report()[0]
+                    ex.append(r.execution_time_ms)
+                    ke.append(r.kernel_time_ms)
+                    co.append(q.collective_ms)
+                v = {"exec_ms_median": statistics.median(ex), "kernel_ms_median": statistics.median(ke), "collective_ms_median": statistics.median(co)}
+                series[key].append(v)
+                emit(dict(v, statement=key[0], ENGINE_DICT_MULTI=key[1], shards=n, run=run))
+        for key, vs in sorted(series.items()):
+            cols = {k: [v[k + "_ms_median"] for v in vs] for k in ("exec", "kernel", "collective")}
+            emit(dict({"summary": key[0], "ENGINE_DICT_MULTI": key[1], "shards": n, "runs": runs, "executions_per_run": repeat},
+                      **{k + "_ms": {"median": round(statistics.median(c), 4), "min": round(min(c), 4), "max": round(max(c), 4)} for k, c in cols.items()}))
+    finally:
+        for q in qs.values():
+            q.close()
+        for m, per in handles.values():
+            m.close()
+
+
+def recode_mode(sf, runs, emit, db):
+    os.environ["RSQ_DICT_SCANS"] = "1"
+    from resql_amd import engine, plan as P
+    c = db["lineitem"].col("l_shipmode")
+    ctx = engine.Context(device=0)
+    tab = ctx.table(P.Table("lineitem", [P.Column(c.name, c.type, c.data)], len(c.data)))
+    try:
+        series = {"recode": [], "encode": []}
+        for run in range(runs + 1):                                           # (run 0 warms both)
+            for which in (("recode", "encode") if run % 2 else ("encode", "recode")):
+                ms = tab.time_dictionary_pass("l_shipmode", 0 if which == "recode" else 1)
+                if run:
+                    series[which].append(ms)
+                    emit({"pass": which, "column": "l_shipmode", "sf": sf, "rows": tab.n_rows, "run": run, "device_ms": round(ms, 4)})
+        for which, v in series.items():
+            emit({"summary": which, "column": "l_shipmode", "sf": sf, "rows": tab.n_rows, "entries": tab.image_info("l_shipmode")[2], "runs": runs,
+                  "device_ms": {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}})
+    finally:
+        tab.close()
+        ctx.close()
+
+
 TAIL_SQL = "select l_shipmode, l_suppkey, count(*), sum(l_quantity) from lineitem group by l_shipmode, l_suppkey"
 
 
@@ -229,6 +327,19 @@ def main():
         if out:
             out.write(line + "\n")
             out.flush()
+
+    if "--shards" in sys.argv or "--recode" in sys.argv:
+        sys.path.insert(0, HERE)
+        from resql_amd import tpch_full
+        db = tpch_full.database(sf, fill_unused=False)                        # (generated once for everything asked for)
+        print("tables generated", file=sys.stderr, flush=True)
+        if "--recode" in sys.argv:
+            recode_mode(sf, runs, emit, db)
+        for n in ([int(x) for x in arg("--shards", "").split(",")] if "--shards" in sys.argv else []):
+            shards_mode(sf, n, runs, repeat, emit, db)
+        if sha:
+            emit({"head_sha": sha})
+        return
 
     if "--join-keys" in sys.argv:
         join_keys(sf, runs, repeat, emit, arg("--parent-tree", ""))
