@@ -401,13 +401,9 @@ bool queryHasDerived(const Query& q);                   // the plan has a derive
 // query per shard, same plan; `tables` [shard][nTables]; `sharded[t]`: table t's instances differ between the shards.  The plan step
 // decides every derived table's split (local / merged, sliced / whole) or refuses naming the table, and marks the queries so that
 // executeQuery leaves their derived tables to the run step, which builds them on every shard (innermost first).
-typedef std::function<void(const std::function<void(int)>&)> ShardThreads;     // runs f(shard) for every shard, on host threads
 struct DerivedMultiRun { int64_t exchangeBytes = 0; double exchangeMs = 0; std::string text; };
 std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* const* tables, int nTables, const std::vector<bool>& sharded);
-void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out);
-// multi.cpp: `bytes` from device memory on srcDevice to device memory on dstDevice, enqueued on `stream` (dstDevice's): a device-to-device
-// copy when both are one device, else a peer copy
-void copyDeviceAsync(void* dst, int dstDevice, const void* src, int srcDevice, size_t bytes, hipStream_t stream);
+void runDerivedAcrossShards(const std::vector<Query*>& qs, DerivedMultiRun& out);      // (the exchanges themselves: shard_exchange.h)
 bool queryAsyncCapable(const Query& q);                 // every pipeline can be enqueued without the host in between
 bool queryIsDense(const Query& q);              // its aggregation ends in a dense partial table ([min | max | sum] words)
 void queryDenseLayout(const Query& q, int64_t* nMin, int64_t* nMax, int64_t* nSum, void** dptr);

@@ -8,26 +8,25 @@
 //           tables - the reference has ONE hash table all workers reach (aggregation.h:240-343, JitContextFlounder.h:459-487);
 //   anything else is refused, naming the table.
 // Merged, hash / join-entry groups: on the DEVICE path (where one context's sub-query would take its device tail) the shards' group rows
-// are gathered to the root in shard order with peer copies, merged by key in one device hash table (devtail.hip k_gm_*), and go through
-// the device tail's emission order; the root writes its columns and copies them (or each shard's slice) to the other shards.  On the
-// HOST path the root merges them with runTailMerged and every shard uploads the tuples and writes its own columns.  A dense sub-query
-// merges its partial tables on the root (mergePartialsAsync) and finalises there; its tuples then travel the same two ways.
+// are gathered to the root in shard order (shard_exchange.h gatherParts), merged by key in one device hash table (devtail.hip k_gm_*),
+// and go through the device tail's emission order; the root writes its columns and copies them (or each shard's slice) to the other
+// shards.  On the HOST path the root merges them with runTailMerged and every shard uploads the tuples and writes its own columns.  A
+// dense sub-query merges its partial tables on the root (shard_exchange.h mergeDenseOnRoot) and finalises there; its tuples then travel
+// the same two ways.  The events between the shards' streams and the shards' host threads are that layer's too.
 // Where the table lands: the source of the plan's last pipeline is scanned slice by slice (rsq_multi_shard_rows of its rows, the slice's
 // first row numbered over the whole table, bound at launch); any other place (a build side, an earlier pipeline's source) holds it whole.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <map>
 
 #include "engine_internal.h"
+#include "shard_exchange.h"
 
 namespace rsq {
 
 namespace {
 
 enum { LOCAL = 1, MERGED = 2 };
-
-double wallMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 void scansOf(OpNode* o, std::vector<OpNode*>& out) {
     if (!o) return;
@@ -120,9 +119,7 @@ void* mergeBuffer(Context& root, DerivedState& d, size_t bytes) {
 }
 
 struct Runner {
-    const ShardThreads* onThreads = nullptr;
     DerivedMultiRun* out = nullptr;
-    bool trace = false;
 
     void run(const std::vector<Query*>& qs, const std::string& prefix) {
         const int n = (int)qs.size();
@@ -131,17 +128,14 @@ struct Runner {
             for (Query* q : qs) subs.push_back(q->derived[k].sub.query.get());
             run(subs, prefix + qs[0]->derived[k].table->name + "/");      // (the tables below it first)
             const std::string name = prefix + qs[0]->derived[k].table->name;
-            if (qs[0]->derived[k].multi == LOCAL || n == 1) {
-                (*onThreads)([&](int i) {
-                    Query& q = *qs[(size_t)i];
-                    buildDerived(q, q.derived[k]);
-                    applySlice(q.derived[k]);
-                });
-                if (trace) fprintf(stderr, "[rsq trace] %s: %lld rows, local on %d shards\n", name.c_str(), (long long)qs[0]->derived[k].table->totalRows(), n);
-                describe(name, "local", qs[0]->derived[k], -1);
-                continue;
-            }
-            merged(qs, k, name);
+            if (qs[0]->derived[k].multi != LOCAL && n > 1) { merged(qs, k, name); continue; }
+            onShardThreads(n, [&](int i) {
+                Query& q = *qs[(size_t)i];
+                buildDerived(q, q.derived[k]);
+                applySlice(q.derived[k]);
+            });
+            traceLine("[rsq trace] %s: %lld rows, local on %d shards\n", name.c_str(), (long long)qs[0]->derived[k].table->totalRows(), n);
+            describe(name, "local", qs[0]->derived[k], -1);
         }
     }
 
@@ -157,81 +151,57 @@ struct Runner {
         Query& s0 = *d0.sub.query;
         Context& root = q0.ctx;
         const bool dense = queryIsDense(s0);
-        std::vector<hipEvent_t> done((size_t)n, nullptr);
-        hipEvent_t written = nullptr;
-        auto cleanup = [&] {
-            for (int i = 0; i < n; i++) if (done[(size_t)i]) { (void)hipSetDevice(qs[(size_t)i]->ctx.device); (void)hipEventDestroy(done[(size_t)i]); }
-            if (written) { (void)hipSetDevice(root.device); (void)hipEventDestroy(written); }
-        };
-        try {
-            // every shard's sub-query up to its group rows (hash) or its partial table (dense)
-            (*onThreads)([&](int i) {
-                SubQuery& sub = qs[(size_t)i]->derived[k].sub;
-                Query& s = *sub.query;
-                RSQ_HIP(hipSetDevice(s.ctx.device));
-                if (!dense) { setHoldTail(s, true); s.holdTailOnDevice = true; }
-                runSubQuery(sub, dense);
-                RSQ_HIP(hipEventCreateWithFlags(&done[(size_t)i], hipEventDisableTiming));
-                RSQ_HIP(hipEventRecord(done[(size_t)i], s.ctx.stream));
-            });
-            const double t0 = wallMs();
-            int64_t moved = 0;
-            std::string path;
-            if (dense) path = exchangeDense(qs, k, done, moved);
-            else path = exchangeRows(qs, k, done, moved);
-            // the root's columns, then every other shard's: copies of the root's (tuples on the root's device) or its own writer over the uploaded tuples
-            const bool devTuples = s0.resultInPinned && s0.resultDev != nullptr;
-            RSQ_HIP(hipSetDevice(root.device));
-            writeDerivedFrom(q0, d0, s0, true);
-            RSQ_HIP(hipEventCreateWithFlags(&written, hipEventDisableTiming));
-            RSQ_HIP(hipEventRecord(written, root.stream));
-            const int64_t rows = d0.table->nRows;
-            for (int j = 1; j < n; j++) {
-                Query& q = *qs[(size_t)j];
-                DerivedState& d = q.derived[k];
-                if (devTuples) {
-                    int64_t r0 = 0, nr = rows;
-                    if (d.sliceShards > 0) rsq_multi_shard_rows(rows, d.sliceShards, d.sliceAt, &r0, &nr);
-                    copyColumns(root, d0, q.ctx, d, r0, nr, written, &moved);
-                } else {
-                    RSQ_HIP(hipSetDevice(q.ctx.device));
-                    writeDerivedFrom(q, d, s0, false);
-                }
+        // every shard's sub-query up to its group rows (hash) or its partial table (dense)
+        std::vector<ShardEvent> done((size_t)n);
+        onShardThreads(n, [&](int i) {
+            SubQuery& sub = qs[(size_t)i]->derived[k].sub;
+            Query& s = *sub.query;
+            RSQ_HIP(hipSetDevice(s.ctx.device));
+            if (!dense) { setHoldTail(s, true); s.holdTailOnDevice = true; }
+            runSubQuery(sub, dense);
+            done[(size_t)i] = ShardEvent(s.ctx, false);
+            done[(size_t)i].record(s.ctx.stream);
+        });
+        const double t0 = nowMs();
+        int64_t moved = 0;
+        const std::string path = dense ? exchangeDense(qs, k, done, moved) : exchangeRows(qs, k, done, moved);
+        // the root's columns, then every other shard's: copies of the root's (tuples on the root's device) or its own writer over the uploaded tuples
+        const bool devTuples = s0.resultInPinned && s0.resultDev != nullptr;
+        RSQ_HIP(hipSetDevice(root.device));
+        writeDerivedFrom(q0, d0, s0, true);
+        ShardEvent written(root, false);
+        written.record(root.stream);
+        const int64_t rows = d0.table->nRows;
+        for (int j = 1; j < n; j++) {
+            Query& q = *qs[(size_t)j];
+            DerivedState& d = q.derived[k];
+            if (devTuples) {
+                int64_t r0 = 0, nr = rows;
+                if (d.sliceShards > 0) rsq_multi_shard_rows(rows, d.sliceShards, d.sliceAt, &r0, &nr);
+                copyColumns(root, d0, q.ctx, d, r0, nr, written.get(), &moved);
+            } else {
+                RSQ_HIP(hipSetDevice(q.ctx.device));
+                writeDerivedFrom(q, d, s0, false);
             }
-            for (int i = 0; i < n; i++) applySlice(qs[(size_t)i]->derived[k]);
-            for (int i = 0; i < n; i++) { RSQ_HIP(hipSetDevice(qs[(size_t)i]->ctx.device)); RSQ_HIP(hipStreamSynchronize(qs[(size_t)i]->ctx.stream)); }
-            const double ms = wallMs() - t0;
-            out->exchangeMs += ms;
-            out->exchangeBytes += moved;
-            if (trace)
-                fprintf(stderr, "[rsq trace] %s: %lld rows merged %s over %d shards (%lld bytes moved, %.3f ms)\n", name.c_str(), (long long)rows,
-                        path.c_str(), n, (long long)moved, ms);
-            describe(name, "merged " + path + " over " + std::to_string(n) + " shards", d0, moved);
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        }
+        for (int i = 0; i < n; i++) applySlice(qs[(size_t)i]->derived[k]);
+        for (int i = 0; i < n; i++) { RSQ_HIP(hipSetDevice(qs[(size_t)i]->ctx.device)); RSQ_HIP(hipStreamSynchronize(qs[(size_t)i]->ctx.stream)); }
+        const double ms = nowMs() - t0;
+        out->exchangeMs += ms;
+        out->exchangeBytes += moved;
+        traceLine("[rsq trace] %s: %lld rows merged %s over %d shards (%lld bytes moved, %.3f ms)\n", name.c_str(), (long long)rows, path.c_str(), n, (long long)moved, ms);
+        describe(name, "merged " + path + " over " + std::to_string(n) + " shards", d0, moved);
     }
 
-    // partial tables -> the root's gather buffer (peer copies in shard order) -> the engine's merge kernel -> the root's tail
-    std::string exchangeDense(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
-        const int n = (int)qs.size();
-        Query& s0 = *qs[0]->derived[k].sub.query;
-        Context& root = s0.ctx;
+    // the shared dense merge on the root (gather buffer: mergeBuffer), then the root's tail
+    std::string exchangeDense(const std::vector<Query*>& qs, size_t k, const std::vector<ShardEvent>& done, int64_t& moved) {
+        std::vector<Query*> subs;
+        for (Query* q : qs) subs.push_back(q->derived[k].sub.query.get());
+        Query& s0 = *subs[0];
         int64_t nMin, nMax, nSum; void* p0;
         queryDenseLayout(s0, &nMin, &nMax, &nSum, &p0);
-        const int64_t words = nMin + nMax + nSum;
-        int64_t* gathered = (int64_t*)mergeBuffer(root, qs[0]->derived[k], (size_t)n * (size_t)words * 8);
-        RSQ_HIP(hipSetDevice(root.device));
-        for (int i = 0; i < n; i++) {
-            Query& s = *qs[(size_t)i]->derived[k].sub.query;
-            int64_t a, b, c; void* part;
-            queryDenseLayout(s, &a, &b, &c, &part);
-            if (a != nMin || b != nMax || c != nSum) throw Error(RSQ_ERR_RUNTIME, "internal: shards disagree on the partial table of a derived aggregation");
-            RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
-            int64_t* to = gathered + (size_t)i * (size_t)words;
-            copyDeviceAsync(to, root.device, part, s.ctx.device, (size_t)words * 8, root.stream);
-            if (i > 0) moved += words * 8;
-        }
-        mergePartialsAsync(root, gathered, n, words, nMin, nMax, nSum, (int64_t*)p0);
+        int64_t* gathered = (int64_t*)mergeBuffer(s0.ctx, qs[0]->derived[k], qs.size() * (size_t)(nMin + nMax + nSum) * 8);
+        moved += mergeDenseOnRoot(subs, done, gathered, "internal: shards disagree on the partial table of a derived aggregation");
         const uint64_t before = s0.report.num_kernels;
         finalizeQuery(s0);
         qs[0]->derived[k].sub.kernels += 1 + (s0.report.num_kernels >= before ? s0.report.num_kernels - before : 0);      // (the merge and the tail's launches)
@@ -239,7 +209,7 @@ struct Runner {
     }
 
     // group rows: gathered and merged on the root's device (device path), or merged by the host (host path)
-    std::string exchangeRows(const std::vector<Query*>& qs, size_t k, const std::vector<hipEvent_t>& done, int64_t& moved) {
+    std::string exchangeRows(const std::vector<Query*>& qs, size_t k, const std::vector<ShardEvent>& done, int64_t& moved) {
         const int n = (int)qs.size();
         DerivedState& d0 = qs[0]->derived[k];
         Query& s0 = *d0.sub.query;
@@ -275,18 +245,9 @@ struct Runner {
         int64_t* mergedRows = (int64_t*)(buf + up(rowBytes));
         void* temp = buf + up(rowBytes) * 2;
         uint64_t* dCount = (uint64_t*)(buf + up(rowBytes) * 2 + up(groupMergeTempBytes(total)));
-        RSQ_HIP(hipSetDevice(root.device));
-        int64_t at = 0;
-        for (int i = 0; i < n; i++) {
-            Query& s = *subs[(size_t)i];
-            RSQ_HIP(hipStreamWaitEvent(root.stream, done[(size_t)i], 0));
-            const size_t b = (size_t)s.nGroupRows * (size_t)stride * 8;
-            if (b) {
-                copyDeviceAsync(gathered + (size_t)at * (size_t)stride, root.device, s.dGroupRows, s.ctx.device, b, root.stream);
-                if (i > 0) moved += (int64_t)b;
-            }
-            at += s.nGroupRows;
-        }
+        std::vector<GatherPart> parts;
+        for (int i = 0; i < n; i++) parts.push_back({&subs[(size_t)i]->ctx, subs[(size_t)i]->dGroupRows, (size_t)subs[(size_t)i]->nGroupRows * (size_t)stride * 8, done[(size_t)i].get()});
+        moved += gatherParts(root, gathered, parts);
         mergeGroupRows(root, gathered, total, spec, temp, mergedRows, dCount);
         uint64_t groups = 0;
         uint32_t err = 0;
@@ -334,11 +295,9 @@ std::string planDerivedAcrossShards(const std::vector<Query*>& qs, rsq_table* co
     return where + (text.empty() ? "" : " (" + text + ")");
 }
 
-void runDerivedAcrossShards(const std::vector<Query*>& qs, const ShardThreads& onThreads, DerivedMultiRun& out) {
+void runDerivedAcrossShards(const std::vector<Query*>& qs, DerivedMultiRun& out) {
     out = DerivedMultiRun();
-    Runner r;
-    r.onThreads = &onThreads; r.out = &out; r.trace = sw::traceOn();
-    r.run(qs, "");
+    Runner{&out}.run(qs, "");
 }
 
 }  // namespace rsq

@@ -8,23 +8,25 @@
 // issued from this process through communicators made by ncclCommInitAll.  librccl is loaded with dlopen when the first
 // multi-GPU handle is created, so that hosts with one GPU (and machines without RCCL) never need it.
 //
-// A second merge path moves the partial tables with peer copies into the root GPU and reduces them with the engine's own
-// merge kernel (no RCCL): chosen with rsq_multi_config.merge = RSQ_MERGE_PEER_COPY, and the only one possible when a device
-// ordinal is listed twice — which is how a box with ONE GPU exercises N-shard execution end to end (tests).
+// A second merge path gathers the partial tables on the root GPU and reduces them with the engine's own merge kernel (no RCCL,
+// shard_exchange.h mergeDenseOnRoot): chosen with rsq_multi_config.merge = RSQ_MERGE_PEER_COPY, and the only one possible when a
+// device ordinal is listed twice — which is how a box with ONE GPU exercises N-shard execution end to end (tests).
 //
 // Plans that do not end in a dense partial table (joins with many groups, hash aggregation, plain materialisation) run
 // whole on every shard in parallel host threads; the shards must then be disjoint in the group key (the caller shards the
 // probe-side table on a key boundary and replicates the build sides), and the merge is a host-side ordered
 // merge of the (LIMIT-ed) result rows.
+//
+// Whatever passes between shards here - events, gathers, the dense merge, peer access, the shards' host threads - is shard_exchange.h's.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <cstring>
 #include <set>
-#include <thread>
 
 #include "engine_internal.h"
+#include "shard_exchange.h"
 
 using namespace rsq;
 
@@ -82,61 +84,41 @@ struct rsq_multi {
     }
 };
 
+// a nested-loops join (see "Nested-loops joins across GPUs" below): its pair space split by the outer side's rows
+struct NljSplit {
+    bool gathered = false;              // the inner side is sharded: every shard's part is all-gathered into every shard (else replicated)
+    std::vector<std::unique_ptr<Table>> outerSlices;      // a replicated outer table: shard i's slice of its copy (views, no rows of their own)
+    std::vector<ShardEvent> innerDone;  // shard i's inner part is materialised (the gather's copies wait for it)
+    std::vector<ShardEvent> gather0, gather1;             // around the gather's copies on shard i's stream
+    int64_t gatherBytes = -1;           // moved between shards by the last gather (-1: none has run)
+};
+
 struct rsq_multi_query {
     rsq_multi* m = nullptr;
     std::vector<Query*> qs;             // one compiled query per device, same plan
     bool dense = false;
     bool async = false;                 // dense and every pipeline can be enqueued without the host in between (no join builds)
     bool orderedFast = false;           // not dense: shards provably disjoint in a group key + ORDER BY ... LIMIT: merge of the shards' ordered rows
-    std::string mergeText;              // which merge this query takes, and why
-    int64_t nMin = 0, nMax = 0, nSum = 0;
+    std::string mergeText;              // which merge this query takes, and why (composeMergeText)
+    std::string mergeBase, derivedText; // ... its parts: the merge of the plan's kind, the derived tables' splits
     int64_t* gathered = nullptr;        // peer-copy mode: [n][words] on the root device
-    std::vector<hipEvent_t> ready;      // peer-copy mode: shard i's partial table is complete
+    std::vector<ShardEvent> ready;      // peer-copy mode: shard i's partial table is complete (none for the root)
     rsq_report report{};
     std::vector<double> shardKernelMs;
-    hipEvent_t evMerge0 = nullptr, evMerge1 = nullptr;      // on the root's stream, around the group-by merge of the last execution
+    ShardEvent evMerge0, evMerge1;      // on the root's stream, around the group-by merge of the last execution
     double collectiveMs = 0;
-    // a nested-loops join (see "Nested-loops joins across GPUs" below): its pair space split by the outer side's rows
     bool nlj = false;
-    bool nljGathered = false;           // the inner side is sharded: every shard's part is all-gathered into every shard (else replicated)
-    std::string mergeBase;              // mergeText behind the split's description
-    std::vector<std::unique_ptr<Table>> outerSlices;      // a replicated outer table: shard i's slice of its copy (views, no rows of their own)
-    std::vector<hipEvent_t> innerDone;  // shard i's inner part is materialised (the gather's copies wait for it)
-    std::vector<hipEvent_t> gather0, gather1;             // around the gather's copies on shard i's stream
-    int64_t gatherBytes = 0;            // moved between shards by the last gather
+    NljSplit split;
     // derived aggregations (engine_derived_multi.cpp): built on every shard in front of the parent's pipelines
     bool derived = false;
     double derivedMs = 0;               // the last execution's exchanges (part of the collective time)
     ~rsq_multi_query() {
-        for (size_t i = 0; i < innerDone.size(); i++) {      // (a compilation that failed part-way made some of them only)
-            (void)hipSetDevice(m->ctxs[i]->device);
-            for (hipEvent_t e : {innerDone[i], gather0[i], gather1[i]}) if (e) (void)hipEventDestroy(e);
-        }
-        if (evMerge0 && m && !m->ctxs.empty()) { (void)hipSetDevice(m->ctxs[0]->device); (void)hipEventDestroy(evMerge0); (void)hipEventDestroy(evMerge1); }
-        if (gathered && m && !m->ctxs.empty()) { (void)hipSetDevice(m->ctxs[0]->device); m->ctxs[0]->free(gathered); }
-        for (size_t i = 0; i < ready.size(); i++) if (ready[i]) { (void)hipSetDevice(m->ctxs[i]->device); (void)hipEventDestroy(ready[i]); }
+        if (gathered) { (void)hipSetDevice(m->ctxs[0]->device); m->ctxs[0]->free(gathered); }
         for (Query* q : qs) destroyQuery(q);
     }
 };
 
-void rsq::copyDeviceAsync(void* dst, int dstDevice, const void* src, int srcDevice, size_t bytes, hipStream_t stream) {
-    if (dstDevice == srcDevice) RSQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
-    else RSQ_HIP(hipMemcpyPeerAsync(dst, dstDevice, src, srcDevice, bytes, stream));
-}
-
 namespace {
-
-// peer copies between distinct GPUs: direct over xGMI where the pair allows it
-void enablePeerAccess(rsq_multi& m) {
-    const size_t n = m.devices.size();
-    for (size_t j = 0; j < n; j++)
-        for (size_t i = 0; i < n; i++) {
-            int can = 0;
-            if (m.devices[i] == m.devices[j] || hipDeviceCanAccessPeer(&can, m.devices[j], m.devices[i]) != hipSuccess || !can) continue;
-            RSQ_HIP(hipSetDevice(m.devices[j]));
-            if (hipDeviceEnablePeerAccess(m.devices[i], 0) != hipSuccess) (void)hipGetLastError();
-        }
-}
 
 template <typename F>
 int guardedM(rsq_multi* m, F&& f) {
@@ -146,59 +128,49 @@ int guardedM(rsq_multi* m, F&& f) {
     catch (const std::exception& e) { if (m) m->lastError = e.what(); else g_multiCreateError = e.what(); return RSQ_ERR_INVALID; }
 }
 
-void enqueueMergeUntimed(rsq_multi_query& mq);
-// the group-by merge of one step, enqueued behind every shard's kernels; returns after enqueueing.  An event pair on the root's
-// stream brackets it: rsq_multi_query_collective_ms (from the root's last kernel to the merged table, i.e. including the wait for
-// the slowest shard)
+// mergeText: how the shards run in front of the merge (a nested-loops split with the last gather's bytes, the derived tables' splits),
+// then the merge of the plan's kind
+void composeMergeText(rsq_multi_query& mq) {
+    const int n = (int)mq.m->ctxs.size();
+    const int64_t bytes = mq.split.gatherBytes;
+    std::string s;
+    if (mq.nlj)
+        s = "nested-loops: outer rows over " + std::to_string(n) + (n == 1 ? " shard" : " shards") + ", inner side " +
+            (!mq.split.gathered ? "replicated" : bytes < 0 ? "gathered (peer copies)" : "gathered (peer copies, " + std::to_string((long long)bytes) + " bytes)") + "; ";
+    if (mq.derived) s += "derived tables: " + mq.derivedText + "; ";
+    mq.mergeText = s + mq.mergeBase;
+}
+
+// the group-by merge of one step, enqueued behind every shard's kernels; returns after enqueueing.  An event pair on the root's stream
+// brackets it: rsq_multi_query_collective_ms (from the root's last kernel to the merged table, i.e. including the wait for the slowest
+// shard).  A single shard without a communicator has no such events and nothing to merge.
 void enqueueMerge(rsq_multi_query& mq) {
     rsq_multi& m = *mq.m;
-    if (m.ctxs.size() == 1 && m.comms.empty()) return;
-    Context& root = *m.ctxs[0];
-    RSQ_HIP(hipSetDevice(root.device));
-    if (!mq.evMerge0) { RSQ_HIP(hipEventCreate(&mq.evMerge0)); RSQ_HIP(hipEventCreate(&mq.evMerge1)); }
-    RSQ_HIP(hipEventRecord(mq.evMerge0, root.stream));
-    enqueueMergeUntimed(mq);
-    RSQ_HIP(hipSetDevice(root.device));
-    RSQ_HIP(hipEventRecord(mq.evMerge1, root.stream));
-}
-void enqueueMergeUntimed(rsq_multi_query& mq) {
-    rsq_multi& m = *mq.m;
     const int n = (int)m.ctxs.size();
-    const int64_t words = mq.nMin + mq.nMax + mq.nSum;
-    if (n == 1 && m.comms.empty()) return;          // (a one-GPU handle made with RSQ_MERGE_RCCL still runs its collective)
-    std::vector<int64_t*> part((size_t)n);
-    for (int i = 0; i < n; i++) { int64_t a, b, c; void* p; queryDenseLayout(*mq.qs[(size_t)i], &a, &b, &c, &p); part[(size_t)i] = (int64_t*)p; }
+    if (!mq.evMerge0.get()) return;
+    mq.evMerge0.record(m.ctxs[0]->stream);
     if (m.merge == RSQ_MERGE_RCCL) {
         // one reduce per non-empty segment to the root (device 0, in place), all of them for all GPUs in ONE group:
         // RCCL launches a single kernel per GPU for the group.  Integer min / max / sum: bit-exact in any order.
         RcclApi& R = rccl();
-        const int64_t off[3] = {0, mq.nMin, mq.nMin + mq.nMax};
-        const int64_t cnt[3] = {mq.nMin, mq.nMax, mq.nSum};
+        int64_t cnt[3];
+        std::vector<void*> part((size_t)n);
+        for (int i = 0; i < n; i++) queryDenseLayout(*mq.qs[(size_t)i], &cnt[0], &cnt[1], &cnt[2], &part[(size_t)i]);      // (one layout: the compile checked it)
+        const int64_t off[3] = {0, cnt[0], cnt[0] + cnt[1]};
         const ncclRedOp_t op[3] = {ncclMin, ncclMax, ncclSum};
         RSQ_NCCL(R.GroupStart());
         for (int i = 0; i < n; i++)
             for (int s = 0; s < 3; s++)
                 if (cnt[s] > 0)
-                    RSQ_NCCL(R.Reduce(part[(size_t)i] + off[s], part[(size_t)i] + off[s], (size_t)cnt[s], ncclInt64, op[s], 0, m.comms[(size_t)i],
-                                      m.ctxs[(size_t)i]->stream));
+                    RSQ_NCCL(R.Reduce((int64_t*)part[(size_t)i] + off[s], (int64_t*)part[(size_t)i] + off[s], (size_t)cnt[s], ncclInt64, op[s], 0,
+                                      m.comms[(size_t)i], m.ctxs[(size_t)i]->stream));
         RSQ_NCCL(R.GroupEnd());
-        return;
+    } else {
+        // peer copies: every shard's table, complete behind an event on its stream, to the root's gather buffer and through the merge kernel
+        for (int i = 1; i < n; i++) mq.ready[(size_t)i].record(m.ctxs[(size_t)i]->stream);
+        mergeDenseOnRoot(mq.qs, mq.ready, mq.gathered, "internal: shards planned from the same statistics disagree on the aggregation strategy");
     }
-    // peer copies: every shard's table -> root's gather buffer (ordered behind the shard's kernels by an event), then the
-    // engine's merge kernel on the root's stream
-    Context& root = *m.ctxs[0];
-    for (int i = 0; i < n; i++) {
-        Context& c = *m.ctxs[(size_t)i];
-        if (i > 0) {
-            RSQ_HIP(hipSetDevice(c.device));
-            RSQ_HIP(hipEventRecord(mq.ready[(size_t)i], c.stream));
-            RSQ_HIP(hipSetDevice(root.device));
-            RSQ_HIP(hipStreamWaitEvent(root.stream, mq.ready[(size_t)i], 0));
-        }
-        RSQ_HIP(hipSetDevice(root.device));
-        copyDeviceAsync(mq.gathered + (size_t)i * (size_t)words, root.device, part[(size_t)i], c.device, (size_t)words * 8, root.stream);
-    }
-    mergePartialsAsync(root, mq.gathered, n, words, mq.nMin, mq.nMax, mq.nSum, part[0]);
+    mq.evMerge1.record(m.ctxs[0]->stream);
 }
 
 // ---- Nested-loops joins across GPUs ---------------------------------------------------------------------------------------------
@@ -213,14 +185,12 @@ void enqueueMergeUntimed(rsq_multi_query& mq) {
 //              in shard order with peer copies.  Everything else (a sharded build side, two sharded inner tables, a sharded table under a
 //              nested inner side) is refused.
 
-// the scan a plan operator's pipeline starts at (codegen.cpp Walker::produce: a hash join's probe side and a nested-loops join's outer
-// side continue the pipeline, every other operator its one child)
+// the child an operator's pipeline continues through (codegen.cpp Walker::produce: a hash join's probe side and a nested-loops join's
+// outer side continue the pipeline, every other operator its one child), and the scan the pipeline starts at
+int pipelineChild(const rsq_op& o) { return o.tag == RSQ_OP_HASHJOIN || o.tag == RSQ_OP_NESTEDLOOPSJOIN ? o.child[1] : o.child[0]; }
 int pipelineScan(const rsq_plan_desc& p, int op) {
-    for (int steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops; steps++) {
-        const rsq_op& o = p.ops[op];
-        if (o.tag == RSQ_OP_SCAN) return op;
-        op = o.tag == RSQ_OP_HASHJOIN || o.tag == RSQ_OP_NESTEDLOOPSJOIN ? o.child[1] : o.child[0];
-    }
+    for (int steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops; steps++, op = pipelineChild(p.ops[op]))
+        if (p.ops[op].tag == RSQ_OP_SCAN) return op;
     failInvalid("malformed plan: an operator chain ends without a scan");
 }
 void subtreeOps(const rsq_plan_desc& p, int op, std::vector<int>& out) {
@@ -255,10 +225,8 @@ int planNestedLoopsSplit(rsq_multi& m, const rsq_plan_desc& p, rsq_table* const*
         }
     // ... on the plan's last pipeline: its outer rows are split, so it must not fill a join table every shard needs whole
     bool onLast = false;
-    for (int op = p.root, steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops && p.ops[op].tag != RSQ_OP_SCAN; steps++) {
+    for (int op = p.root, steps = 0; op >= 0 && op < p.n_ops && steps <= p.n_ops && p.ops[op].tag != RSQ_OP_SCAN; steps++, op = pipelineChild(p.ops[op]))
         if (op == nlj) onLast = true;
-        op = p.ops[op].tag == RSQ_OP_HASHJOIN || p.ops[op].tag == RSQ_OP_NESTEDLOOPSJOIN ? p.ops[op].child[1] : p.ops[op].child[0];
-    }
     if (!onLast) failUnsupported("a nested-loops join that feeds a join's build side is not split across GPUs");
     const int outerScan = pipelineScan(p, p.ops[nlj].child[1]);
     const int innerScan = pipelineScan(p, p.ops[nlj].child[0]);
@@ -283,7 +251,7 @@ int planNestedLoopsSplit(rsq_multi& m, const rsq_plan_desc& p, rsq_table* const*
     if (gathered >= 0) {
         // the parts go together in shard order: that is the inner side's order only if the shards hold increasing row ranges
         const int t = tableOf(gathered);
-        for (int op = p.ops[nlj].child[0]; op != gathered; op = p.ops[op].tag == RSQ_OP_HASHJOIN || p.ops[op].tag == RSQ_OP_NESTEDLOOPSJOIN ? p.ops[op].child[1] : p.ops[op].child[0])
+        for (int op = p.ops[nlj].child[0]; op != gathered; op = pipelineChild(p.ops[op]))
             if (p.ops[op].tag == RSQ_OP_ORDERBY || p.ops[op].tag == RSQ_OP_AGGREGATION)
                 failUnsupported("table " + tab(0, t)->name + " is sharded, and the nested-loops join's inner side over it is sorted or aggregated: replicate it");
         for (int i = 1; i < n; i++)
@@ -313,27 +281,27 @@ std::unique_ptr<Table> sliceOf(const Table& t, int64_t start, int64_t rows) {
 
 // one execution of a nested-loops plan: every shard's inner part (shard threads), the pair budget of the whole statement, the
 // all-gather of the parts (or each shard binds its own, replicated, inner side), then every shard's outer pipelines
-template <typename OnThreads>
-void executeNestedLoops(rsq_multi_query& mq, OnThreads&& onThreads) {
+void executeNestedLoops(rsq_multi_query& mq) {
     rsq_multi& m = *mq.m;
+    NljSplit& sp = mq.split;
     const int n = (int)m.ctxs.size();
     std::vector<NljState*> nl((size_t)n);
     int64_t outer = 0;
     for (int i = 0; i < n; i++) { nl[(size_t)i] = &topNestedLoops(*mq.qs[(size_t)i]); outer += nl[(size_t)i]->outerSrc->nRows; }
     // (a shard whose outer slice is empty still makes its inner part for the others)
     std::vector<int64_t> rows((size_t)n, 0);
-    onThreads([&](int i) {
+    onShardThreads(n, [&](int i) {
         RSQ_HIP(hipSetDevice(m.ctxs[(size_t)i]->device));
         runNestedLoopsInner(*nl[(size_t)i], outer > 0);
         rows[(size_t)i] = nl[(size_t)i]->nInner;
-        RSQ_HIP(hipEventRecord(mq.innerDone[(size_t)i], m.ctxs[(size_t)i]->stream));
+        sp.innerDone[(size_t)i].record(m.ctxs[(size_t)i]->stream);
     });
     int64_t inner = 0;
     for (int i = 0; i < n; i++) {
-        if (!mq.nljGathered && rows[(size_t)i] != rows[0])
+        if (!sp.gathered && rows[(size_t)i] != rows[0])
             throw Error(RSQ_ERR_RUNTIME, "internal: replicated inner sides of a nested-loops join differ between shards (" + std::to_string((long long)rows[0]) +
                                          " and " + std::to_string((long long)rows[(size_t)i]) + " rows)");
-        inner = mq.nljGathered ? inner + rows[(size_t)i] : rows[0];
+        inner = sp.gathered ? inner + rows[(size_t)i] : rows[0];
     }
     try {
         for (int i = 0; i < n; i++) { RSQ_HIP(hipSetDevice(m.ctxs[(size_t)i]->device)); bindNestedLoops(*mq.qs[(size_t)i], *nl[(size_t)i], outer, inner); }
@@ -343,42 +311,32 @@ void executeNestedLoops(rsq_multi_query& mq, OnThreads&& onThreads) {
         for (int i = 0; i < n; i++) { mq.report.num_kernels += (int32_t)nl[(size_t)i]->sub.kernels; mq.report.bytes_read += nl[(size_t)i]->sub.bytes; }
         throw;
     }
-    // the bound columns of shard j: the parts of all shards back to back (gathered), or its own inner side
-    mq.gatherBytes = 0;
+    // the bound columns of shard j, column by column: the parts of all shards back to back (gathered, each shard's part behind its
+    // innerDone, waited for in front of the first column), or its own inner side
+    sp.gatherBytes = 0;
     for (int j = 0; j < n; j++) {
         Context& dst = *m.ctxs[(size_t)j];
         const NljState& to = *nl[(size_t)j];
-        RSQ_HIP(hipSetDevice(dst.device));
-        if (mq.nljGathered) RSQ_HIP(hipEventRecord(mq.gather0[(size_t)j], dst.stream));
-        int64_t at = 0;
-        for (int i = 0; i < n; i++) {
-            if (!mq.nljGathered && i != j) continue;
-            const Context& src = *m.ctxs[(size_t)i];
-            const NljState& from = *nl[(size_t)i];
-            if (i != j && rows[(size_t)i] > 0) RSQ_HIP(hipStreamWaitEvent(dst.stream, mq.innerDone[(size_t)i], 0));
-            for (size_t k = 0; k < to.innerSchema.size() && rows[(size_t)i] > 0; k++) {
-                const size_t w = (size_t)columnWidth(to.innerSchema[k].type);
-                const size_t b = (size_t)rows[(size_t)i] * w;
-                copyDeviceAsync((char*)to.sub.dCols[k] + (size_t)at * w, dst.device, from.sub.query->dMatCols[(size_t)from.innerCol[k]], src.device, b, dst.stream);
-                if (i != j) mq.gatherBytes += (int64_t)b;
-            }
-            at += rows[(size_t)i];
+        if (sp.gathered) sp.gather0[(size_t)j].record(dst.stream);
+        for (size_t k = 0; k < to.innerSchema.size(); k++) {
+            const size_t w = (size_t)columnWidth(to.innerSchema[k].type);
+            std::vector<GatherPart> parts;
+            for (int i = 0; i < n; i++)
+                if ((sp.gathered || i == j) && rows[(size_t)i] > 0)
+                    parts.push_back({m.ctxs[(size_t)i], nl[(size_t)i]->sub.query->dMatCols[(size_t)nl[(size_t)i]->innerCol[k]], (size_t)rows[(size_t)i] * w,
+                                     k == 0 && i != j ? sp.innerDone[(size_t)i].get() : nullptr});
+            if (!parts.empty()) sp.gatherBytes += gatherParts(dst, to.sub.dCols[k], parts);
         }
-        if (mq.nljGathered) RSQ_HIP(hipEventRecord(mq.gather1[(size_t)j], dst.stream));
+        if (sp.gathered) sp.gather1[(size_t)j].record(dst.stream);
     }
-    if (mq.nljGathered) mq.mergeText = "nested-loops: outer rows over " + std::to_string(n) + " shards, inner side gathered (peer copies, " +
-                                       std::to_string((long long)mq.gatherBytes) + " bytes); " + mq.mergeBase;
-    onThreads([&](int i) { executeQuery(*mq.qs[(size_t)i], mq.dense); });
+    if (sp.gathered) composeMergeText(mq);
+    onShardThreads(n, [&](int i) { executeQuery(*mq.qs[(size_t)i], mq.dense); });
 }
 
 // device time of the last gather: the slowest shard's copies (0 without a gather)
-double gatherMs(rsq_multi_query& mq) {
+double gatherMs(const rsq_multi_query& mq) {
     double ms = 0;
-    for (size_t i = 0; mq.nljGathered && i < mq.gather0.size(); i++) {
-        float e = 0;
-        RSQ_HIP(hipSetDevice(mq.m->ctxs[i]->device));
-        if (hipEventSynchronize(mq.gather1[i]) == hipSuccess && hipEventElapsedTime(&e, mq.gather0[i], mq.gather1[i]) == hipSuccess) ms = std::max(ms, (double)e);
-    }
+    for (size_t i = 0; mq.split.gathered && i < mq.split.gather0.size(); i++) ms = std::max(ms, mq.split.gather1[i].msSince(mq.split.gather0[i]));
     return ms;
 }
 
@@ -415,12 +373,7 @@ int rsq_multi_create(const rsq_multi_config* hostCfg, rsq_multi** out) {
             c.device = cfg->devices[i];
             m->ctxs.push_back(new Context(c));
         }
-        if (m->merge == RSQ_MERGE_PEER_COPY && !m->sharedDevice)
-            for (int i = 1; i < cfg->n_devices; i++) {
-                int can = 0;
-                RSQ_HIP(hipDeviceCanAccessPeer(&can, m->devices[0], m->devices[(size_t)i]));
-                if (can) { RSQ_HIP(hipSetDevice(m->devices[0])); hipError_t e = hipDeviceEnablePeerAccess(m->devices[(size_t)i], 0); if (e != hipSuccess) (void)hipGetLastError(); }
-            }
+        if (m->merge == RSQ_MERGE_PEER_COPY && !m->sharedDevice) enablePeerAccess(m->devices, true);      // (the root gathers the partial tables)
         if (m->merge == RSQ_MERGE_RCCL && (cfg->n_devices > 1 || cfg->merge == RSQ_MERGE_RCCL)) {
             m->comms.assign((size_t)cfg->n_devices, nullptr);
             RSQ_NCCL(rccl().CommInitAll(m->comms.data(), cfg->n_devices, m->devices.data()));
@@ -597,16 +550,15 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             rsq_plan_desc p = *plan;
             if (sliced) { ops[(size_t)outerScan].table = n_tables; p.ops = ops.data(); }
             const int nt = n_tables + (sliced ? 1 : 0);
-            mq->innerDone.assign((size_t)n, nullptr); mq->gather0.assign((size_t)n, nullptr); mq->gather1.assign((size_t)n, nullptr);
             for (int i = 0; i < n; i++) {
                 std::vector<rsq_table*> ts(tables + (size_t)i * (size_t)n_tables, tables + (size_t)(i + 1) * (size_t)n_tables);
                 const Table* outer = reinterpret_cast<const Table*>(ts[(size_t)outerTable]);
                 if (sliced) {
                     int64_t r0, nr;
                     rsq_multi_shard_rows(outer->nRows, n, i, &r0, &nr);
-                    mq->outerSlices.push_back(sliceOf(*outer, r0, nr));
-                    outer = mq->outerSlices.back().get();
-                    ts.push_back(reinterpret_cast<rsq_table*>(mq->outerSlices.back().get()));
+                    mq->split.outerSlices.push_back(sliceOf(*outer, r0, nr));
+                    outer = mq->split.outerSlices.back().get();
+                    ts.push_back(reinterpret_cast<rsq_table*>(mq->split.outerSlices.back().get()));
                 }
                 Query* q = compileQuery(*m->ctxs[(size_t)i], p, ts.data(), nt);
                 mq->qs.push_back(q);
@@ -616,20 +568,18 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 // (executeQuery runs the outer side only; the gathered table is seen whole by every shard: it never proves shards disjoint in a group key)
                 top.sub.external = true;
                 if (gatheredTable >= 0) q->gatheredTables.push_back(reinterpret_cast<const Table*>(ts[(size_t)gatheredTable]));
-                RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device));
-                RSQ_HIP(hipEventCreateWithFlags(&mq->innerDone[(size_t)i], hipEventDisableTiming));
-                RSQ_HIP(hipEventCreate(&mq->gather0[(size_t)i])); RSQ_HIP(hipEventCreate(&mq->gather1[(size_t)i]));
+                const Context& c = *m->ctxs[(size_t)i];
+                mq->split.innerDone.emplace_back(c, false); mq->split.gather0.emplace_back(c, true); mq->split.gather1.emplace_back(c, true);
             }
-            mq->nljGathered = gatheredTable >= 0;
-            if (mq->nljGathered) enablePeerAccess(*m);
+            mq->split.gathered = gatheredTable >= 0;
+            if (mq->split.gathered) enablePeerAccess(m->devices, false);
         }
         // derived aggregations: across the shards with RSQ_ENGINE_DERIVED_MULTI (never inside a nested-loops plan), else on one context only
-        std::string derivedText;
         if (!mq->qs.empty() && queryHasDerived(*mq->qs[0])) {
             if (!(m->ctxs[0]->cfg.engine_flags & RSQ_ENGINE_DERIVED_MULTI) || mq->nlj) refuseDerived(*mq->qs[0], "a multi-GPU compile (rsq_multi_query_compile)");
             mq->derived = true;
-            derivedText = planDerivedAcrossShards(mq->qs, tables, n_tables, sharded);
-            enablePeerAccess(*m);
+            mq->derivedText = planDerivedAcrossShards(mq->qs, tables, n_tables, sharded);
+            enablePeerAccess(m->devices, false);
         }
         mq->dense = queryIsDense(*mq->qs[0]);
         if (mq->dense) {
@@ -639,18 +589,19 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
                 if (!queryIsDense(*mq->qs[(size_t)i]) || queryPartialLayoutText(*mq->qs[(size_t)i]) != l0)
                     throw Error(RSQ_ERR_RUNTIME, "internal: shards planned from the same statistics disagree on the partial aggregate table layout: shard 0 has \"" + l0 +
                                                  "\", shard " + std::to_string(i) + " has \"" + queryPartialLayoutText(*mq->qs[(size_t)i]) + "\"");
-            void* p;
-            queryDenseLayout(*mq->qs[0], &mq->nMin, &mq->nMax, &mq->nSum, &p);
+            Context& root = *m->ctxs[0];
             if (n > 1 && m->merge == RSQ_MERGE_PEER_COPY) {
-                Context& root = *m->ctxs[0];
-                mq->gathered = (int64_t*)root.alloc((size_t)n * (size_t)(mq->nMin + mq->nMax + mq->nSum) * 8);
-                mq->ready.assign((size_t)n, nullptr);
-                for (int i = 1; i < n; i++) { RSQ_HIP(hipSetDevice(m->ctxs[(size_t)i]->device)); RSQ_HIP(hipEventCreateWithFlags(&mq->ready[(size_t)i], hipEventDisableTiming)); }
+                int64_t nMin, nMax, nSum; void* p;
+                queryDenseLayout(*mq->qs[0], &nMin, &nMax, &nSum, &p);
+                mq->gathered = (int64_t*)root.alloc((size_t)n * (size_t)(nMin + nMax + nSum) * 8);
+                mq->ready.emplace_back();
+                for (int i = 1; i < n; i++) mq->ready.emplace_back(*m->ctxs[(size_t)i], false);
             }
+            if (n > 1 || !m->comms.empty()) { mq->evMerge0 = ShardEvent(root, true); mq->evMerge1 = ShardEvent(root, true); }      // (enqueueMerge)
             // (a nested-loops plan runs on host threads: the host stands between its inner and its outer sides)
             mq->async = !mq->nlj && !mq->derived;
             for (Query* q : mq->qs) mq->async = mq->async && queryAsyncCapable(*q);
-            mq->mergeText = std::string("dense partial tables: ") + rsq_multi_merge_name(m) +
+            mq->mergeBase = std::string("dense partial tables: ") + rsq_multi_merge_name(m) +
                             (mq->async ? "" : mq->nlj ? " (nested-loops join: the shards run on host threads)" : mq->derived ? " (derived tables: the shards run on host threads)"
                                                                                                                   : " (join builds: the shards run on host threads)");
         } else {
@@ -664,21 +615,13 @@ int rsq_multi_query_compile(rsq_multi* m, const rsq_plan_desc* plan, rsq_table* 
             const bool disjoint = n > 1 && shardGroupsDisjoint(mq->qs, why);
             const bool forceGeneral = sw::flag<sw::RSQ_MULTI_GENERAL_MERGE>();
             mq->orderedFast = disjoint && queryOrderedWithLimit(*mq->qs[0]) && !forceGeneral;
-            if (n == 1) mq->mergeText = "single shard";
-            else if (mq->orderedFast) mq->mergeText = "ordered merge of the shards' LIMIT-ed rows (" + why + ")";
-            else mq->mergeText = "general merge: all shards' group rows re-aggregated by key on the host, then one tail (" +
+            if (n == 1) mq->mergeBase = "single shard";
+            else if (mq->orderedFast) mq->mergeBase = "ordered merge of the shards' LIMIT-ed rows (" + why + ")";
+            else mq->mergeBase = "general merge: all shards' group rows re-aggregated by key on the host, then one tail (" +
                                  (forceGeneral ? std::string("forced") : disjoint ? std::string("no ORDER BY ... LIMIT to shorten") : why) + ")";
             if (n > 1 && !mq->orderedFast) for (Query* q : mq->qs) setHoldTail(*q, true);
         }
-        if (mq->nlj) {
-            mq->mergeBase = mq->mergeText;
-            mq->mergeText = "nested-loops: outer rows over " + std::to_string(n) + (n == 1 ? " shard" : " shards") + ", inner side " +
-                            (mq->nljGathered ? "gathered (peer copies)" : "replicated") + "; " + mq->mergeBase;
-        }
-        if (mq->derived) {
-            mq->mergeBase = mq->mergeText;
-            mq->mergeText = "derived tables: " + derivedText + "; " + mq->mergeBase;
-        }
+        composeMergeText(*mq);
         mq->shardKernelMs.assign((size_t)n, 0.0);
         *out = mq.release();
     });
@@ -689,64 +632,36 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
     rsq_multi* m = mq->m;
     return guardedM(m, [&] {
         const int n = (int)m->ctxs.size();
-        const double t0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        // every shard's execution on its own host thread (plans whose pipelines need the host between kernels: join builds size
-        // their tables, hash aggregations grow theirs)
-        auto onThreadsDo = [&](auto&& step) {
-            std::vector<std::string> errs((size_t)n);
-            std::vector<int> status((size_t)n, RSQ_OK);
-            std::vector<std::thread> th;
-            for (int i = 0; i < n; i++)
-                th.emplace_back([&, i] {
-                    try { step(i); }
-                    catch (const Error& e) { status[(size_t)i] = e.status; errs[(size_t)i] = e.what(); }
-                    catch (const std::exception& e) { status[(size_t)i] = RSQ_ERR_RUNTIME; errs[(size_t)i] = e.what(); }
-                });
-            for (auto& t : th) t.join();
-            for (int i = 0; i < n; i++) if (status[(size_t)i] != RSQ_OK) throw Error(status[(size_t)i], "shard " + std::to_string(i) + ": " + errs[(size_t)i]);
-        };
-        auto onThreads = [&](bool partialOnly) { onThreadsDo([&](int i) { executeQuery(*mq->qs[(size_t)i], partialOnly); }); };
+        const double t0 = nowMs();
+        // 1. the shards, up to their partial tables (dense) or their own results
         mq->derivedMs = 0;
         if (mq->derived) {
             // the derived tables on every shard, innermost first (their sub-queries, exchanges and writers), then the parent as below
-            const ShardThreads threads = [&](const std::function<void(int)>& f) { onThreadsDo(f); };
             DerivedMultiRun run;
-            runDerivedAcrossShards(mq->qs, threads, run);
+            runDerivedAcrossShards(mq->qs, run);
             mq->derivedMs = run.exchangeMs;
-            mq->mergeText = "derived tables: " + run.text + "; " + mq->mergeBase;
+            mq->derivedText = run.text;
+            composeMergeText(*mq);
         }
-        if (mq->nlj) {
-            // inner parts, the budget, the gather, the outer sides - then the merge of the plan's kind
-            executeNestedLoops(*mq, onThreadsDo);
-            if (mq->dense) {
-                enqueueMerge(*mq);
-                finalizeQuery(*mq->qs[0]);
-            } else {
-                double t1 = now();
-                if (n > 1) { if (mq->orderedFast) mergeShardResults(*mq->qs[0], mq->qs); else runTailMerged(*mq->qs[0], mq->qs); }
-                mq->report.finalize_time_ms = now() - t1;
-            }
-        } else if (mq->dense && mq->async) {
-            // fan out: enqueue every shard's pipelines (no host synchronisation), then the merge behind them, then ONE
-            // synchronising read-back on the root
+        if (mq->nlj) executeNestedLoops(*mq);      // inner parts, the budget, the gather, the outer sides
+        else if (mq->dense && mq->async)
+            // fan out: enqueue every shard's pipelines (no host synchronisation); the merge goes behind them, then ONE synchronising
+            // read-back on the root
             for (int i = 0; i < n; i++) executeQuery(*mq->qs[(size_t)i], true, true);
+        else
+            // on host threads: join builds in front of a dense aggregation (TPC-H Q14-like) need the host's help, as does any other plan
+            onShardThreads(n, [&](int i) { executeQuery(*mq->qs[(size_t)i], mq->dense); });
+        // 2. the merge of the plan's kind
+        if (mq->dense) {
             enqueueMerge(*mq);
             finalizeQuery(*mq->qs[0]);
-            for (int i = 1; i < n; i++) settleAsync(*mq->qs[(size_t)i]);
-        } else if (mq->dense) {
-            // join builds in front of the dense aggregation (TPC-H Q14-like): the shards run to their partial tables with the
-            // host's help, the merge and the root's finalisation follow
-            onThreads(true);
-            enqueueMerge(*mq);
-            finalizeQuery(*mq->qs[0]);
+            if (mq->async) for (int i = 1; i < n; i++) settleAsync(*mq->qs[(size_t)i]);
         } else {
-            onThreads(false);
-            double t1 = now();
+            const double t1 = nowMs();
             if (n > 1) { if (mq->orderedFast) mergeShardResults(*mq->qs[0], mq->qs); else runTailMerged(*mq->qs[0], mq->qs); }
-            mq->report.finalize_time_ms = now() - t1;
+            mq->report.finalize_time_ms = nowMs() - t1;
         }
-        // report: the slowest shard's kernel time (the shards run concurrently), bytes of all shards
+        // 3. the report: the slowest shard's kernel time (the shards run concurrently), bytes of all shards
         rsq_report r0; queryReport(*mq->qs[0], &r0);
         rsq_report rep = r0;
         rep.bytes_read = 0; rep.num_kernels = 0; rep.kernel_time_ms = 0;
@@ -758,15 +673,8 @@ int rsq_multi_query_execute(rsq_multi_query* mq) {
             mq->shardKernelMs[(size_t)i] = r.kernel_time_ms;
         }
         if (!mq->dense && n > 1) rep.finalize_time_ms = r0.finalize_time_ms + mq->report.finalize_time_ms;
-        mq->collectiveMs = 0;
-        if (mq->dense && mq->evMerge0) {
-            float ms = 0;
-            RSQ_HIP(hipSetDevice(m->ctxs[0]->device));
-            if (hipEventSynchronize(mq->evMerge1) == hipSuccess && hipEventElapsedTime(&ms, mq->evMerge0, mq->evMerge1) == hipSuccess) mq->collectiveMs = ms;
-        }
-        if (mq->nlj) mq->collectiveMs += gatherMs(*mq);
-        mq->collectiveMs += mq->derivedMs;
-        rep.execution_time_ms = now() - t0;
+        mq->collectiveMs = (mq->dense ? mq->evMerge1.msSince(mq->evMerge0) : 0) + (mq->nlj ? gatherMs(*mq) : 0) + mq->derivedMs;
+        rep.execution_time_ms = nowMs() - t0;
         rep.hbm_gbps = rep.kernel_time_ms > 0 ? (double)rep.bytes_read / (rep.kernel_time_ms * 1e-3) / 1e9 : 0;
         mq->report = rep;
     });

@@ -8,13 +8,13 @@ import json
 import os
 import sys
 
-import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import derivedcases as D  # noqa: E402
+import shardlayouts  # noqa: E402
 from resql_amd import dist, engine, tpch_full  # noqa: E402
 from resql_amd import plan as P  # noqa: E402
 
@@ -106,8 +106,7 @@ def _classify(plan, sharded):
 
 
 # ---- tables ---------------------------------------------------------------------------------------------------------------------
-def _slice(t: P.Table, lo: int, hi: int) -> P.Table:
-    return P.Table(t.name, [P.Column(c.name, c.type, None if c.data is None else np.ascontiguousarray(c.data[lo:hi])) for c in t.columns], hi - lo)
+_slice = shardlayouts.slice_rows
 
 
 def _cuts(t: P.Table, kind, n):
@@ -123,29 +122,8 @@ def _cuts(t: P.Table, kind, n):
     raise ValueError(kind)
 
 
-class Shards:
-    def __init__(self, m, tables):
-        self.m, self.tables, self.made = m, {t.name: t for t in tables}, {}
-
-    def get(self, i, name, cut):
-        key = (i, name, cut)
-        if key not in self.made:
-            t = self.tables[name]
-            if cut is None:
-                self.made[key] = self.m.shards[i].table(t)
-            else:
-                c = _cuts(t, cut, self.m.n)
-                d = self.m.shards[i].table(_slice(t, c[i], c[i + 1]))
-                d.set_row0(c[i])
-                self.made[key] = d
-        return self.made[key]
-
-    def layout(self, names, cut_of):
-        return [[self.get(i, k, cut_of.get(k)) for k in names] for i in range(self.m.n)]
-
-    def close(self):
-        for t in self.made.values():
-            t.close()
+def Shards(m, tables):
+    return shardlayouts.Shards(m, {t.name: t for t in tables}, _cuts)
 
 
 LAYOUTS = {"replicated": {}, "lineitem": {"lineitem": "spread"}, "lineitem_late": {"lineitem": "late"},
@@ -386,3 +364,52 @@ def test_refusals_that_stay(db, single):
         for t in t2:
             t.close()
         c2.close()
+
+
+# ---- a merged derived table without a single group -------------------------------------------------------------------------------------
+def _no_group(db, key):
+    """groups of the suppliers no supplier is among, counted by size"""
+    p = D._plan(db)
+    c = p.count(p.star())
+    none = p.selection(p.gt(p.attr("s_acctbal"), p.constant("99999999.00", P.DECIMAL)), p.scan("supplier"))
+    a = p.aggregation([c], [p.attr(key)], none)
+    return p.set_root(p.materialize(p.aggregation([p.count(p.star())], [c], a)), request_all=True)
+
+
+@pytest.mark.parametrize("form,key", [("dense", "s_nationkey"), ("hash", "s_name")])
+def test_merged_table_without_a_group(single, multi, db, form, key):
+    ctx, tabs = single
+    m, shards = multi
+    plan = _no_group(db, key)
+    assert _classify(plan, {"supplier"})[:2] == (None, True)
+    want = _run(ctx.compile(plan, tabs))[0]
+    mq = m.compile(plan, shards.layout(list(D.TABLES), {"supplier": "spread"}))
+    try:
+        outs, kernels = [], []
+        for _ in range(2):
+            mq.execute()
+            outs.append(mq.result())
+            kernels.append(mq.report()[0].num_kernels)
+        merge = mq.merge_name
+    finally:
+        mq.close()
+    assert all(o.tuples == want.tuples and o.text == want.text for o in outs) and want.n_rows == 0
+    assert kernels[0] == kernels[1] > 0
+    assert "derived0 merged on the " in merge and f"over {N} shards (" in merge, merge
+    assert ("dense partial tables" in merge) == (form == "dense"), merge
+
+
+def test_one_shard_with_the_peer_copy_merge(single, db):
+    """a handle of one shard asked for peer copies: every derived table is built locally, the one context's bytes"""
+    ctx, tabs = single
+    plan = D.having_dense_key(db)
+    want = _run(ctx.compile(plan, tabs))[0]
+    m = engine.MultiContext([0], merge=engine.MERGE_PEER_COPY, engine_flags=FLAG)
+    shards = Shards(m, [db[k] for k in D.TABLES])
+    try:
+        got, merge, _ = _run(m.compile(plan, shards.layout(list(D.TABLES), {})), times=2)
+        assert got.tuples == want.tuples and got.text == want.text and got.n_rows > 0
+        assert "derived0 local" in merge and "bytes" not in merge, merge
+    finally:
+        shards.close()
+        m.close()

@@ -15,6 +15,7 @@ from resql_amd import plan as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import shardlayouts  # noqa: E402
 from test_gpu_nested_loops import JIT_CAST, NO_ROW_IN_REFERENCE, _source_answer  # noqa: E402
 
 with open(os.path.join(HERE, "golden", "nlj_reference.json")) as f:
@@ -57,8 +58,7 @@ def _roles(plan):
 
 
 # ---- tables ---------------------------------------------------------------------------------------------------------------------
-def _slice(t: P.Table, lo: int, hi: int) -> P.Table:
-    return P.Table(t.name, [P.Column(c.name, c.type, None if c.data is None else np.ascontiguousarray(c.data[lo:hi])) for c in t.columns], hi - lo)
+_slice = shardlayouts.slice_rows
 
 
 def _cuts(n, kind):
@@ -66,31 +66,9 @@ def _cuts(n, kind):
     return {"spread": [0, n // 5, 3 * n // 5, n], "late": [0, 0, n // 2, n]}[kind]
 
 
-class Shards:
-    """per shard context: the whole table (replicated) or a row slice with its first row set, made on first use"""
-
-    def __init__(self, m, db):
-        self.m, self.db, self.made = m, db, {}
-
-    def get(self, i, name, cut=None):
-        key = (i, name, cut)
-        if key not in self.made:
-            t = self.db[name]
-            if cut is None:
-                self.made[key] = self.m.shards[i].table(t)
-            else:
-                c = _cuts(t.n_rows, cut)
-                d = self.m.shards[i].table(_slice(t, c[i], c[i + 1]))
-                d.set_row0(c[i])
-                self.made[key] = d
-        return self.made[key]
-
-    def layout(self, names, cut_of):
-        return [[self.get(i, k, cut_of.get(k)) for k in names] for i in range(self.m.n)]
-
-    def close(self):
-        for t in self.made.values():
-            t.close()
+def Shards(m, db):
+    """the database's tables over m's three shards, under the cuts above"""
+    return shardlayouts.Shards(m, db, lambda t, kind, n: _cuts(t.n_rows, kind))
 
 
 @pytest.fixture(scope="module")
@@ -443,6 +421,66 @@ def test_gathered_inner_side_over_distinct_devices(single, db):
             per.append(row)
         got, merge, _ = _run_multi(m, plan, per)
         assert "inner side gathered" in merge and got.tuples == want.tuples
+    finally:
+        shards.close()
+        m.close()
+
+
+# ---- the gather moves exactly the inner side's bound columns, once to every other shard ----------------------------------------------
+def _attributes(plan, e, out):
+    if plan.exprs[e].tag == "ATTRIBUTE":
+        out.add(plan.exprs[e].symbol)
+    for c in plan.exprs[e].children:
+        _attributes(plan, c, out)
+    return out
+
+
+def _bound_width(plan, inner_table):
+    """bytes of one inner row in the pair loop: the inner table's columns that the join or an operator above it names
+    (codegen.cpp consumeNestedLoops; what only the inner side's own operators read stays there)"""
+    top = [o for o in plan.ops if o.tag == "NESTEDLOOPSJOIN"]
+    assert len(top) == 1 and not plan.request_all
+    inner_ops = set(_subtree(plan, top[0].children[0], []))
+    named = set()
+    for i, o in enumerate(plan.ops):
+        if i not in inner_ops:
+            for e in o.exprs + o.exprs2:
+                _attributes(plan, e, named)
+    return sum(c.type.width for c in inner_table.columns if c.name in named)
+
+
+@pytest.mark.parametrize("cut,below", [("spread", 40), ("late", 40), ("spread", 0)])
+def test_gathered_bytes_are_the_inner_rows_times_the_bound_widths(single, multi, db, cut, below):
+    """every shard takes the other two shards' parts: 2 x (inner rows over all shards) x (widths of the bound columns); below = 0: no inner
+    row passes, nothing moves"""
+    ctx, tabs = single
+    m, shards = multi
+    names = GOLD["tables"]
+    sql = f"select s_name, r_name, s_acctbal from supplier, region where s_suppkey < {below} and r_regionkey >= 0"
+    plan = ctx.sql_plan(sql, tabs, [db[k] for k in names])
+    assert _roles(plan)[:2] == ("region", "supplier")
+    inner_rows = int((np.asarray(db["supplier"].col("s_suppkey").data) < below).sum())
+    width = _bound_width(plan, db["supplier"])
+    assert width == 25 + 8 and inner_rows == (39 if below else 0)          # s_name CHAR(25), s_acctbal DECIMAL; s_suppkey stays below
+    want = _run_single(ctx, tabs, plan)
+    got, merge, _ = _run_multi(m, plan, shards.layout(names, {"supplier": cut}), times=2)
+    assert f"inner side gathered (peer copies, {2 * inner_rows * width} bytes)" in merge, merge
+    assert got.tuples == want.tuples and got.text == want.text and got.n_rows == 5 * inner_rows
+
+
+def test_one_shard_with_the_peer_copy_merge(single, db):
+    """a handle of one shard asked for peer copies: nothing to gather, the one context's bytes"""
+    ctx, tabs = single
+    names = GOLD["tables"]
+    plan = ctx.sql_plan("select r_name, count(*) from supplier, region where s_nationkey < r_regionkey * 5 group by r_name", tabs,
+                        [db[k] for k in names])
+    want = _run_single(ctx, tabs, plan)
+    m = engine.MultiContext([0], merge=engine.MERGE_PEER_COPY, engine_flags=FLAG)
+    shards = Shards(m, db)
+    try:
+        got, merge, _ = _run_multi(m, plan, shards.layout(names, {}), times=2)
+        assert got.tuples == want.tuples and got.text == want.text and got.n_rows > 0
+        assert "outer rows over 1 shard, inner side replicated" in merge and "bytes" not in merge, merge
     finally:
         shards.close()
         m.close()
