@@ -75,7 +75,8 @@ typedef struct rsq_config {
     int64_t  nested_loops_max_pairs;/* RSQ_ENGINE_NESTED_LOOPS: most (outer rows x inner rows) one nested-loops join may pair; an execution
                                   * beyond it is RSQ_ERR_UNSUPPORTED before any pair is formed (0: 2^36; < 0: RSQ_ERR_INVALID) */
     int32_t nested_loops_inner_slices;   /* 0: chosen per execution; 1: never split; 2..4096: that many (at most the grid cap); else RSQ_ERR_INVALID */
-    int32_t reserved1;
+    int32_t tbl_ingest;          /* where BULK INSERT parses its '.tbl' text: 0 host threads, 1 the device (rsq_table_load_tbl_ex below);
+                                  * else RSQ_ERR_INVALID */
 } rsq_config;
 
 /* A ReSQL host compiles a statement, executes it ONCE and deletes the plan (reference src/execute.h:213-247).  Two things make that one
@@ -195,9 +196,42 @@ int  rsq_table_from_rowstore(rsq_ctx* ctx, const rsq_table_desc* schema /* data 
  * executeBulkInsert / parseConstant (reference src/execute.h:332-388, src/expressions.h:369-515): see
  * resql_amd/csrc/tbl.cpp for the rules that matter (DECIMAL = digits with the point removed, BIGINT through int32,
  * dates as yyyy-mm-dd or yyyy/mm/dd).  `schema` gives names and types (data pointers ignored).
- * n_threads <= 0: all host threads.  Malformed lines give RSQ_ERR_INVALID with the line number. */
+ * n_threads <= 0: all host threads.  Malformed lines give RSQ_ERR_INVALID with the line number.
+ * The text is parsed where the context's rsq_config.tbl_ingest says: the call is rsq_table_load_tbl_ex with NULL options. */
 int  rsq_table_load_tbl(rsq_ctx* ctx, const rsq_table_desc* schema, const char* path, char field_terminator,
                         int32_t n_threads, rsq_table** out);
+/* The same load with the parse on the DEVICE (opt-in: rsq_config.tbl_ingest = 1, or mode 2 here).  The file is streamed into device
+ * memory in chunk_bytes pieces through two pinned buffers; kernels find the lines and parse every line whose fields all have a PLAIN
+ * form (resql_amd/csrc/tbl_fields.h: -?digits for INT / BIGINT, digits with at most one '.' for DECIMAL, dddd-dd-dd or dddd/dd/dd,
+ * true / false, any text without NUL); every other line - leading blanks, signs, trailing garbage, a wrong field count - is parsed by
+ * the host path's own line function and patched into the columns, so columns, statistics, error texts and line numbers are those of
+ * the host path byte for byte.  The load takes the host path for the whole file - reported, never an error - where the context has
+ * no device, the table has more than 64 columns, the terminator is '\n' or NUL, text + line offsets + columns exceed
+ * max_device_text_bytes, or more than 65536 lines are not plain.
+ * Options and report carry struct_size like rsq_config: the library reads / writes no more than that many bytes. */
+typedef struct rsq_tbl_load_options {
+    uint32_t struct_size;            /* sizeof(rsq_tbl_load_options) */
+    int32_t  mode;                   /* 0: the context's tbl_ingest; 1: host; 2: device; else RSQ_ERR_INVALID */
+    int64_t  chunk_bytes;            /* bytes per piece of the file on its way to the device (0: 64 MiB; 1..63 and < 0: RSQ_ERR_INVALID) */
+    int64_t  max_device_text_bytes;  /* device memory the load may take while it runs (0: what is free minus 1 GiB; < 0: RSQ_ERR_INVALID) */
+} rsq_tbl_load_options;
+enum rsq_tbl_fallback { RSQ_TBL_FALLBACK_NONE = 0, RSQ_TBL_FALLBACK_NO_DEVICE = 1, RSQ_TBL_FALLBACK_COLUMNS = 2, RSQ_TBL_FALLBACK_TERMINATOR = 3,
+                        RSQ_TBL_FALLBACK_DOES_NOT_FIT = 4, RSQ_TBL_FALLBACK_ODD_LINES = 5 };
+typedef struct rsq_tbl_load_report {
+    uint32_t struct_size;            /* sizeof(rsq_tbl_load_report) */
+    int32_t  path;                   /* 0: parsed by host threads; 1: parsed on the device */
+    int32_t  fallback_reason;        /* rsq_tbl_fallback: why a load that asked for the device took the host path (0: it did not) */
+    int32_t  reserved;
+    int64_t  rows, text_bytes;
+    int64_t  lines_patched;          /* lines the host's line function parsed for the device path */
+    /* host wall time in ms.  Device path: read = file reads into the pinned buffers, copy = waiting for the copies behind them,
+     * kernel = HIP events around the three kernels, patch = the odd lines.  Host path: read = file read + parse, copy = upload. */
+    double   read_ms, copy_ms, kernel_ms, patch_ms, stats_ms, total_ms;
+    double   count_kernel_ms, starts_kernel_ms, parse_kernel_ms;     /* kernel_ms by kernel (HIP events), for measurements */
+} rsq_tbl_load_report;
+int  rsq_table_load_tbl_ex(rsq_ctx* ctx, const rsq_table_desc* schema, const char* path, char field_terminator, int32_t n_threads,
+                           const rsq_tbl_load_options* options /* NULL: the defaults */, rsq_tbl_load_report* report /* may be NULL */,
+                           rsq_table** out);
 /* Fill a lineitem / orders / customer / synthetic table on the device with the deterministic
  * generator of resql_amd/datagen.py (same bits), rows [row0, row0 + n_rows).  kind: 0 lineitem,
  * 1 orders, 2 customer, 3 synthetic 4 x int64 (param = number of groups). */
@@ -445,6 +479,7 @@ int  rsq_db_execute(rsq_db* db, const char* sql, int32_t* kind, rsq_result_view*
 const char* rsq_db_message(const rsq_db* db);
 int  rsq_db_adopt_table(rsq_db* db, rsq_table* table);
 int  rsq_db_report(const rsq_db* db, rsq_report* out);          /* of the last SELECT */
+int  rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out);      /* of the last BULK INSERT (out->struct_size set by the caller) */
 void rsq_db_destroy(rsq_db* db);
 
 /* ---- one host process, N GPUs ------------------------------------------------------------------

@@ -205,7 +205,8 @@ public:
 
     // BULK INSERT (execute.h:332-388) straight into device columns: the Relation object stays the table's identity
     // (plans scan it), its rows live on the GPU only.  Same field rules as the reference's loop (csrc/tbl.cpp).  A second
-    // BULK INSERT into the same table appends, as the reference's does.
+    // BULK INSERT into the same table appends, as the reference's does.  The text is parsed where the context's rsq_config.tbl_ingest
+    // says (0: host threads, 1: the device; same columns, same errors): rsq_table_load_tbl obeys it, nothing changes here.
     int64_t bulkInsert(Relation* rel, const std::string& name, const std::string& fileName, char fieldTerminator) {
         std::vector<rsq_column> cols = columnsOf(rel);
         rsq_table_desc d{};

@@ -1,5 +1,6 @@
 // api.cpp — the extern "C" surface of include/resql_hip.h.  No exception crosses it.
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -28,7 +29,7 @@ Query* Q(rsq_query* q) { return reinterpret_cast<Query*>(q); }
 
 struct QueryHandle { Context* ctx; Query* q; };
 
-Table* makeTable(Context& ctx, const rsq_table_desc& d, bool adopt) {
+Table* makeTable(Context& ctx, const rsq_table_desc& d, bool adopt, double* statsMs = nullptr) {
     std::unique_ptr<Table> t(new Table());
     t->ctx = &ctx;
     t->name = std::string(d.name, strnlen(d.name, RSQ_SYMBOL_MAX));
@@ -53,7 +54,9 @@ Table* makeTable(Context& ctx, const rsq_table_desc& d, bool adopt) {
         }
         t->cols.push_back(tc);
     }
+    const auto t0 = std::chrono::steady_clock::now();
     computeColumnStats(ctx, *t);
+    if (statsMs) *statsMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return t.release();
 }
 }  // namespace
@@ -80,6 +83,7 @@ rsq_config readConfig(const rsq_config* cfg, bool multiBase) {
     if (c.nested_loops_max_pairs == 0) c.nested_loops_max_pairs = (int64_t)1 << 36;
     if (c.nested_loops_inner_slices < 0 || c.nested_loops_inner_slices > 4096)
         failInvalid("rsq_config.nested_loops_inner_slices is " + std::to_string(c.nested_loops_inner_slices) + " (0: chosen per execution, 1: never split, 2..4096: that many)");
+    if (c.tbl_ingest != 0 && c.tbl_ingest != 1) failInvalid("rsq_config.tbl_ingest is " + std::to_string(c.tbl_ingest) + " (0: BULK INSERT parses on the host, 1: on the device)");
     return c;
 }
 }  // namespace rsq
@@ -312,22 +316,67 @@ int rsq_table_from_rowstore(rsq_ctx* ctx, const rsq_table_desc* schema, const ui
 
 int rsq_table_load_tbl(rsq_ctx* ctx, const rsq_table_desc* schema, const char* path, char field_terminator,
                        int32_t n_threads, rsq_table** out) {
+    return rsq_table_load_tbl_ex(ctx, schema, path, field_terminator, n_threads, nullptr, nullptr, out);
+}
+
+int rsq_table_load_tbl_ex(rsq_ctx* ctx, const rsq_table_desc* schema, const char* path, char field_terminator, int32_t n_threads,
+                          const rsq_tbl_load_options* options, rsq_tbl_load_report* report, rsq_table** out) {
     if (!ctx || !schema || !path || !out || schema->n_cols < 0) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
+        Context& cx = *C(ctx);
+        rsq_tbl_load_options opt{};
+        if (options) {
+            if (options->struct_size < 8 || options->struct_size > 4096) failInvalid("rsq_tbl_load_options.struct_size is " + std::to_string(options->struct_size) + ": set it to sizeof(rsq_tbl_load_options)");
+            memcpy(&opt, options, std::min<size_t>(options->struct_size, sizeof opt));
+        }
+        if (report && (report->struct_size < 8 || report->struct_size > 4096)) failInvalid("rsq_tbl_load_report.struct_size is " + std::to_string(report->struct_size) + ": set it to sizeof(rsq_tbl_load_report)");
+        if (opt.mode < 0 || opt.mode > 2) failInvalid("rsq_tbl_load_options.mode must be 0 (the context's tbl_ingest), 1 (host) or 2 (device)");
+        if (opt.chunk_bytes < 0 || (opt.chunk_bytes > 0 && opt.chunk_bytes < 64)) failInvalid("rsq_tbl_load_options.chunk_bytes is " + std::to_string(opt.chunk_bytes) + " (0: 64 MiB; at least 64)");
+        if (opt.max_device_text_bytes < 0) failInvalid("rsq_tbl_load_options.max_device_text_bytes is negative (0: what is free on the device minus 1 GiB)");
+        const bool device = opt.mode == 2 || (opt.mode == 0 && cx.cfg.tbl_ingest == 1);
         std::vector<Type> types;
         for (int i = 0; i < schema->n_cols; i++) types.push_back(Type::fromC(schema->cols[i].type));
-        std::vector<std::vector<uint8_t>> cols;
-        int64_t n = 0;
-        int threads = n_threads > 0 ? n_threads : (int)std::max(1u, std::thread::hardware_concurrency());
-        parseTblFile(path, types, field_terminator, threads, cols, n);
-        static const uint8_t kEmpty[16] = {0};       // an empty file still gives columns WITH data (of zero rows)
-        std::vector<rsq_column> cd((size_t)schema->n_cols);
-        for (int i = 0; i < schema->n_cols; i++) {
-            cd[(size_t)i] = schema->cols[i];
-            cd[(size_t)i].data = cols[(size_t)i].empty() ? (const void*)kEmpty : (const void*)cols[(size_t)i].data();
+        rsq_tbl_load_report rep{};
+        const auto started = std::chrono::steady_clock::now();
+        auto ms = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+        std::unique_ptr<Table> t;
+        if (device) t = loadTblDevice(cx, *schema, types, path, field_terminator, opt.chunk_bytes, opt.max_device_text_bytes, rep);
+        if (t) {
+            const auto t0 = std::chrono::steady_clock::now();
+            computeColumnStats(cx, *t);
+            rep.stats_ms = ms(t0);
+        } else {
+            // the host path: all of it, also after a device load that gave up (its reason stays in the report)
+            const int32_t why = rep.fallback_reason;
+            rep = rsq_tbl_load_report{};
+            rep.fallback_reason = why;
+            std::vector<std::vector<uint8_t>> cols;
+            int64_t n = 0;
+            int threads = n_threads > 0 ? n_threads : (int)std::max(1u, std::thread::hardware_concurrency());
+            auto t0 = std::chrono::steady_clock::now();
+            parseTblFile(path, types, field_terminator, threads, cols, n);
+            rep.read_ms = ms(t0);
+            static const uint8_t kEmpty[16] = {0};       // an empty file still gives columns WITH data (of zero rows)
+            std::vector<rsq_column> cd((size_t)schema->n_cols);
+            for (int i = 0; i < schema->n_cols; i++) {
+                cd[(size_t)i] = schema->cols[i];
+                cd[(size_t)i].data = cols[(size_t)i].empty() ? (const void*)kEmpty : (const void*)cols[(size_t)i].data();
+            }
+            rsq_table_desc d = *schema; d.n_rows = n; d.cols = cd.data();
+            t0 = std::chrono::steady_clock::now();
+            t.reset(makeTable(cx, d, false, &rep.stats_ms));
+            rep.copy_ms = ms(t0) - rep.stats_ms;
+            rep.rows = n;
+            FILE* f = fopen(path, "rb");          // (the size alone: parseTblFile has read the file)
+            if (f) { if (fseek(f, 0, SEEK_END) == 0) rep.text_bytes = (int64_t)ftell(f); fclose(f); }
         }
-        rsq_table_desc d = *schema; d.n_rows = n; d.cols = cd.data();
-        *out = reinterpret_cast<rsq_table*>(makeTable(*C(ctx), d, false));
+        rep.total_ms = ms(started);
+        if (report) {
+            const uint32_t have = report->struct_size;
+            rep.struct_size = have;
+            memcpy(report, &rep, std::min<size_t>(have, sizeof rep));
+        }
+        *out = reinterpret_cast<rsq_table*>(t.release());
     });
 }
 
@@ -823,6 +872,7 @@ struct rsq_db {
     std::map<std::string, Table*> tables;                                          // name order = the planner's table order
     rsq_query* last = nullptr;
     rsq_report lastReport{};
+    rsq_tbl_load_report lastLoad{};          // of the last BULK INSERT
     // DBConfig / JitConfig as the control variables set them (execute.h:23-27, JitContextFlounder.h:86-109)
     bool showPlan = false, writeResultsToFile = false;
     uint16_t numThreads = 1;
@@ -1015,6 +1065,14 @@ int rsq_db_report(const rsq_db* db, rsq_report* out) {
     return RSQ_OK;
 }
 
+int rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out) {
+    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
+    rsq_tbl_load_report r = db->lastLoad;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return RSQ_OK;
+}
+
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
 int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_view* result) {
@@ -1068,8 +1126,11 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
             snprintf(d.name, RSQ_SYMBOL_MAX, "%s", stmt.tableName.c_str());
             d.n_cols = (int32_t)cols.size(); d.cols = cols.data();
             rsq_table* t = nullptr;
-            int rc = rsq_table_load_tbl(cx, &d, stmt.fileName.c_str(), stmt.fieldTerminator[0], 0, &t);
+            rsq_tbl_load_report loaded{};
+            loaded.struct_size = (uint32_t)sizeof loaded;
+            int rc = rsq_table_load_tbl_ex(cx, &d, stmt.fileName.c_str(), stmt.fieldTerminator[0], 0, nullptr, &loaded, &t);
             if (rc != RSQ_OK) throw Error(rc, db->ctx->lastError);
+            db->lastLoad = loaded;
             const int64_t inserted = T(t)->nRows;
             if (have != db->tables.end() && have->second->nRows > 0) {
                 // the reference appends to the relation (AppendIterator on the existing table, execute.h:348-350)

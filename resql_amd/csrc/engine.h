@@ -20,6 +20,7 @@
 #include "mempool.h"
 #include "resql_hip.h"
 #include "switches.h"
+#include "tbl.h"
 
 #define RSQ_RANK_CHUNK_BLOCKS 1024       /* 32-byte bitmap blocks one workgroup of the rank index handles (aot_kernels.hip) */
 
@@ -365,9 +366,12 @@ size_t runningMinTempBytes(int64_t n);
 void runningMinInPlace(Context& ctx, int64_t* v, int64_t n, int64_t* chunkMin /* runningMinTempBytes(n) */);
 void replayEmissionOrderDevice(Context& ctx, const uint64_t* hashes, uint64_t n, const std::vector<std::pair<uint64_t, uint64_t>>& levels, void* work, uint32_t* order);
 
-// tbl.cpp: '.tbl' text -> columns with the reference's BULK INSERT semantics (execute.h:332-388)
-void parseTblFile(const std::string& path, const std::vector<Type>& types, char terminator, int nThreads,
-                  std::vector<std::vector<uint8_t>>& cols, int64_t& nRows);
+// tbl.cpp: '.tbl' text -> columns with the reference's BULK INSERT semantics (execute.h:332-388): tbl.h (parseTblFile, tblParseLine)
+// tbl_device.hip: the same file parsed on the device (rsq_config.tbl_ingest, rsq_table_load_tbl_ex).  Returns the table - columns filled,
+// no statistics yet - with rep.path = 1, or null with rep.fallback_reason set (never an error: the caller takes the host path); a
+// malformed line is the host path's RSQ_ERR_INVALID.  rep's rows / text_bytes / phase times are filled as far as the load got.
+std::unique_ptr<Table> loadTblDevice(Context& ctx, const rsq_table_desc& schema, const std::vector<Type>& types, const std::string& path,
+                                     char terminator, int64_t chunkBytes, int64_t maxDeviceBytes, rsq_tbl_load_report& rep);
 
 // ---- query ------------------------------------------------------------------------------------
 struct Query;

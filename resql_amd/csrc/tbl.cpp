@@ -11,6 +11,7 @@
 //
 // This is ingest, not the hot path, but SF10 lineitem is 7.5 GB of text: the file is split at line boundaries and
 // parsed by all host threads into preallocated columns.
+#include <algorithm>
 #include <cerrno>
 #include <climits>
 #include <cstdio>
@@ -20,7 +21,7 @@
 #include <mutex>
 #include <thread>
 
-#include "engine.h"
+#include "tbl.h"
 
 namespace rsq {
 
@@ -93,6 +94,27 @@ const char* parseField(const Type& t, char* tok /* NUL terminated, writable */, 
 
 }  // namespace
 
+// std::getline(lineStream, token, terminator) over one line; see tbl.h
+const char* tblParseLine(const std::vector<Type>& types, char* line, size_t len, char terminator, uint8_t* const* cells, std::string& what) {
+    char* const lineEnd = line + len;
+    size_t att = 0;
+    char* q = line;
+    while (q < lineEnd) {
+        char* d = (char*)memchr(q, terminator, (size_t)(lineEnd - q));
+        char* tokEnd = d ? d : lineEnd;
+        if (att >= types.size()) { what = "contains extra attributes."; return what.c_str(); }
+        const char saved = *tokEnd;
+        *tokEnd = '\0';
+        const char* bad = parseField(types[att], q, (size_t)(tokEnd - q), cells[att]);
+        *tokEnd = saved;
+        if (bad) { what = std::string("field ") + std::to_string(att + 1) + ": " + bad; return what.c_str(); }
+        att++;
+        q = d ? d + 1 : lineEnd;
+    }
+    if (att < types.size()) { what = "is missing attributes."; return what.c_str(); }
+    return nullptr;
+}
+
 // -> columns (columnWidth(type) bytes per row) and the row count
 void parseTblFile(const std::string& path, const std::vector<Type>& types, char terminator, int nThreads,
                   std::vector<std::vector<uint8_t>>& cols, int64_t& nRows) {
@@ -154,25 +176,13 @@ void parseTblFile(const std::string& path, const std::vector<Type>& types, char 
     auto parseChunk = [&](const Chunk& ch) {
         char* p = buf.data() + ch.begin; char* e = buf.data() + ch.end;
         int64_t row = ch.firstLine;
+        std::vector<uint8_t*> cells(types.size());
+        std::string what;
         while (p < e) {
             char* nl = (char*)memchr(p, '\n', (size_t)(e - p));
             char* lineEnd = nl ? nl : e;
-            size_t att = 0;
-            bool bad = false;
-            char* q = p;
-            while (q < lineEnd) {                            // std::getline(lineStream, token, terminator)
-                char* d = (char*)memchr(q, terminator, (size_t)(lineEnd - q));
-                char* tokEnd = d ? d : lineEnd;
-                if (att >= types.size()) { fail(row, "contains extra attributes."); bad = true; break; }
-                const char saved = *tokEnd;
-                *tokEnd = '\0';
-                const char* what = parseField(types[att], q, (size_t)(tokEnd - q), &cols[att][(size_t)row * (size_t)width[att]]);
-                *tokEnd = saved;
-                if (what) { fail(row, std::string("field ") + std::to_string(att + 1) + ": " + what); bad = true; break; }
-                att++;
-                q = d ? d + 1 : lineEnd;
-            }
-            if (!bad && att < types.size()) fail(row, "is missing attributes.");
+            for (size_t i = 0; i < types.size(); i++) cells[i] = cols[i].data() + (size_t)row * (size_t)width[i];
+            if (tblParseLine(types, p, (size_t)(lineEnd - p), terminator, cells.data(), what)) fail(row, what);
             row++;
             if (!nl) break;
             p = nl + 1;

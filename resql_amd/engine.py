@@ -28,14 +28,14 @@ class rsq_config(C.Structure):
                 ("device", C.c_int32), ("kernel_cache_dir", C.c_char_p), ("emission_order", C.c_int32),
                 ("compat_flags", C.c_uint32), ("engine_flags", C.c_uint32), ("reserved0", C.c_uint32),
                 ("arena_reserve_bytes", C.c_int64), ("arena_keep_bytes", C.c_int64), ("nested_loops_max_pairs", C.c_int64),
-                ("nested_loops_inner_slices", C.c_int32), ("reserved1", C.c_int32)]
+                ("nested_loops_inner_slices", C.c_int32), ("tbl_ingest", C.c_int32)]
 
     @classmethod
     def make(cls, device: int, cache_dir=None, print_source: bool = False, emission_order: int = 0, compat_flags: int = 0,
              engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0, nested_loops_max_pairs: int = 0,
-             nested_loops_inner_slices: int = 0):
+             nested_loops_inner_slices: int = 0, tbl_ingest: int = 0):
         return cls(C.sizeof(cls), 1 if print_source else 0, 0, 0, 1, 1, 0, device, cache_dir, emission_order, compat_flags,
-                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes, nested_loops_max_pairs, nested_loops_inner_slices, 0)
+                   engine_flags, 0, arena_reserve_bytes, arena_keep_bytes, nested_loops_max_pairs, nested_loops_inner_slices, tbl_ingest)
 
 
 class rsq_report(C.Structure):
@@ -43,6 +43,26 @@ class rsq_report(C.Structure):
                 ("kernel_time_ms", C.c_double), ("finalize_time_ms", C.c_double),
                 ("num_kernels", C.c_uint64), ("bytes_read", C.c_uint64), ("hbm_gbps", C.c_double),
                 ("jit_cache_hits", C.c_int32), ("jit_compiles", C.c_int32)]
+
+
+class rsq_tbl_load_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_bytes", C.c_int64), ("max_device_text_bytes", C.c_int64)]
+
+
+class rsq_tbl_load_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("text_bytes", C.c_int64), ("lines_patched", C.c_int64),
+                ("read_ms", C.c_double), ("copy_ms", C.c_double), ("kernel_ms", C.c_double), ("patch_ms", C.c_double),
+                ("stats_ms", C.c_double), ("total_ms", C.c_double),
+                ("count_kernel_ms", C.c_double), ("starts_kernel_ms", C.c_double), ("parse_kernel_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+TBL_HOST, TBL_DEVICE = 1, 2      # rsq_tbl_load_options.mode (0: the context's tbl_ingest)
+# rsq_tbl_fallback: why a load that asked for the device took the host path
+TBL_FALLBACK_NONE, TBL_FALLBACK_NO_DEVICE, TBL_FALLBACK_COLUMNS, TBL_FALLBACK_TERMINATOR, TBL_FALLBACK_DOES_NOT_FIT, TBL_FALLBACK_ODD_LINES = range(6)
 
 
 class rsq_memory_stats(C.Structure):
@@ -103,6 +123,8 @@ def lib():
                                               C.POINTER(C.c_size_t), i32, C.POINTER(vp)]
         L.rsq_table_generate.argtypes = [vp, i32, i64, i64, C.c_double, i64, C.c_uint64, C.POINTER(vp)]
         L.rsq_table_load_tbl.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.c_char_p, C.c_char, i32, C.POINTER(vp)]
+        L.rsq_table_load_tbl_ex.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.c_char_p, C.c_char, i32, C.POINTER(rsq_tbl_load_options),
+                                            C.POINTER(rsq_tbl_load_report), C.POINTER(vp)]
         L.rsq_table_rows.restype = i64
         L.rsq_table_rows.argtypes = [vp]
         L.rsq_table_read_column.argtypes = [vp, vp, C.c_char_p, vp, C.c_size_t]
@@ -171,6 +193,7 @@ def lib():
         L.rsq_db_message.restype = C.c_char_p
         L.rsq_db_message.argtypes = [vp]
         L.rsq_db_report.argtypes = [vp, C.POINTER(rsq_report)]
+        L.rsq_db_load_report.argtypes = [vp, C.POINTER(rsq_tbl_load_report)]
         L.rsq_db_destroy.argtypes = [vp]
         L.rsq_multi_create.argtypes = [C.POINTER(rsq_multi_config), C.POINTER(vp)]
         L.rsq_multi_destroy.argtypes = [vp]
@@ -203,7 +226,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "rsq_ctx_create", "rsq_ctx_destroy", "rsq_last_error", "rsq_table_create", "rsq_table_create_device",
-    "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
+    "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_load_tbl_ex", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
     "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_unify_shard_dictionaries", "rsq_table_time_dictionary_pass", "rsq_table_total_rows",
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
@@ -213,7 +236,7 @@ EXPORTED_SYMBOLS = [
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
-    "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_destroy",
+    "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_load_report", "rsq_db_destroy",
     "rsq_multi_create", "rsq_multi_destroy", "rsq_multi_last_error", "rsq_multi_devices", "rsq_multi_ctx", "rsq_multi_merge_name",
     "rsq_multi_shard_rows", "rsq_multi_table_generate", "rsq_multi_table_generate_on_key", "rsq_multi_query_merge_name", "rsq_multi_query_explain", "rsq_multi_query_compile", "rsq_multi_query_execute",
     "rsq_multi_query_result", "rsq_multi_query_report", "rsq_multi_query_collective_ms", "rsq_multi_query_destroy",
@@ -256,15 +279,16 @@ class Context:
 
     def __init__(self, device: int = 0, cache_dir: Optional[str] = None, print_source: bool = False, emission_order: int = 0,
                  compat_flags: int = 0, engine_flags: int = 0, arena_reserve_bytes: int = 0, arena_keep_bytes: int = 0,
-                 nested_loops_max_pairs: int = 0, nested_loops_inner_slices: int = 0):
+                 nested_loops_max_pairs: int = 0, nested_loops_inner_slices: int = 0, tbl_ingest: int = 0):
         """emission_order: EMIT_REFERENCE (0: rows of an unsorted aggregation in the reference's hash-table order) or EMIT_ANY;
         compat_flags: rsq_compat bits (COMPAT_JIT_INT16_CAST); engine_flags: rsq_engine_flags bits (ENGINE_DRIVER_ALLOC,
         ENGINE_NO_PLAN_MEMO, ENGINE_NESTED_LOOPS); arena_*, nested_loops_max_pairs (0: 2^36 pairs), nested_loops_inner_slices (0: chosen per execution,
-        1: never split, 2..4096: that many slices of an aggregating nested-loops join's inner rows): see rsq_config"""
+        1: never split, 2..4096: that many slices of an aggregating nested-loops join's inner rows), tbl_ingest (0: BULK INSERT parses its
+        text on the host, 1: on the device): see rsq_config"""
         self._L = lib()
         self._cache = cache_dir.encode() if cache_dir else None
         cfg = rsq_config.make(device, self._cache, print_source, emission_order, compat_flags, engine_flags, arena_reserve_bytes, arena_keep_bytes,
-                              nested_loops_max_pairs, nested_loops_inner_slices)
+                              nested_loops_max_pairs, nested_loops_inner_slices, tbl_ingest)
         h = C.c_void_p()
         rc = self._L.rsq_ctx_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -410,14 +434,21 @@ class Context:
         self._check(self._L.rsq_table_create_device(self.h, C.byref(d), C.byref(h)))
         return DeviceTable(self, h, name, {cn: ct.width for cn, ct, _ in columns})
 
-    def load_tbl(self, schema: P.Table, path: str, terminator: str = "|", threads: int = 0) -> "DeviceTable":
-        """BULK INSERT of a '.tbl' text file into a table with `schema`'s column names and types"""
+    def load_tbl(self, schema: P.Table, path: str, terminator: str = "|", threads: int = 0, mode: int = 0, chunk_bytes: int = 0,
+                 max_device_text_bytes: int = 0) -> "DeviceTable":
+        """BULK INSERT of a '.tbl' text file into a table with `schema`'s column names and types (rsq_table_load_tbl_ex).  mode 0: parsed
+        where the context's tbl_ingest says, TBL_HOST, TBL_DEVICE; the table's load_report says which path ran, why, and its phases"""
         keep: list = []
         bare = P.Table(schema.name, [P.Column(c.name, c.type) for c in schema.columns], 0)
         d = bare.to_c(keep)
         h = C.c_void_p()
-        self._check(self._L.rsq_table_load_tbl(self.h, C.byref(d), path.encode(), terminator.encode()[:1], threads, C.byref(h)))
-        return DeviceTable(self, h, schema.name, {c.name: c.type.width for c in schema.columns})
+        opt = rsq_tbl_load_options(C.sizeof(rsq_tbl_load_options), mode, chunk_bytes, max_device_text_bytes)
+        rep = rsq_tbl_load_report(C.sizeof(rsq_tbl_load_report))
+        self._check(self._L.rsq_table_load_tbl_ex(self.h, C.byref(d), path.encode(), terminator.encode()[:1], threads, C.byref(opt), C.byref(rep),
+                                                  C.byref(h)))
+        t = DeviceTable(self, h, schema.name, {c.name: c.type.width for c in schema.columns})
+        t.load_report = rep.as_dict()
+        return t
 
     def generate(self, kind: int, n_rows: int, sf: float, row0: int = 0, param: int = 0,
                  seed: int = 20240613) -> "DeviceTable":
@@ -513,6 +544,7 @@ class DeviceTable:
     def __init__(self, ctx: Context, h, name: str, widths: Optional[dict] = None):
         self.ctx, self.h, self.name = ctx, h, name
         self.widths = dict(widths or {})          # bytes per row of the columns, by name, where the schema came through Python (read_image)
+        self.load_report: Optional[dict] = None   # of Context.load_tbl
         ctx._adopt(self)
 
     @property
@@ -710,6 +742,13 @@ class Database:
         r = rsq_report()
         self.ctx._check(self.ctx._L.rsq_db_report(self.h, C.byref(r)))
         return r
+
+    @property
+    def load_report(self) -> dict:
+        """rsq_tbl_load_report of the last BULK INSERT: which path parsed the file, why, rows, lines patched, phase times"""
+        r = rsq_tbl_load_report(C.sizeof(rsq_tbl_load_report))
+        self.ctx._check(self.ctx._L.rsq_db_load_report(self.h, C.byref(r)))
+        return r.as_dict()
 
     def execute_script(self, text: str):
         res = None
