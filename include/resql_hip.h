@@ -355,6 +355,43 @@ char* rsq_serialize_expr(rsq_ctx* ctx, const rsq_plan_desc* plan, int32_t expr, 
 /* serializeRelation (reference src/dbdata.h:688-701) of a result view. */
 char* rsq_result_serialize(const rsq_result_view* view);
 void  rsq_free(void* p);
+/* The same text of a query's result, optionally written on the DEVICE (opt-in: rsq_ctx_set_result_text, or mode 2 here).  The host
+ * path is rsq_result_serialize's: one thread, one cell after the other, and it stays the definition of the text.  The device path
+ * produces the same bytes: the tuples are uploaded in chunks of chunk_rows rows, one kernel takes every row's text length (one lane
+ * per row; resql_amd/csrc/result_text.h holds the text of a cell for both sides), the toolkit's exclusive scan turns the workgroups'
+ * totals into offsets, a second kernel writes the text - staged in LDS and stored 16 bytes per lane where a workgroup's span fits
+ * the tile - and the text comes back through pinned staging.  Device and pinned memory are the context's arenas' and are given back
+ * however the call ends.  The call takes the host path - reported, never an error - where the context has no device, the schema
+ * is outside the device form (more than 64 columns, CHAR of length 0, a DECIMAL scale above 18, a row whose text may exceed
+ * 64 KiB), or a chunk of one row does not fit max_device_bytes.  The tuples are always uploaded from the host copy the result
+ * view hands out (tuples_from_device stays 0: reading a device tail's buffer in place is not built).
+ * Options and report carry struct_size like rsq_config: the library reads / writes no more than that many bytes.  A query that has
+ * not been executed answers as rsq_query_result does (a relation of no rows).  The handles of several GPUs keep the host text. */
+typedef struct rsq_result_text_options {
+    uint32_t struct_size;            /* sizeof(rsq_result_text_options) */
+    int32_t  mode;                   /* 0: the context's setting; 1: host; 2: device; else RSQ_ERR_INVALID */
+    int64_t  chunk_rows;             /* rows per chunk (0: chosen, so that a chunk's text stays below 2^32 bytes and within the budget; < 0: RSQ_ERR_INVALID) */
+    int64_t  max_device_bytes;       /* device memory the call may take while it runs (0: what is free minus 1 GiB; < 0: RSQ_ERR_INVALID) */
+} rsq_result_text_options;
+enum rsq_text_fallback { RSQ_TEXT_FALLBACK_NONE = 0, RSQ_TEXT_FALLBACK_NO_DEVICE = 1, RSQ_TEXT_FALLBACK_SCHEMA = 2, RSQ_TEXT_FALLBACK_DOES_NOT_FIT = 3 };
+typedef struct rsq_result_text_report {
+    uint32_t struct_size;            /* sizeof(rsq_result_text_report) */
+    int32_t  path;                   /* 0: written by the host; 1: on the device */
+    int32_t  fallback_reason;        /* rsq_text_fallback: why a call that asked for the device took the host path (0: it did not) */
+    int32_t  tuples_from_device;     /* 1: the kernels read the tuples where a device tail had left them; 0: uploaded from the host */
+    int64_t  rows, text_bytes, chunks;
+    /* ms.  Device path: HIP events around the uploads, the kernels (lengths, scan, write) and the copies back; download_ms also
+     * holds the host's copy out of the staging buffer (or its fwrite).  Host path: total_ms alone. */
+    double   upload_ms, kernel_ms, download_ms, total_ms;
+} rsq_result_text_report;
+/* *text: malloc'ed, *text_bytes long and NUL-terminated behind that (rsq_free). */
+int  rsq_query_result_text(rsq_query* q, const rsq_result_text_options* options /* NULL: the defaults */, rsq_result_text_report* report /* may be NULL */,
+                           char** text, int64_t* text_bytes);
+/* ... straight into the file `path` (created or truncated) */
+int  rsq_query_result_write(rsq_query* q, const char* path, const rsq_result_text_options* options, rsq_result_text_report* report);
+/* Where mode 0 and the statement loop's `tofile` write their text: 0 host (the default), 1 device; else RSQ_ERR_INVALID naming
+ * "result_text".  A setter, not a field: rsq_config keeps its size. */
+int  rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where);
 /* The slot order of the reference's aggregation hash table (allocateHashTable / ht_put / growHashTable, src/qlib/hash.h:225-287,
  * 330-419) after inserting n groups with the given Values::hash values in this order into a table allocated for min_size
  * entries: out[k] = index of the group in the k-th occupied slot.  parallel != 0 takes the cluster-parallel replay the engine's
@@ -473,13 +510,15 @@ int  rsq_db_execute(rsq_db* db, const char* sql, int32_t* kind, rsq_result_view*
  * the name may stand anywhere in the line — and `tables`.  Effects on later SELECTs: showplan puts the operator tree,
  * showperf the `compile:` / `execute:` lines of showReport (JitContextFlounder.h:132-150) plus the device figures, showasm the
  * generated HIP source, showfln the pipeline description into the message; tofile=true writes the result to "qres.tbl"
- * (serializeRelation format, execute.h:203-210, 243-245); threads / optimize / emitmc are stored and reported only.
+ * (serializeRelation format, execute.h:203-210, 243-245; written where rsq_ctx_set_result_text says, the host by default - the bytes
+ * are the same, rsq_db_result_text_report tells which path wrote them); threads / optimize / emitmc are stored and reported only.
  * rsq_db_message: what the reference's printQueryResult prints for the last statement in front of the relation
  * (execute.h:173-200): the control statement's answer, "Created table x", "Inserted n tuples", or plan + report. */
 const char* rsq_db_message(const rsq_db* db);
 int  rsq_db_adopt_table(rsq_db* db, rsq_table* table);
 int  rsq_db_report(const rsq_db* db, rsq_report* out);          /* of the last SELECT */
 int  rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out);      /* of the last BULK INSERT (out->struct_size set by the caller) */
+int  rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out);      /* of the last SELECT that `tofile` wrote (likewise) */
 void rsq_db_destroy(rsq_db* db);
 
 /* ---- one host process, N GPUs ------------------------------------------------------------------

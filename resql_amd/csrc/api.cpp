@@ -579,6 +579,71 @@ char* rsq_result_serialize(const rsq_result_view* view) {
 
 void rsq_free(void* p) { free(p); }
 
+namespace {
+// options and report of rsq_query_result_text / _write as the host's header declared them
+void readTextOptions(const rsq_result_text_options* options, const rsq_result_text_report* report, rsq_result_text_options& opt) {
+    opt = rsq_result_text_options{};
+    if (options) {
+        if (options->struct_size < 8 || options->struct_size > 4096) failInvalid("rsq_result_text_options.struct_size is " + std::to_string(options->struct_size) + ": set it to sizeof(rsq_result_text_options)");
+        memcpy(&opt, options, std::min<size_t>(options->struct_size, sizeof opt));
+    }
+    if (report && (report->struct_size < 8 || report->struct_size > 4096)) failInvalid("rsq_result_text_report.struct_size is " + std::to_string(report->struct_size) + ": set it to sizeof(rsq_result_text_report)");
+    if (opt.mode < 0 || opt.mode > 2) failInvalid("rsq_result_text_options.mode must be 0 (the context's result_text setting), 1 (host) or 2 (device)");
+    if (opt.chunk_rows < 0) failInvalid("rsq_result_text_options.chunk_rows is negative (0: chosen)");
+    if (opt.max_device_bytes < 0) failInvalid("rsq_result_text_options.max_device_bytes is negative (0: what is free on the device minus 1 GiB)");
+}
+void handTextReport(rsq_result_text_report rep, rsq_result_text_report* report) {
+    if (!report) return;
+    const uint32_t have = report->struct_size;
+    rep.struct_size = have;
+    memcpy(report, &rep, std::min<size_t>(have, sizeof rep));
+}
+}  // namespace
+
+int rsq_query_result_text(rsq_query* q, const rsq_result_text_options* options, rsq_result_text_report* report, char** text, int64_t* text_bytes) {
+    if (!q || !text || !text_bytes) return RSQ_ERR_INVALID;
+    *text = nullptr; *text_bytes = 0;
+    return guarded(QH(q)->ctx, [&] {
+        Context& cx = *QH(q)->ctx;
+        rsq_result_text_options opt;
+        readTextOptions(options, report, opt);
+        rsq_result_view view;
+        queryResult(*QH(q)->q, &view);
+        TextOut out;
+        rsq_result_text_report rep{};
+        writeResultText(cx, view, opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
+        handTextReport(rep, report);
+        *text_bytes = (int64_t)out.size;
+        *text = out.release();
+    });
+}
+
+int rsq_query_result_write(rsq_query* q, const char* path, const rsq_result_text_options* options, rsq_result_text_report* report) {
+    if (!q || !path) return RSQ_ERR_INVALID;
+    return guarded(QH(q)->ctx, [&] {
+        Context& cx = *QH(q)->ctx;
+        rsq_result_text_options opt;
+        readTextOptions(options, report, opt);
+        rsq_result_view view;
+        queryResult(*QH(q)->q, &view);
+        TextOut out;
+        out.file = fopen(path, "w");
+        if (!out.file) failInvalid(std::string("Could not open file ") + path);
+        rsq_result_text_report rep{};
+        writeResultText(cx, view, opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
+        out.closeFile();
+        handTextReport(rep, report);
+    });
+}
+
+int rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid("result_text is " + std::to_string(where) + " (0: results become text on the host, 1: on the device)");
+        C(ctx)->resultText = where;
+    });
+}
+
 int rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t n, uint64_t min_size, uint32_t* out) {
     if (!ctx || n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
@@ -873,6 +938,7 @@ struct rsq_db {
     rsq_query* last = nullptr;
     rsq_report lastReport{};
     rsq_tbl_load_report lastLoad{};          // of the last BULK INSERT
+    rsq_result_text_report lastText{};       // of the last SELECT that `tofile` wrote
     // DBConfig / JitConfig as the control variables set them (execute.h:23-27, JitContextFlounder.h:86-109)
     bool showPlan = false, writeResultsToFile = false;
     uint16_t numThreads = 1;
@@ -1073,6 +1139,14 @@ int rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out) {
     return RSQ_OK;
 }
 
+int rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out) {
+    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
+    rsq_result_text_report r = db->lastText;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return RSQ_OK;
+}
+
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
 int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_view* result) {
@@ -1167,11 +1241,11 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
     if (selectStatus != RSQ_OK) return selectStatus;
     if (db->writeResultsToFile) {            // writeRelationToFile(*rel, "qres.tbl") (execute.h:203-210, 243-245)
         selectStatus = guarded(db->ctx, [&] {
-            FILE* f = fopen("qres.tbl", "w");
-            if (!f) failInvalid("Could not open file qres.tbl");
-            std::string text = serializeResultView(view);
-            fwrite(text.data(), 1, text.size(), f);
-            fclose(f);
+            TextOut out;
+            out.file = fopen("qres.tbl", "w");
+            if (!out.file) failInvalid("Could not open file qres.tbl");
+            writeResultText(*db->ctx, view, db->ctx->resultText == 1, 0, 0, out, db->lastText);          // (the context's setting at 0: serializeResultView, as ever)
+            out.closeFile();
         });
         if (selectStatus != RSQ_OK) return selectStatus;
     }

@@ -1961,17 +1961,4 @@ const char* querySource(const Query& q) { return q.allSource.c_str(); }
 const char* queryExplain(const Query& q) { return q.explainText.c_str(); }
 void destroyQuery(Query* q) { delete q; }
 
-std::string serializeResultView(const rsq_result_view& v) {
-    std::string out;
-    for (int64_t r = 0; r < v.n_rows; r++) {
-        const uint8_t* t = v.tuples + (size_t)r * (size_t)v.tuple_size;
-        for (int c = 0; c < v.n_cols; c++) {
-            Type ty = Type::fromC(v.types[c]);
-            out += serializeSqlValue(loadValue(t + v.offsets[c], ty), ty) + "|";
-        }
-        out += "\n";
-    }
-    return out;
-}
-
 }  // namespace rsq

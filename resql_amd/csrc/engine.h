@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <functional>
 #include <map>
@@ -219,6 +220,7 @@ struct Context {
     // merge of the shards' results takes hash aggregations, not dense tables keyed by one context's dictionary.  The exception: a unified
     // shard scanned for a key whose dictionary all shards share (TableColumn::dictShared, RSQ_ENGINE_DICT_MULTI)
     bool shardCompile = false;
+    int32_t resultText = 0;                    // rsq_ctx_set_result_text: 0 results become text on the host, 1 on the device (result_text.hip)
 };
 
 rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // api.cpp: the host's struct (struct_size bytes), validated
@@ -424,5 +426,17 @@ const char* queryExplain(const Query& q);
 void destroyQuery(Query* q);
 
 std::string serializeResultView(const rsq_result_view& v);
+// result_text.hip: the same text written on the device (rsq_ctx_set_result_text, rsq_query_result_text).  Where the text goes: a file,
+// or a malloc'ed buffer that grows (NUL-terminated by release).
+struct TextOut {
+    FILE* file = nullptr;
+    char* buf = nullptr; size_t size = 0, cap = 0;
+    void append(const void* p, size_t n);
+    char* release();                      // the buffer, the caller's from now on
+    void closeFile();                     // with the error a full disk raises only now
+    ~TextOut() { if (file) fclose(file); ::free(buf); }
+};
+// device == false, or a device path that cannot take the view (rep.fallback_reason says why): serializeResultView.  rep is filled either way.
+void writeResultText(Context& ctx, const rsq_result_view& v, bool device, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep);
 
 }  // namespace rsq

@@ -415,6 +415,20 @@ Val loadValue(const uint8_t* addr, const Type& t) {
     return v;
 }
 
+// (here, beside loadValue, so that host-only programs link it: tests/cpp/result_text_test.cpp)
+std::string serializeResultView(const rsq_result_view& v) {
+    std::string out;
+    for (int64_t r = 0; r < v.n_rows; r++) {
+        const uint8_t* t = v.tuples + (size_t)r * (size_t)v.tuple_size;
+        for (int c = 0; c < v.n_cols; c++) {
+            Type ty = Type::fromC(v.types[c]);
+            out += serializeSqlValue(loadValue(t + v.offsets[c], ty), ty) + "|";
+        }
+        out += "\n";
+    }
+    return out;
+}
+
 int compareTyped(const Type& t, const uint8_t* l, const uint8_t* r) {
     switch (t.tag) {
         case RSQ_BIGINT: case RSQ_DECIMAL: { int64_t a, b; memcpy(&a, l, 8); memcpy(&b, r, 8); return a < b ? -1 : a > b; }

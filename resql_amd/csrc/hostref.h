@@ -52,5 +52,6 @@ bool refLike(const char* s, const char* pattern);
 // packed tuple access (reference src/values.h:151-232)
 void storeValue(uint8_t* addr, Val v, const Type& t);      // strings by value, NUL terminated
 Val loadValue(const uint8_t* addr, const Type& t);
+std::string serializeResultView(const rsq_result_view& v);      // serializeRelation: every cell's serializeSqlValue with its '|', a newline per row
 
 }  // namespace rsq

@@ -65,6 +65,24 @@ TBL_HOST, TBL_DEVICE = 1, 2      # rsq_tbl_load_options.mode (0: the context's t
 TBL_FALLBACK_NONE, TBL_FALLBACK_NO_DEVICE, TBL_FALLBACK_COLUMNS, TBL_FALLBACK_TERMINATOR, TBL_FALLBACK_DOES_NOT_FIT, TBL_FALLBACK_ODD_LINES = range(6)
 
 
+class rsq_result_text_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_rows", C.c_int64), ("max_device_bytes", C.c_int64)]
+
+
+class rsq_result_text_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("tuples_from_device", C.c_int32),
+                ("rows", C.c_int64), ("text_bytes", C.c_int64), ("chunks", C.c_int64),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double), ("download_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+TEXT_HOST, TEXT_DEVICE = 1, 2      # rsq_result_text_options.mode (0: the context's set_result_text)
+# rsq_text_fallback: why a result text that asked for the device was written by the host
+TEXT_FALLBACK_NONE, TEXT_FALLBACK_NO_DEVICE, TEXT_FALLBACK_SCHEMA, TEXT_FALLBACK_DOES_NOT_FIT = range(4)
+
+
 class rsq_memory_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("device_slab_bytes", C.c_uint64), ("device_used_bytes", C.c_uint64),
                 ("device_slab_allocs", C.c_uint64), ("pinned_slab_bytes", C.c_uint64), ("pinned_used_bytes", C.c_uint64),
@@ -168,6 +186,10 @@ def lib():
         L.rsq_result_serialize.restype = vp
         L.rsq_result_serialize.argtypes = [C.POINTER(P.rsq_result_view)]
         L.rsq_free.argtypes = [vp]
+        L.rsq_query_result_text.argtypes = [vp, C.POINTER(rsq_result_text_options), C.POINTER(rsq_result_text_report), C.POINTER(vp), C.POINTER(i64)]
+        L.rsq_query_result_write.argtypes = [vp, C.c_char_p, C.POINTER(rsq_result_text_options), C.POINTER(rsq_result_text_report)]
+        L.rsq_ctx_set_result_text.argtypes = [vp, i32]
+        L.rsq_db_result_text_report.argtypes = [vp, C.POINTER(rsq_result_text_report)]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
         L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
@@ -231,7 +253,7 @@ EXPORTED_SYMBOLS = [
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_nested_loops_slices", "rsq_nested_loops_slices", "rsq_query_source", "rsq_query_explain",
-    "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
+    "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_query_result_text", "rsq_query_result_write", "rsq_ctx_set_result_text", "rsq_db_result_text_report", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
     "rsq_measure_read_bandwidth",
@@ -386,6 +408,11 @@ class Context:
                                                  1 if is32 else 0, 1 if desc else 0, want, form, None if rng is None else rng.ctypes.data, capacity,
                                                  cand.ctypes.data, C.addressof(count), C.addressof(notes)))
         return cand, count.value, notes.value
+
+    def set_result_text(self, where: int):
+        """where results become text under mode 0 and the statement loop's `tofile`: 0 on the host (the default), 1 on the device
+        (rsq_ctx_set_result_text)"""
+        self._check(self._L.rsq_ctx_set_result_text(self.h, where))
 
     def set_stream(self, hip_stream: Optional[int]):
         """launch on the caller's HIP stream (an integer handle, 0 = the null stream; e.g.
@@ -670,6 +697,25 @@ class Query:
         res.text = res.serialize() if text else None
         return res
 
+    def result_text(self, mode: int = 0, chunk_rows: int = 0, max_device_bytes: int = 0):
+        """(the result's '.tbl' text as bytes, the report as a dict) - rsq_query_result_text.  mode 0: written where the context's
+        set_result_text says, TEXT_HOST, TEXT_DEVICE; the report says which path ran, why, rows, chunks and the phases"""
+        opt = rsq_result_text_options(C.sizeof(rsq_result_text_options), mode, chunk_rows, max_device_bytes)
+        rep = rsq_result_text_report(C.sizeof(rsq_result_text_report))
+        p, n = C.c_void_p(), C.c_int64(0)
+        self.ctx._check(self.ctx._L.rsq_query_result_text(self.h, C.byref(opt), C.byref(rep), C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value), rep.as_dict()
+        finally:
+            self.ctx._L.rsq_free(p)
+
+    def write_result_text(self, path: str, mode: int = 0, chunk_rows: int = 0, max_device_bytes: int = 0) -> dict:
+        """the same text straight into the file `path` (rsq_query_result_write); returns the report"""
+        opt = rsq_result_text_options(C.sizeof(rsq_result_text_options), mode, chunk_rows, max_device_bytes)
+        rep = rsq_result_text_report(C.sizeof(rsq_result_text_report))
+        self.ctx._check(self.ctx._L.rsq_query_result_write(self.h, path.encode(), C.byref(opt), C.byref(rep)))
+        return rep.as_dict()
+
     def report(self) -> rsq_report:
         r = rsq_report()
         self.ctx._check(self.ctx._L.rsq_query_report(self.h, C.byref(r)))
@@ -748,6 +794,13 @@ class Database:
         """rsq_tbl_load_report of the last BULK INSERT: which path parsed the file, why, rows, lines patched, phase times"""
         r = rsq_tbl_load_report(C.sizeof(rsq_tbl_load_report))
         self.ctx._check(self.ctx._L.rsq_db_load_report(self.h, C.byref(r)))
+        return r.as_dict()
+
+    @property
+    def result_text_report(self) -> dict:
+        """rsq_result_text_report of the last SELECT that `tofile` wrote: which path wrote qres.tbl, why, rows, chunks, phase times"""
+        r = rsq_result_text_report(C.sizeof(rsq_result_text_report))
+        self.ctx._check(self.ctx._L.rsq_db_result_text_report(self.h, C.byref(r)))
         return r.as_dict()
 
     def execute_script(self, text: str):
