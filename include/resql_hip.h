@@ -187,10 +187,44 @@ int  rsq_table_create_device(rsq_ctx* ctx, const rsq_table_desc* desc, rsq_table
  * statistics they were compiled with (and their checks); compile the statement again to plan with the new ones. */
 int  rsq_table_refresh_stats(rsq_table* t);
 /* Transpose a ReSQL row store (reference src/dbdata.h: DataBlocks of packed tuples, strings by
- * value) into device columns: the bridge for a host that keeps ReSQL's own Relation objects. */
+ * value) into device columns: the bridge for a host that keeps ReSQL's own Relation objects.
+ * The tuples are transposed where the context's rsq_ctx_set_rowstore_bridge says (the host by default): the call is
+ * rsq_table_from_rowstore_ex with NULL options. */
 int  rsq_table_from_rowstore(rsq_ctx* ctx, const rsq_table_desc* schema /* data pointers ignored */,
                              const uint8_t* const* blocks, const size_t* content_size, int32_t n_blocks,
                              rsq_table** out);
+/* The same bridge with the transposition on the DEVICE (opt-in: rsq_ctx_set_rowstore_bridge, or mode 2 here).  The host path zero-fills
+ * one buffer per column, walks every tuple on one thread and uploads the columns from pageable memory.  The device path copies the
+ * tuples - whole tuples, packed back to back, chunk_bytes at a time - into one of two pinned buffers, sends the chunk to the device
+ * behind the kernel of the chunk before it, and one kernel per chunk writes every cell of the chunk's rows into the columns
+ * (resql_amd/csrc/rowstore.h holds the rule of a cell for both sides: a string's bytes behind its first NUL are zero in the column).
+ * Columns, statistics and errors are those of the host path byte for byte.  Besides the columns the call holds two chunks of device
+ * memory and two of pinned memory from the context's arenas, given back however it ends.  The call takes the host path - reported,
+ * never an error - where the context has no device or the table has more than 64 columns.
+ * Options and report carry struct_size like rsq_config: the library reads / writes no more than that many bytes. */
+typedef struct rsq_rowstore_options {
+    uint32_t struct_size;            /* sizeof(rsq_rowstore_options) */
+    int32_t  mode;                   /* 0: the context's setting; 1: host; 2: device; else RSQ_ERR_INVALID */
+    int64_t  chunk_bytes;            /* bytes of tuples per chunk (0: 64 MiB; raised to one tuple where smaller; < 0 or > 1 GiB: RSQ_ERR_INVALID) */
+} rsq_rowstore_options;
+enum rsq_rowstore_fallback { RSQ_ROWSTORE_FALLBACK_NONE = 0, RSQ_ROWSTORE_FALLBACK_NO_DEVICE = 1, RSQ_ROWSTORE_FALLBACK_COLUMNS = 2 };
+typedef struct rsq_rowstore_report {
+    uint32_t struct_size;            /* sizeof(rsq_rowstore_report) */
+    int32_t  path;                   /* 0: transposed by the host; 1: on the device */
+    int32_t  fallback_reason;        /* rsq_rowstore_fallback: why a call that asked for the device took the host path (0: it did not) */
+    int32_t  reserved;
+    int64_t  rows, tuple_bytes;      /* tuples taken from the blocks, and their bytes */
+    int64_t  chunks;                 /* device path: chunks sent */
+    /* host wall time in ms.  Device path: stage = the copies into the pinned buffers, copy = waiting for the link behind them,
+     * kernel = HIP events around the kernels.  Host path: transpose = the host loop, copy = the upload of the columns. */
+    double   stage_ms, copy_ms, kernel_ms, transpose_ms, stats_ms, total_ms;
+} rsq_rowstore_report;
+int  rsq_table_from_rowstore_ex(rsq_ctx* ctx, const rsq_table_desc* schema /* data pointers ignored */, const uint8_t* const* blocks,
+                                const size_t* content_size, int32_t n_blocks, const rsq_rowstore_options* options /* NULL: the defaults */,
+                                rsq_rowstore_report* report /* may be NULL */, rsq_table** out);
+/* Where mode 0 - and so rsq_table_from_rowstore - transposes: 0 host (the default), 1 device; else RSQ_ERR_INVALID naming
+ * "rowstore_bridge".  A setter, not a field: rsq_config keeps its size. */
+int  rsq_ctx_set_rowstore_bridge(rsq_ctx* ctx, int32_t where);
 /* BULK INSERT: load a '.tbl' text file (one tuple per line, fields ended by `field_terminator`, dbgen style with or
  * without the trailing terminator) straight into device columns, with the parsing rules of the reference's
  * executeBulkInsert / parseConstant (reference src/execute.h:332-388, src/expressions.h:369-515): see

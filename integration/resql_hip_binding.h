@@ -203,6 +203,10 @@ public:
         return r.t;
     }
 
+    // Where deviceTable transposes a Relation's tuples - whole Relations and the tails of grown ones alike: 0 on one host thread (the
+    // default), 1 on the device (rsq_ctx_set_rowstore_bridge; same columns, same statistics).  rsq_table_from_rowstore obeys it.
+    void setRowstoreBridge(int where) { check(rsq_ctx_set_rowstore_bridge(ctx_, where)); }
+
     // BULK INSERT (execute.h:332-388) straight into device columns: the Relation object stays the table's identity
     // (plans scan it), its rows live on the GPU only.  Same field rules as the reference's loop (csrc/tbl.cpp).  A second
     // BULK INSERT into the same table appends, as the reference's does.  The text is parsed where the context's rsq_config.tbl_ingest

@@ -278,39 +278,72 @@ int rsq_table_create_device(rsq_ctx* ctx, const rsq_table_desc* desc, rsq_table*
 
 int rsq_table_from_rowstore(rsq_ctx* ctx, const rsq_table_desc* schema, const uint8_t* const* blocks,
                             const size_t* content_size, int32_t n_blocks, rsq_table** out) {
+    return rsq_table_from_rowstore_ex(ctx, schema, blocks, content_size, n_blocks, nullptr, nullptr, out);
+}
+
+int rsq_table_from_rowstore_ex(rsq_ctx* ctx, const rsq_table_desc* schema, const uint8_t* const* blocks, const size_t* content_size,
+                               int32_t n_blocks, const rsq_rowstore_options* options, rsq_rowstore_report* report, rsq_table** out) {
     if (!ctx || !schema || !out || n_blocks < 0) return RSQ_ERR_INVALID;
     if (schema->n_cols <= 0 || (n_blocks > 0 && (!blocks || !content_size))) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
-        // transpose packed ReSQL tuples (strings by value, schema.h:76-106 offsets) into columns on the host,
-        // then upload: the bridge is ingest, not the hot path
-        std::vector<Type> types; std::vector<int> offs; int ts = 0;
-        for (int i = 0; i < schema->n_cols; i++) {
-            Type t = Type::fromC(schema->cols[i].type);
-            types.push_back(t); offs.push_back(ts); ts += sizeInTuple(t, true);
+        Context& cx = *C(ctx);
+        rsq_rowstore_options opt{};
+        if (options) {
+            if (options->struct_size < 8 || options->struct_size > 4096) failInvalid("rsq_rowstore_options.struct_size is " + std::to_string(options->struct_size) + ": set it to sizeof(rsq_rowstore_options)");
+            memcpy(&opt, options, std::min<size_t>(options->struct_size, sizeof opt));
         }
-        int64_t n = 0;
-        for (int b = 0; b < n_blocks; b++) n += (int64_t)(content_size[b] / (size_t)ts);
-        std::vector<std::vector<uint8_t>> cols((size_t)schema->n_cols);
-        for (int i = 0; i < schema->n_cols; i++) cols[(size_t)i].assign((size_t)n * (size_t)columnWidth(types[(size_t)i]), 0);
-        int64_t r = 0;
-        for (int b = 0; b < n_blocks; b++) {
-            size_t cnt = content_size[b] / (size_t)ts;
-            for (size_t k = 0; k < cnt; k++, r++) {
-                const uint8_t* tup = blocks[b] + k * (size_t)ts;
-                for (int i = 0; i < schema->n_cols; i++) {
-                    int w = columnWidth(types[(size_t)i]);
-                    uint8_t* dst = &cols[(size_t)i][(size_t)r * (size_t)w];
-                    if (types[(size_t)i].tag == RSQ_CHAR || types[(size_t)i].tag == RSQ_VARCHAR) {
-                        const uint8_t* s = tup + offs[(size_t)i];
-                        for (int c = 0; c < w && s[c]; c++) dst[c] = s[c];
-                    } else memcpy(dst, tup + offs[(size_t)i], (size_t)w);
-                }
-            }
+        if (report && (report->struct_size < 8 || report->struct_size > 4096)) failInvalid("rsq_rowstore_report.struct_size is " + std::to_string(report->struct_size) + ": set it to sizeof(rsq_rowstore_report)");
+        if (opt.mode < 0 || opt.mode > 2) failInvalid("rsq_rowstore_options.mode must be 0 (the context's rowstore_bridge setting), 1 (host) or 2 (device)");
+        if (opt.chunk_bytes < 0 || opt.chunk_bytes > ((int64_t)1 << 30)) failInvalid("rsq_rowstore_options.chunk_bytes is " + std::to_string(opt.chunk_bytes) + " (0: 64 MiB; at most 1 GiB)");
+        const bool device = opt.mode == 2 || (opt.mode == 0 && cx.rowstoreBridge == 1);
+        std::vector<Type> types;
+        for (int i = 0; i < schema->n_cols; i++) types.push_back(Type::fromC(schema->cols[i].type));
+        rsq_rowstore_report rep{};
+        const auto started = std::chrono::steady_clock::now();
+        auto ms = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+        // (a type no column holds raises here, on either path and in front of every allocation, what it always raised)
+        const RowstoreLayout layout = rowstoreLayout(types);
+        int64_t n = rowstoreRows(content_size, n_blocks, layout.tupleSize);
+        std::unique_ptr<Table> t;
+        if (device) t = rowstoreToDevice(cx, *schema, types, layout, blocks, content_size, n_blocks, n, opt.chunk_bytes, rep);
+        if (t) {
+            const auto t0 = std::chrono::steady_clock::now();
+            computeColumnStats(cx, *t);
+            rep.stats_ms = ms(t0);
         }
-        std::vector<rsq_column> cd((size_t)schema->n_cols);
-        for (int i = 0; i < schema->n_cols; i++) { cd[(size_t)i] = schema->cols[i]; cd[(size_t)i].data = cols[(size_t)i].data(); }
-        rsq_table_desc d = *schema; d.n_rows = n; d.cols = cd.data();
-        *out = reinterpret_cast<rsq_table*>(makeTable(*C(ctx), d, false));
+        if (!t) {
+            // the host path: packed ReSQL tuples (strings by value, schema.h:76-106 offsets) transposed into columns by one host thread
+            // (rowstore.cpp), then uploaded - all of it, also where the device path gave up (its reason stays in the report)
+            const int32_t why = rep.fallback_reason;
+            rep = rsq_rowstore_report{};
+            rep.fallback_reason = why;
+            std::vector<std::vector<uint8_t>> cols;
+            auto t0 = std::chrono::steady_clock::now();
+            transposeRowstoreHost(types, blocks, content_size, n_blocks, cols, n);
+            rep.transpose_ms = ms(t0);
+            std::vector<rsq_column> cd((size_t)schema->n_cols);
+            for (int i = 0; i < schema->n_cols; i++) { cd[(size_t)i] = schema->cols[i]; cd[(size_t)i].data = cols[(size_t)i].data(); }
+            rsq_table_desc d = *schema; d.n_rows = n; d.cols = cd.data();
+            t0 = std::chrono::steady_clock::now();
+            t.reset(makeTable(cx, d, false, &rep.stats_ms));
+            rep.copy_ms = ms(t0) - rep.stats_ms;
+        }
+        rep.rows = n; rep.tuple_bytes = n * (int64_t)layout.tupleSize;
+        rep.total_ms = ms(started);
+        if (report) {
+            const uint32_t have = report->struct_size;
+            rep.struct_size = have;
+            memcpy(report, &rep, std::min<size_t>(have, sizeof rep));
+        }
+        *out = reinterpret_cast<rsq_table*>(t.release());
+    });
+}
+
+int rsq_ctx_set_rowstore_bridge(rsq_ctx* ctx, int32_t where) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid("rowstore_bridge is " + std::to_string(where) + " (0: row stores are transposed on the host, 1: on the device)");
+        C(ctx)->rowstoreBridge = where;
     });
 }
 

@@ -20,6 +20,7 @@
 #include "hostref.h"
 #include "mempool.h"
 #include "resql_hip.h"
+#include "rowstore.h"
 #include "switches.h"
 #include "tbl.h"
 
@@ -221,6 +222,7 @@ struct Context {
     // shard scanned for a key whose dictionary all shards share (TableColumn::dictShared, RSQ_ENGINE_DICT_MULTI)
     bool shardCompile = false;
     int32_t resultText = 0;                    // rsq_ctx_set_result_text: 0 results become text on the host, 1 on the device (result_text.hip)
+    int32_t rowstoreBridge = 0;                // rsq_ctx_set_rowstore_bridge: 0 row stores are transposed on the host, 1 on the device (rowstore_device.hip)
 };
 
 rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // api.cpp: the host's struct (struct_size bytes), validated
@@ -374,6 +376,14 @@ void replayEmissionOrderDevice(Context& ctx, const uint64_t* hashes, uint64_t n,
 // malformed line is the host path's RSQ_ERR_INVALID.  rep's rows / text_bytes / phase times are filled as far as the load got.
 std::unique_ptr<Table> loadTblDevice(Context& ctx, const rsq_table_desc& schema, const std::vector<Type>& types, const std::string& path,
                                      char terminator, int64_t chunkBytes, int64_t maxDeviceBytes, rsq_tbl_load_report& rep);
+
+// rowstore.cpp: packed ReSQL tuples -> columns on the host (rowstore.h: transposeRowstoreHost and the rule of a cell)
+// rowstore_device.hip: the same transposition on the device (rsq_ctx_set_rowstore_bridge, rsq_table_from_rowstore_ex).  Returns the table -
+// columns filled, no statistics yet - with rep.path = 1, or null with rep.fallback_reason set (never an error: the caller takes the host
+// path).  nRows: what rowstoreRows says of the blocks.  rep's chunks and phase times are filled.
+std::unique_ptr<Table> rowstoreToDevice(Context& ctx, const rsq_table_desc& schema, const std::vector<Type>& types, const RowstoreLayout& layout,
+                                        const uint8_t* const* blocks, const size_t* contentSize, int32_t nBlocks, int64_t nRows, int64_t chunkBytes,
+                                        rsq_rowstore_report& rep);
 
 // ---- query ------------------------------------------------------------------------------------
 struct Query;

@@ -65,6 +65,25 @@ TBL_HOST, TBL_DEVICE = 1, 2      # rsq_tbl_load_options.mode (0: the context's t
 TBL_FALLBACK_NONE, TBL_FALLBACK_NO_DEVICE, TBL_FALLBACK_COLUMNS, TBL_FALLBACK_TERMINATOR, TBL_FALLBACK_DOES_NOT_FIT, TBL_FALLBACK_ODD_LINES = range(6)
 
 
+class rsq_rowstore_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_bytes", C.c_int64)]
+
+
+class rsq_rowstore_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("tuple_bytes", C.c_int64), ("chunks", C.c_int64),
+                ("stage_ms", C.c_double), ("copy_ms", C.c_double), ("kernel_ms", C.c_double), ("transpose_ms", C.c_double),
+                ("stats_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+ROWSTORE_HOST, ROWSTORE_DEVICE = 1, 2      # rsq_rowstore_options.mode (0: the context's set_rowstore_bridge)
+# rsq_rowstore_fallback: why a bridge that asked for the device transposed on the host
+ROWSTORE_FALLBACK_NONE, ROWSTORE_FALLBACK_NO_DEVICE, ROWSTORE_FALLBACK_COLUMNS = range(3)
+
+
 class rsq_result_text_options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_rows", C.c_int64), ("max_device_bytes", C.c_int64)]
 
@@ -139,6 +158,9 @@ def lib():
         L.rsq_table_create_device.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.POINTER(vp)]
         L.rsq_table_from_rowstore.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), i32, C.POINTER(vp)]
+        L.rsq_table_from_rowstore_ex.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), i32,
+                                                 C.POINTER(rsq_rowstore_options), C.POINTER(rsq_rowstore_report), C.POINTER(vp)]
+        L.rsq_ctx_set_rowstore_bridge.argtypes = [vp, i32]
         L.rsq_table_generate.argtypes = [vp, i32, i64, i64, C.c_double, i64, C.c_uint64, C.POINTER(vp)]
         L.rsq_table_load_tbl.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.c_char_p, C.c_char, i32, C.POINTER(vp)]
         L.rsq_table_load_tbl_ex.argtypes = [vp, C.POINTER(P.rsq_table_desc), C.c_char_p, C.c_char, i32, C.POINTER(rsq_tbl_load_options),
@@ -248,7 +270,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "rsq_ctx_create", "rsq_ctx_destroy", "rsq_last_error", "rsq_table_create", "rsq_table_create_device",
-    "rsq_table_from_rowstore", "rsq_table_load_tbl", "rsq_table_load_tbl_ex", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
+    "rsq_table_from_rowstore", "rsq_table_from_rowstore_ex", "rsq_ctx_set_rowstore_bridge", "rsq_table_load_tbl", "rsq_table_load_tbl_ex", "rsq_table_generate", "rsq_table_rows", "rsq_table_set_first_row", "rsq_table_refresh_stats", "rsq_table_append", "rsq_ctx_memory_stats", "rsq_table_read_column", "rsq_table_read_image",
     "rsq_table_stats_bytes", "rsq_table_stats_export", "rsq_table_unify_shard_stats", "rsq_table_unify_shard_dictionaries", "rsq_table_time_dictionary_pass", "rsq_table_total_rows",
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
@@ -414,6 +436,11 @@ class Context:
         (rsq_ctx_set_result_text)"""
         self._check(self._L.rsq_ctx_set_result_text(self.h, where))
 
+    def set_rowstore_bridge(self, where: int):
+        """where row stores are transposed under mode 0 (and so by rsq_table_from_rowstore): 0 on the host (the default), 1 on the
+        device (rsq_ctx_set_rowstore_bridge)"""
+        self._check(self._L.rsq_ctx_set_rowstore_bridge(self.h, where))
+
     def set_stream(self, hip_stream: Optional[int]):
         """launch on the caller's HIP stream (an integer handle, 0 = the null stream; e.g.
         torch.cuda.current_stream().cuda_stream), or None to go back to the context's own stream"""
@@ -475,6 +502,24 @@ class Context:
                                                   C.byref(h)))
         t = DeviceTable(self, h, schema.name, {c.name: c.type.width for c in schema.columns})
         t.load_report = rep.as_dict()
+        return t
+
+    def from_rowstore(self, schema: P.Table, blocks: Sequence, mode: int = 0, chunk_bytes: int = 0) -> "DeviceTable":
+        """a table with `schema`'s column names and types out of a ReSQL row store (rsq_table_from_rowstore_ex): `blocks` are byte
+        buffers (bytes, memoryviews, uint8 arrays - views at any offset) of packed tuples.  mode 0: transposed where the context's
+        set_rowstore_bridge says, ROWSTORE_HOST, ROWSTORE_DEVICE; the table's bridge_report says which path ran, why, and its phases"""
+        keep: list = []
+        bare = P.Table(schema.name, [P.Column(c.name, c.type) for c in schema.columns], 0)
+        d = bare.to_c(keep)
+        views = [np.frombuffer(b, dtype=np.uint8) for b in blocks]
+        ptrs = (C.c_void_p * max(1, len(views)))(*[v.ctypes.data for v in views])
+        sizes = (C.c_size_t * max(1, len(views)))(*[v.size for v in views])
+        h = C.c_void_p()
+        opt = rsq_rowstore_options(C.sizeof(rsq_rowstore_options), mode, chunk_bytes)
+        rep = rsq_rowstore_report(C.sizeof(rsq_rowstore_report))
+        self._check(self._L.rsq_table_from_rowstore_ex(self.h, C.byref(d), ptrs, sizes, len(views), C.byref(opt), C.byref(rep), C.byref(h)))
+        t = DeviceTable(self, h, schema.name, {c.name: c.type.width for c in schema.columns})
+        t.bridge_report = rep.as_dict()
         return t
 
     def generate(self, kind: int, n_rows: int, sf: float, row0: int = 0, param: int = 0,
@@ -572,6 +617,7 @@ class DeviceTable:
         self.ctx, self.h, self.name = ctx, h, name
         self.widths = dict(widths or {})          # bytes per row of the columns, by name, where the schema came through Python (read_image)
         self.load_report: Optional[dict] = None   # of Context.load_tbl
+        self.bridge_report: Optional[dict] = None   # of Context.from_rowstore
         ctx._adopt(self)
 
     @property
