@@ -426,6 +426,14 @@ int  rsq_query_result_write(rsq_query* q, const char* path, const rsq_result_tex
 /* Where mode 0 and the statement loop's `tofile` write their text: 0 host (the default), 1 device; else RSQ_ERR_INVALID naming
  * "result_text".  A setter, not a field: rsq_config keeps its size. */
 int  rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where);
+/* The register aggregation's second form.  A register aggregation with 32-bit partial sums that runs four waves per SIMD (TPC-H Q1) has a
+ * second form of its kernel, in which every row adds its inputs into its lane's words of the workgroup's LDS image.  mode -1 (the
+ * default): a statement runs each form in two timed executions and keeps the second only where its kernel time is clearly the better
+ * one; 0: statements compiled from now on get no second form (the kernel text of earlier versions); 1: they run it in every launch
+ * that fits the fields of its shared words.  The answers are the same bit for bit.  Read when a statement is compiled (under 0 it
+ * gets no second form at all) and at every launch: 0 or 1 set later holds from the next execution on, for compiled statements too
+ * (0 then runs form 0 of the two-form text, whatever the statement had measured or the plan memo remembered). */
+int  rsq_ctx_set_row_cells(rsq_ctx* ctx, int32_t mode);
 /* The slot order of the reference's aggregation hash table (allocateHashTable / ht_put / growHashTable, src/qlib/hash.h:225-287,
  * 330-419) after inserting n groups with the given Values::hash values in this order into a table allocated for min_size
  * entries: out[k] = index of the group in the k-th occupied slot.  parallel != 0 takes the cluster-parallel replay the engine's

@@ -669,6 +669,14 @@ int rsq_query_result_write(rsq_query* q, const char* path, const rsq_result_text
     });
 }
 
+int rsq_ctx_set_row_cells(rsq_ctx* ctx, int32_t mode) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (mode < -1 || mode > 1) failInvalid("row_cells is " + std::to_string(mode) + " (-1: chosen by the executions' kernel times, 0: no second form, 1: in every launch that fits it)");
+        C(ctx)->rowCellsMode = mode;
+    });
+}
+
 int rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where) {
     if (!ctx) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
@@ -1083,6 +1091,7 @@ std::string reportText(const rsq_db& db, rsq_query* q, const rsq_report& r) {
         snprintf(b, sizeof b, "compile: %.3f ms\n", r.compilation_time_ms); o += b;
         snprintf(b, sizeof b, "execute: %.3f ms\n", r.execution_time_ms); o += b;
         snprintf(b, sizeof b, "device:  %.3f ms, %llu bytes scanned, %.1f GB/s\n", r.kernel_time_ms, (unsigned long long)r.bytes_read, r.hbm_gbps); o += b;
+        if (q) o += rowCellsLine(*QH(q)->q);
     }
     return o;
 }

@@ -1,6 +1,7 @@
 // codegen_agg.cpp - the aggregation sinks: dense group ids in registers / LDS / HBM (plain, staged, partitioned), aggregation at the join
 // entry, hash aggregation with its LDS front table.  Reference: src/operators/aggregation.h.
 #include "codegen_internal.h"
+#include "row_cells.h"
 
 namespace rsq {
 namespace cg {
@@ -945,25 +946,40 @@ void Walker::emitDenseAggregation(OpNode* o) {
         // the kernel at two waves per SIMD.  All waves of the workgroup add into the same 64 words of a cell, hence the LDS
         // atomic; the image is filled with the identities, behind a barrier, in front of the tile loop.
         std::vector<char> part32((size_t)W, 0);
+        std::vector<rowcells::Accumulator> envelopes((size_t)W, rowcells::Accumulator{false, false, -1});
         if (sw::flag<sw::RSQ_NARROW_SCANS>() && !compacted && pipe.src && !pipe.src->derived) {
             for (int w = 1; w < W; w++) {
                 const Accum& ac = q.accums[(size_t)w];
                 if (ac.merge != 0) continue;
                 int bits = -1;
+                bool negative = false;
                 if (ac.input == "((i64)1)") bits = 1;
                 else if (ac.input.compare(0, 2, "v_") == 0 && ac.input.find_first_not_of("0123456789", 2) == std::string::npos && ac.input.size() > 2) {
                     const int k = atoi(ac.input.c_str() + 2);
                     if (k >= 0 && k < (int)pipe.cols.size() && !colIsString[(size_t)k]) {
                         bool neg = false;
                         if (!envelopeOf(pipe.src->cols[(size_t)pipe.cols[(size_t)k]], neg, bits)) bits = -1;
+                        negative = neg;
                     }
                 }
                 if (bits >= 0 && bits <= 24) part32[(size_t)w] = 1;
+                envelopes[(size_t)w] = rowcells::Accumulator{part32[(size_t)w] != 0, negative, bits};
             }
         }
         // accumulators in VGPRs, branch-free per-group update.  (An `if (gid == g) acc_g += x` chain gets its
         // common tail sunk by the compiler into one store through a selected pointer, which forces every
         // accumulator into scratch.)
+        // The second form of this aggregation (RSQ_ROW_CELLS 1, row_cells.h): no accumulator registers at all - a row adds its inputs into
+        // its lane's words of the image, at cell block * D + gid, one LDS atomic per word.  Form 0 runs a 7-VALU block per distinct group
+        // among a wave's 64 rows and holds a register per group and accumulator (TPC-H Q1: 54 of 104 VGPRs) only to merge them into this
+        // very image in the end; form 1 issues five LDS operations a row instead and fits 40 VGPRs.  Written between markers here: which
+        // statements get it is known in finishPipeline (the ones held to four waves per SIMD), which turns the markers into #if lines or
+        // drops them with the text of form 1.
+        bool anyPartial = false;
+        for (int w = 1; w < W; w++) anyPartial = anyPartial || part32[(size_t)w];
+        rowCells = typed && anyPartial && q.ctx.rowCellsMode != 0;
+        const std::vector<rowcells::Field> fields = rowcells::assignFields(envelopes);
+        if (rowCells) stateDecl += RC_IFNOT;
         for (int w = 0; w < W; w++)
             for (int64_t g = 0; g < D && !part32[(size_t)w]; g++)
                 stateDecl += "    i64 acc_" + std::to_string(w) + "_" + std::to_string((long long)g) + " = (i64)" + identityOf(q.accums[(size_t)w].merge) + ";\n";
@@ -971,6 +987,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
         // The first row of a group, accumulator 0, is min(row) with row = a.row0 + lr: a 64-bit compare and two selects per update.
         // Below 2^32 - 1 rows the offset lr alone is tracked, as a u32 with the identity 0xffffffff and one unsigned minimum per
         // update, and becomes the i64 cell in front of the epilogue; from s_lane on nothing changes.
+        if (rowCells) ep << RC_IFNOT;
         if (fr32)
             for (int64_t g = 0; g < D; g++) {
                 const std::string G = std::to_string((long long)g);
@@ -991,8 +1008,10 @@ void Walker::emitDenseAggregation(OpNode* o) {
         if (!fold.empty()) {
             stateDecl += "    int fold_n = 0;\n";
             foldTile = "            if (++st.fold_n == 32) { st.fold_n = 0; " + fold + "}\n";
+            if (rowCells) foldTile = RC_IFNOT + foldTile + RC_END;
             ep << "    " << fold << "\n";
         }
+        if (rowCells) { ep << RC_END; stateDecl += std::string(RC_ELSE) + "    u64* cells;      // the lane's word of cell 0 of the image\n" + RC_END; }
         auto addLine = [&](const std::string& acc, int w, const std::string& in, const std::string& sel) {
             if (part32[(size_t)w]) {
                 const std::string p = "st.p32_" + acc.substr(7);
@@ -1001,6 +1020,7 @@ void Walker::emitDenseAggregation(OpNode* o) {
             (void)in;
         };
         const bool branchy = (D > 1 ? 1 : 0) == 1;
+        if (rowCells) body += RC_IFNOT;
         for (int64_t g = 0; g < D; g++) {
             if (branchy) {
                 // EXEC-masked update of one group's accumulators (2 VALU per 64-bit add instead of the
@@ -1032,6 +1052,28 @@ void Walker::emitDenseAggregation(OpNode* o) {
             }
             closeScope();
         }
+        if (rowCells) {
+            body += RC_ELSE;
+            line("u64* cell = st.cells + gid * 64;");
+            for (int w = 0; w < W; w++) {
+                const std::string at = "cell + " + std::to_string((long long)(q.accumSlot[(size_t)w] * D * 64));
+                const int m = q.accums[(size_t)w].merge;
+                if (w == 0 && fr32) line("atomicMin(reinterpret_cast<u32*>(" + at + "), (u32)lr);");
+                else if (fields[(size_t)w].host == w) {
+                    std::string word;
+                    for (int v = w; v < W; v++)
+                        if (fields[(size_t)v].host == w)
+                            word += (word.empty() ? "" : " | ") + std::string("(u64)(u32)") + inOf(v) + (fields[(size_t)v].shift ? " << " + std::to_string(fields[(size_t)v].shift) : std::string());
+                    line("rsq::lds_merge<0>(" + at + ", " + word + ");");
+                }
+                else if (fields[(size_t)w].host >= 0) continue;      // its field of another accumulator's word
+                else if (m == 0) line("rsq::lds_merge<0>(" + at + ", (u64)(i64)" + inOf(w) + ");");
+                else line("rsq::lds_merge<" + std::to_string(m) + ">(" + at + ", (u64)" + inOf(w) + ");");
+            }
+            body += RC_END;
+            // (the engine asks row_cells.h launchFits with these before every launch of form 1)
+            for (int v = 0; v < W; v++) if (fields[(size_t)v].host >= 0) pipe.rowCellsEnvelopes.push_back(envelopes[(size_t)v].envelopeBits);
+        }
         const bool dbgTail = sw::num<sw::RSQ_DEBUG_TAIL>() != 0;      // (measurement only: device timestamps of the epilogue's stages)
         auto stamp = [&](int k) { if (dbgTail) ep << "    if (a.dbg && threadIdx.x == 0) a.dbg[(u64)blockIdx.x * 8 + " << k << "] = (u64)wall_clock64();\n"; };
         if (dbgTail) { addArg("dbg", "u64*", 0); prologue += "    if (a.dbg && threadIdx.x == 0) a.dbg[(u64)blockIdx.x * 8 + 0] = (u64)wall_clock64();\n"; }
@@ -1051,12 +1093,30 @@ void Walker::emitDenseAggregation(OpNode* o) {
             image << "    __syncthreads();\n";
             if (fold.empty()) ep << image.str();
             else prologue += image.str();
+            if (rowCells) prologue += std::string(RC_IF) + "    st.cells = s_lane + (threadIdx.x & 63);\n" + RC_END;
+            if (rowCells) ep << RC_IFNOT;
             for (int w = 0; w < W; w++)
                 for (int64_t g = 0; g < D && !part32[(size_t)w]; g++)
                     ep << "    rsq::lds_merge<" << q.accums[(size_t)w].merge << ">(&s_lane[" << (q.accumSlot[(size_t)w] * D + g) * 64 << " + (threadIdx.x & 63)], (u64)st.acc_" << w << "_" << g << ");\n";
+            if (rowCells) ep << RC_END;
             ep << "    __syncthreads();\n";
             ep << "    for (int c = threadIdx.x >> 6; c < " << cells << "; c += blockDim.x >> 6) {\n";
-            ep << "        const int blk = c / " << D << ";\n        const u64 v = s_lane[c * 64 + (threadIdx.x & 63)];\n";
+            ep << "        const int blk = c / " << D << ";\n";
+            if (rowCells) ep << RC_IFNOT;
+            ep << "        const u64 v = s_lane[c * 64 + (threadIdx.x & 63)];\n";
+            if (rowCells) {
+                // what a lane's word holds becomes the cell's value before the lanes meet: the u32 offset of the first row the i64 row (or
+                // the identity), a field of a shared word the sum it counted
+                ep << RC_ELSE << "        u64 v = s_lane[c * 64 + (threadIdx.x & 63)];\n";
+                if (fr32) ep << "        if (c < " << D << ") v = (u32)v == 0xffffffffu ? " << identityOf(2) << " : (u64)(a.row0 + (i64)(u32)v);\n";
+                for (int w = 1; w < W; w++) {
+                    if (fields[(size_t)w].host < 0) continue;
+                    const int64_t lo = q.accumSlot[(size_t)w] * D, back = (q.accumSlot[(size_t)w] - q.accumSlot[(size_t)fields[(size_t)w].host]) * D;
+                    ep << "        if (c >= " << lo << " && c < " << lo + D << ") v = (s_lane[(c - " << back << ") * 64 + (threadIdx.x & 63)] >> " << fields[(size_t)w].shift
+                       << ") & " << (unsigned long long)rowcells::kFieldMask << "ull;\n";
+                }
+                ep << RC_END;
+            }
             ep << "        const u64 r = blk < " << q.nMinBlocks << " ? rsq::wave_reduce_to_lane63<2>(v) : blk < " << (q.nMinBlocks + q.nMaxBlocks)
                << " ? rsq::wave_reduce_to_lane63<3>(v) : rsq::wave_reduce_to_lane63<0>(v);\n";
             ep << "        if ((threadIdx.x & 63) == 63) s_acc[c] = r;\n    }\n";

@@ -449,6 +449,15 @@ struct Walker {
     // as row-function parameters.
     std::string foldTile;                                  // code behind every tile of the tile loops: the periodic fold of 32-bit partial sums (codegen_agg.cpp)
     int accRegs = 0;                                       // VGPRs the register aggregation's State holds per lane: 2 per i64 accumulator, 1 per partial sum or u32 first row
+    // The register aggregation's second form (codegen_agg.cpp, row_cells.h): its text stands between marker lines in stateDecl, prologue, body,
+    // foldTile and epilogue until finishPipeline knows whether the statement gets it.  IFNOT ... [ELSE ...] END and IF ... END; no nesting.
+    // Whoever transforms one of those five buffers between emitDenseAggregation and resolveRowCells (finishPipeline, right behind the
+    // fourWaves decision) must leave the marker lines whole and in order: typeScanColumns, the only one today, prepends to body.  The
+    // decision cannot simply move in front of emitDenseAggregation: it reads accRegs and foldTile, which that function makes.
+    bool rowCells = false;
+    static constexpr const char* RC_IFNOT = "\x01rc-ifnot\n"; static constexpr const char* RC_IF = "\x01rc-if\n";
+    static constexpr const char* RC_ELSE = "\x01rc-else\n"; static constexpr const char* RC_END = "\x01rc-end\n";
+    static void resolveRowCells(std::string& text, bool keep);
     std::string postTile;                                  // code behind the two row_fn calls of a tile in the tile loops ($TILE = the tile's number; wave-uniform)
     std::map<int, int> strStaged;                          // scanned column -> byte offset of its tile in the wave's LDS region
     int strStagedBytes = 0;                                // bytes of that region (128 x the staged widths)

@@ -55,6 +55,24 @@ void Walker::emitLateLoads(std::ostringstream& s, const std::string& tile, int u
     s << "            }\n        }\n";
 }
 
+// the marker lines of the register aggregation's second form (codegen_internal.h): preprocessor lines, or form 0's text alone
+void Walker::resolveRowCells(std::string& text, bool keep) {
+    std::string out;
+    bool drop = false;
+    for (size_t at = 0; at < text.size();) {
+        size_t end = text.find('\n', at);
+        end = end == std::string::npos ? text.size() : end + 1;
+        const std::string ln = text.substr(at, end - at);
+        at = end;
+        if (ln == RC_IFNOT) { if (keep) out += "#if !RSQ_ROW_CELLS\n"; }
+        else if (ln == RC_IF) { if (keep) out += "#if RSQ_ROW_CELLS\n"; else drop = true; }
+        else if (ln == RC_ELSE) { if (keep) out += "#else\n"; else drop = true; }
+        else if (ln == RC_END) { if (keep) out += "#endif\n"; drop = false; }
+        else if (!drop) out += ln;
+    }
+    text = out;
+}
+
 void Walker::finishPipeline() {
     while (indent > 1) closeScope();
     addArg("n_rows", "i64", (uint64_t)pipe.src->nRows);
@@ -169,6 +187,11 @@ void Walker::finishPipeline() {
         fourWaves = held(u) <= fourWaveRegs;
         if (fourWaves) { pipe.unroll = u; pipe.gridPerCU = 4; }
     }
+    // ... and those statements carry the second form, rows into per-lane LDS cells, under #if RSQ_ROW_CELLS: same tiles in flight, same
+    // grid, same launch bound (it allocates 40 VGPRs where form 0 takes 104; docs/KERNELS.md has the other geometries measured)
+    rowCells = rowCells && fourWaves && pipe.sink == SinkKind::AGGREGATE;
+    for (std::string* text : {&stateDecl, &prologue, &body, &foldTile, &epilogue}) resolveRowCells(*text, rowCells);
+    if (!rowCells) pipe.rowCellsEnvelopes.clear();
     const int U = pipe.unroll;
     if (strStagedBytes > 0) {
         pipe.extraLdsBytes += (pipe.blockThreads / 64) * strStagedBytes;
@@ -602,6 +625,12 @@ void Walker::finishPipeline() {
         pipe.sourceFlat = "#define RSQ_OUT_STRIDE 1\n" + pipe.source;
         pipe.source = "#define RSQ_OUT_STRIDE " + std::to_string(q.aggPad) + "\n" + pipe.source;
     }
+    if (rowCells) {           // the second form of the register aggregation: same texts, RSQ_ROW_CELLS 1 (the engine picks per execution)
+        const std::string guard = "#ifndef RSQ_ROW_CELLS\n#define RSQ_ROW_CELLS 0\n#endif\n";
+        pipe.sourceCells = "#define RSQ_ROW_CELLS 1\n" + guard + pipe.source;
+        pipe.source = guard + pipe.source;
+        if (!pipe.sourceFlat.empty()) { pipe.sourceFlatCells = "#define RSQ_ROW_CELLS 1\n" + guard + pipe.sourceFlat; pipe.sourceFlat = guard + pipe.sourceFlat; }
+    }
     if (pipe.partitioned) {   // three code objects from one source (see emitDenseAggregation)
         // count and scatter run as ONE 1024-thread workgroup per CU (see the note at the record stores)
         pipe.sourcePartCount = "#define RSQ_AGG_VARIANT 1\n#define RSQ_BLOCK_THREADS 1024\n" + pipe.source;
@@ -630,6 +659,7 @@ void Walker::finishPipeline() {
         snprintf(buf, sizeof buf, " [late loads: ~%.1f %% of the rows expected to pass the leading selection]", leadPass * 100.0);
         ex += buf;
     }
+    if (rowCells) ex += " [second form: rows into per-lane LDS cells, chosen by the executions' kernel times]";
     if (pipe.staged) ex += " [partitioned as packed " + std::to_string(8 * pipe.stagedRecWords) + "-byte records staged through LDS rings]";
     pipe.explain = ex;
     q.pipelines.push_back(pipe);

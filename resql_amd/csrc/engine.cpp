@@ -253,6 +253,8 @@ static std::vector<std::string> kernelSources(const Query& q, bool quick = false
         if (p.partitioned) { v.push_back(T(p.sourcePartCount)); v.push_back(T(p.sourcePartScatter)); v.push_back(p.sourcePartAgg); }
         if (p.staged) { v.push_back(T(p.sourceStagedScatter)); v.push_back(p.sourceStagedAgg); }
         v.push_back(T(p.source));
+        if (!p.sourceCells.empty()) v.push_back(T(p.sourceCells));              // (the second form of a register aggregation: compiled with the first, chosen per execution)
+        if (!p.sourceFlatCells.empty()) v.push_back(T(p.sourceFlatCells));
         if (!p.sourceLazy.empty()) v.push_back(T(p.sourceLazy));      // (chosen at run time; compiled with the others so that choosing it never blocks an execution)
         // ... and so is the 64-slot front table of a hash aggregation that turns out to have a handful of groups (engine_pipelines.cpp
         // fewGroupsKernel): compiled when first wanted it cost TPC-H Q12's second query 0.57 s of hiprtc in the middle of an execution
@@ -285,6 +287,8 @@ static void resolveKernels(Query& q, bool quick = false) {
             p.kernelStagedAgg = &ctx.getKernel(p.sourceStagedAgg, "rsq_staged_agg");
         }
         p.kernel = &ctx.getKernel(T(p.source), p.entry);
+        if (!p.sourceCells.empty()) p.kernelCells = &ctx.getKernel(T(p.sourceCells), p.entry);
+        if (!p.sourceFlatCells.empty()) p.kernelFlatCells = &ctx.getKernel(T(p.sourceFlatCells), p.entry);
         // both forms are loaded now: the first execution that chooses the late-load form must not read and load a code object
         // (TPC-H Q3 at SF10: 0.86 ms for the execution that first chose it, 0.32 ms after)
         if (!p.sourceLazy.empty()) p.kernelLazy = &ctx.getKernel(T(p.sourceLazy), p.entry);
@@ -330,6 +334,7 @@ static void applyPlanMemo(Query& q) {
     for (size_t i = 0; i < q.pipelines.size(); i++) {
         Pipeline& p = q.pipelines[i];
         p.stage2Rows = m.pipes[i].stage2Rows;
+        if (!p.sourceCells.empty()) p.cellsChoice = m.pipes[i].cellsChoice;
         p.stagedExact = m.pipes[i].stagedExact; p.stagedCaps = m.pipes[i].stagedCaps; p.stagedCapsRows = m.pipes[i].stagedCapsRows;
         if (p.sink != SinkKind::BUILD) continue;
         HashTable& h = *q.hashTables[(size_t)p.buildTable];
@@ -398,6 +403,7 @@ static void rememberPlan(Query& q) {
     for (size_t i = 0; i < q.pipelines.size(); i++) {
         const Pipeline& p = q.pipelines[i];
         Context::PlanMemo::Pipe& mp = m.pipes[i];
+        mp.cellsChoice = p.cellsChoice;
         mp.stage2Rows = p.stage2Rows; mp.stagedExact = p.stagedExact; mp.stagedCapsRows = p.stagedCapsRows;
         if (mp.stagedCaps != p.stagedCaps) mp.stagedCaps = p.stagedCaps;
     }
@@ -728,6 +734,7 @@ void resolveKernelTime(Query& q) {
         float ems = 0;
         RSQ_HIP(hipEventElapsedTime(&ems, e.first, e.second));
         q.report.kernel_time_ms = ems; q.kernelTimeSumMs += ems; q.kernelTimeLaunches++;
+        if (!q.ringForms.empty()) { noteRowCellsTime(q, q.ringForms.front(), ems); q.ringForms.pop_front(); }
         q.report.hbm_gbps = ems > 0 ? (double)q.report.bytes_read / (ems * 1e-3) / 1e9 : 0;
     }
     if (!q.kernelTimePending || q.pendingAsync) return;
@@ -737,6 +744,7 @@ void resolveKernelTime(Query& q) {
     float ms = 0;
     RSQ_HIP(hipEventElapsedTime(&ms, q.gev0, q.gev1));
     q.report.kernel_time_ms = ms; q.kernelTimeSumMs += ms; q.kernelTimeLaunches++;
+    noteRowCellsTime(q, q.pairForm, ms); q.pairForm = -1;
     q.report.hbm_gbps = ms > 0 ? (double)q.report.bytes_read / (ms * 1e-3) / 1e9 : 0;
 }
 
@@ -1030,12 +1038,18 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         q.finErr = q.dFinHost + q.pinnedWords;
         if (!q.gev0) { q.gev0 = ctx.takeEvent(); q.gev1 = ctx.takeEvent(); }
         hipEvent_t evA = q.gev0, evB = q.gev1;
+        prepareRowCellsForm(q, p);                             // (may read the earlier steps' events: before this step's pair is picked and recorded)
         if (ringEvents) { auto& e = q.evRing[q.evTail % q.evRing.size()]; evA = e.first; evB = e.second; }
         // two event records around the launch.  (An extended launch that takes the events itself costs the host 3 us more per step
         // and the tail another 1.5: measured 16 us of step overhead against 11.5.)
         RSQ_HIP(hipEventRecord(evA, ctx.stream));
         launchPipelineKernel(q, p, *p.kernel, -1);
         RSQ_HIP(hipEventRecord(evB, ctx.stream));
+        {
+            const int timedForm = p.measuring ? p.lastForm : -1;
+            if (p.measuring) { p.cellsLaunched[p.lastForm]++; p.measuring = false; p.measureForm = 0; }
+            if (ringEvents) q.ringForms.push_back(timedForm); else q.pairForm = timedForm;
+        }
         q.finOut = nullptr;
         q.finSeq = 0;
         if (ringEvents) q.evTail++; else q.kernelTimePending = true;
@@ -1737,6 +1751,7 @@ void finalizeQuery(Query& q) {
         RSQ_HIP(hipEventElapsedTime(&ms, q.gev0, q.gev1)); q.kernelTimePending = false;      // (one-launch step or not: the query's own event pair)
         if (q.pendingFused) q.fusedReady = true;
         q.report.kernel_time_ms = ms; q.kernelTimeSumMs += ms; q.kernelTimeLaunches++;
+        noteRowCellsTime(q, q.pairForm, ms); q.pairForm = -1;
         q.report.hbm_gbps = ms > 0 ? (double)q.report.bytes_read / (ms * 1e-3) / 1e9 : 0;
         if (!q.pendingFused) ctx.errWordClean = (uint32_t)q.hPinned[q.pinnedWords] == 0;
         checkAsyncDeviceError((uint32_t)q.hPinned[q.pinnedWords]);
@@ -1761,6 +1776,7 @@ void settleAsync(Query& q) {
     RSQ_HIP(hipEventElapsedTime(&ms, q.gev0, q.gev1)); q.kernelTimePending = false;
     if (q.pendingFused) q.fusedReady = true;
     q.report.kernel_time_ms = ms; q.kernelTimeSumMs += ms; q.kernelTimeLaunches++;
+    noteRowCellsTime(q, q.pairForm, ms); q.pairForm = -1;
     q.report.hbm_gbps = ms > 0 ? (double)q.report.bytes_read / (ms * 1e-3) / 1e9 : 0;
     if (!q.pendingFused) ctx.errWordClean = (uint32_t)q.hPinned[q.pinnedWords] == 0;
     checkAsyncDeviceError((uint32_t)q.hPinned[q.pinnedWords]);
@@ -1958,7 +1974,13 @@ std::string queryPartialLayoutText(const Query& q) {
     return text;
 }
 const char* querySource(const Query& q) { return q.allSource.c_str(); }
-const char* queryExplain(const Query& q) { return q.explainText.c_str(); }
+// (the line about the register aggregation's form is composed here from the pipelines' state: nothing is kept inside explainText)
+const char* queryExplain(const Query& q) {
+    const std::string form = rowCellsLine(q);
+    if (form.empty()) return q.explainText.c_str();
+    q.explainWithForm = q.explainText + form;
+    return q.explainWithForm.c_str();
+}
 void destroyQuery(Query* q) { delete q; }
 
 }  // namespace rsq

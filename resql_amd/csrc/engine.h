@@ -193,7 +193,7 @@ struct Context {
     // an allocation, which a second query over the same tables must not repeat.  Every entry is re-checked by the execution it serves.
     struct PlanMemo {
         struct Join { int64_t buildRows = -1; bool dupKeys = false; uint32_t lastCount = 0; };
-        struct Pipe { int64_t stage2Rows = -1; bool stagedExact = false; std::vector<uint32_t> stagedCaps; int64_t stagedCapsRows = -1; };
+        struct Pipe { int64_t stage2Rows = -1; bool stagedExact = false; std::vector<uint32_t> stagedCaps; int64_t stagedCapsRows = -1; int cellsChoice = -1; };
         std::vector<Join> joins;
         std::vector<Pipe> pipes;
         int64_t hashCapacity = 0; uint32_t hashCount = 0; bool charGroupsNeedMerge = false;
@@ -216,6 +216,7 @@ struct Context {
     uint64_t columnImageBytes = 0;             // device memory of the tables' narrow and dictionary images (rsq_ctx_memory_stats)
     uint64_t planMemoClock = 0, planMemoHits = 0;
     bool planMemoOff = false;
+    int rowCellsMode = -1;      // rsq_ctx_set_row_cells, the register aggregation's second form (row_cells.h): -1 chosen by kernel times, 0 not generated, 1 whenever a launch fits it
     // set by rsq_multi_query_compile around the compiles of a statement that runs on more than one shard: no dense group ids from dictionary
     // codes there (codegen_agg.cpp tryDenseKeys) - a table the shards hold alike is not unified (nRowsTotal stays -1), and the group-level
     // merge of the shards' results takes hash aggregations, not dense tables keyed by one context's dictionary.  The exception: a unified
@@ -433,6 +434,7 @@ void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool re
 int32_t queryNestedLoopsSlices(const Query& q);      // S of the most recent execution's top nested-loops pipeline (0: none, or not executed yet)
 const char* querySource(const Query& q);
 const char* queryExplain(const Query& q);
+std::string rowCellsLine(const Query& q);      // which form of a two-form register aggregation the last execution ran ("" where there is one form)
 void destroyQuery(Query* q);
 
 std::string serializeResultView(const rsq_result_view& v);

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <deque>
 #include <thread>
 #include <map>
 #include <memory>
@@ -15,6 +16,7 @@
 #include "engine.h"
 #include "hostref.h"
 #include "dense_groups.h"
+#include "row_cells.h"
 
 namespace rsq {
 
@@ -217,6 +219,17 @@ struct Pipeline {
     std::string source;              // generated HIP source
     std::string sourceFlat;          // register-mode aggregation: the variant that flushes into the unpadded table
     Kernel* kernelFlat = nullptr;
+    // the register aggregation's second form, rows into per-lane LDS cells (codegen_agg.cpp, row_cells.h): the same texts with RSQ_ROW_CELLS 1
+    std::string sourceCells, sourceFlatCells;
+    Kernel* kernelCells = nullptr; Kernel* kernelFlatCells = nullptr;
+    std::vector<int> rowCellsEnvelopes;      // envelope widths of the inputs that share a word: what a launch must fit (launchFits)
+    // ... and the choice between the forms (engine_pipelines.cpp rowCellsForm): two timed executions of form 0, two of form 1, then the better
+    int cellsChoice = -1;                    // -1: still measuring; 0 / 1: decided for this query (and, through the plan memo, the next one)
+    int cellsRuns[2] = {0, 0};               // timed executions per form
+    float cellsBestMs[2] = {0, 0};
+    int lastForm = -1;                       // the form the most recent launch ran (-1: the statement has one form)
+    int cellsLaunched[2] = {0, 0};           // measuring executions launched per form (their times arrive later: the event ring)
+    bool measuring = false; int measureForm = 0;      // this execution is one of the four, and the form it is to run
     std::string sourcePass1;         // SinkKind::MATERIALIZE: the counting pass of the same pipeline
     Kernel* kernelPass1 = nullptr;
     // partitioned aggregation (large dense group domains, see emitDenseAggregation): the same pipeline compiled as a
@@ -494,6 +507,8 @@ struct Query {
     bool narrowRowsOff = false;          // an execution needed every group row after all: full rows from now on
     bool fusedSelectOff = false;         // a meeting point of the one-launch candidate selection timed out once: separate launches from now on
     uint64_t mergePublishedSeq = 0;        // > 0: rsq_query_merge_gathered also published the merged table to hPinned; finalize polls for this number
+    std::deque<int> ringForms; int pairForm = -1;      // the register aggregation's form each recorded, unread event pair timed (-1: not one of the four measuring executions)
+    mutable std::string explainWithForm;      // what queryExplain hands out where a pipeline has two forms: explainText + rowCellsLine
     bool kernelTimePending = false;        // the fused step's events have not been read yet (resolveKernelTime)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> evRing; size_t evHead = 0, evTail = 0;      // event pairs of the one-launch steps not read yet
     hipEvent_t gev0 = nullptr, gev1 = nullptr;   // recorded in front of and behind the fused step's kernel
@@ -576,6 +591,11 @@ int residentWorkgroupsPerCU(Kernel* k, int blockThreads);
 void pipelineGridLimits(const Query& q, const Pipeline& p, bool lazyForm, int64_t& want, int64_t& cap);
 unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm = false);
 void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid = 0, unsigned block = 0);
+// the register aggregation's two forms (engine_pipelines.cpp): the choice margin is twice the widest run-to-run spread of the kernel time
+// in the series of docs/KERNELS.md ("Rows into per-lane LDS cells": 2 x 3.1 us = 6.2 us of form 0's 147 us, 4.2 %), rounded up
+constexpr float kRowCellsMargin = 0.045f;
+void prepareRowCellsForm(Query& q, Pipeline& p);
+void noteRowCellsTime(Query& q, int form, float ms);
 void waitForStream(Context& ctx);
 void debugStamps(Query& q, Pipeline& p);
 Kernel* fewGroupsKernel(Query& q, Pipeline& p, const std::string& source, const char* form, Kernel* large);

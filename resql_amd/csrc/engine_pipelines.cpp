@@ -143,14 +143,70 @@ unsigned pipelineGrid(const Query& q, const Pipeline& p, bool lazyForm) {
     return slicedGrid(q, p, want, cap);
 }
 
+// The register aggregation's two forms (codegen_agg.cpp, row_cells.h).  A launch runs form 1 - rows into per-lane LDS cells - only where no
+// packed field of a lane's word can carry (launchFits: the rows the word may receive under this grid, times the largest input, below 2^21;
+// RSQ_MAX_GRID=1 over a large table is the case that does not fit).  Which form: the context's setting, or the statement's own kernel times.
+// The one-launch step calls prepareRowCellsForm before it records its events: a statement that fits runs form 0 in its first two such
+// executions and form 1 in the next two, and keeps form 1 only if the better of its two times is below the better of form 0's by more than
+// kRowCellsMargin.  The decision holds for the query and, through the plan memo, for the next query of the same plan over the same tables.
+// Executions that are not timed one by one (traces, the interpreter in front) run the form decided so far, form 0 until then.
+void prepareRowCellsForm(Query& q, Pipeline& p) {
+    p.measuring = false; p.measureForm = 0;
+    if (!p.kernelCells || q.ctx.rowCellsMode != -1 || p.cellsChoice >= 0) return;
+    if (!rowcells::launchFits(p.rowCellsEnvelopes, (uint64_t)p.src->nRows, pipelineGrid(q, p), (uint64_t)p.blockThreads)) return;
+    p.measuring = true;
+    if (p.cellsLaunched[0] < 2) return;
+    p.measureForm = 1;
+    if (p.cellsLaunched[1] < 2) return;
+    resolveKernelTime(q);
+    if (p.cellsRuns[0] < 2 || p.cellsRuns[1] < 2) return;      // (an asynchronous step's events are read when it is finalised)
+    p.cellsChoice = p.cellsBestMs[1] < p.cellsBestMs[0] * (1.0f - kRowCellsMargin) ? 1 : 0;
+    p.measuring = false; p.measureForm = 0;
+}
+// (the timed executions are one-launch steps, and the one-launch step is a query of ONE pipeline - fusedEligible -, so the time is
+// pipelines[0]'s.  A member of the family that runs outside the one-launch step - a traced execution, a plan with further pipelines - is
+// never timed alone: under the default mode it runs form 0.)
+void noteRowCellsTime(Query& q, int form, float ms) {
+    if (form < 0 || form > 1 || q.pipelines.empty()) return;
+    Pipeline& p = q.pipelines[0];
+    if (p.cellsChoice >= 0) return;
+    if (p.cellsRuns[form] == 0 || ms < p.cellsBestMs[form]) p.cellsBestMs[form] = ms;
+    p.cellsRuns[form]++;
+}
+std::string rowCellsLine(const Query& q) {
+    for (auto& p : q.pipelines) {
+        if (p.lastForm < 0) continue;
+        char b[200];
+        const char* why = q.ctx.rowCellsMode == 0 ? "set by the context"
+                          : q.ctx.rowCellsMode == 1 ? (p.lastForm ? "set by the context" : "the launch does not fit the fields of a shared word")
+                          : p.cellsChoice < 0 ? "not decided yet" : "decided";
+        if (p.cellsRuns[0] && p.cellsRuns[1])
+            snprintf(b, sizeof b, "aggregation form of the last execution: %s (%s; %u workgroups; best kernel times %.1f us in registers, %.1f us in cells)\n",
+                     p.lastForm ? "1, rows into LDS cells" : "0, registers", why, p.lastGrid, p.cellsBestMs[0] * 1000.0, p.cellsBestMs[1] * 1000.0);
+        else snprintf(b, sizeof b, "aggregation form of the last execution: %s (%s; %u workgroups)\n", p.lastForm ? "1, rows into LDS cells" : "0, registers", why, p.lastGrid);
+        return b;
+    }
+    return std::string();
+}
+
 void launchPipelineKernel(Query& q, Pipeline& p, Kernel& k, int countOnlyTable, unsigned grid, unsigned block) {
     p.lastGrid = grid ? grid : pipelineGrid(q, p);
+    Kernel* form = &k;
+    p.lastForm = -1;
+    if (p.kernelCells && (form == p.kernel || form == p.kernelFlat)) {
+        // (the context's mode as it is NOW: 0 set after the statement was compiled, or after the plan memo handed it a decision, still runs form 0)
+        int f = q.ctx.rowCellsMode == 0 ? 0 : q.ctx.rowCellsMode == 1 ? 1 : p.cellsChoice >= 0 ? p.cellsChoice : p.measureForm;
+        if (f == 1 && !rowcells::launchFits(p.rowCellsEnvelopes, (uint64_t)p.src->nRows, p.lastGrid, (uint64_t)(block ? block : (unsigned)p.blockThreads))) f = 0;
+        Kernel* cells = form == p.kernel ? p.kernelCells : p.kernelFlatCells;
+        if (f == 1 && cells) form = cells; else f = 0;
+        p.lastForm = f;
+    }
     if (p.nljSliced >= 0 && p.lastGrid % (unsigned)std::max<int32_t>(1, q.nljs[(size_t)p.nljSliced].slices) != 0)
         failRuntime("internal error: " + p.entry + " launches " + std::to_string(p.lastGrid) + " workgroups, no multiple of its " +
                     std::to_string(q.nljs[(size_t)p.nljSliced].slices) + " inner-range slices");
     std::vector<uint64_t> args;
     for (auto& a : p.args) args.push_back(argValue(q, p, a, countOnlyTable));
-    launch(q.ctx, k, p.lastGrid, block ? block : (unsigned)p.blockThreads, args);
+    launch(q.ctx, *form, p.lastGrid, block ? block : (unsigned)p.blockThreads, args);
     q.report.num_kernels++;
 }
 

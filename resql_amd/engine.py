@@ -211,6 +211,7 @@ def lib():
         L.rsq_query_result_text.argtypes = [vp, C.POINTER(rsq_result_text_options), C.POINTER(rsq_result_text_report), C.POINTER(vp), C.POINTER(i64)]
         L.rsq_query_result_write.argtypes = [vp, C.c_char_p, C.POINTER(rsq_result_text_options), C.POINTER(rsq_result_text_report)]
         L.rsq_ctx_set_result_text.argtypes = [vp, i32]
+        L.rsq_ctx_set_row_cells.argtypes = [vp, i32]
         L.rsq_db_result_text_report.argtypes = [vp, C.POINTER(rsq_result_text_report)]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
@@ -275,7 +276,7 @@ EXPORTED_SYMBOLS = [
     "rsq_table_destroy", "rsq_query_compile", "rsq_query_execute", "rsq_query_await_kernels", "rsq_query_execute_partial",
     "rsq_query_execute_partial_async", "rsq_ctx_set_stream",
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_nested_loops_slices", "rsq_nested_loops_slices", "rsq_query_source", "rsq_query_explain",
-    "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_query_result_text", "rsq_query_result_write", "rsq_ctx_set_result_text", "rsq_db_result_text_report", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
+    "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_query_result_text", "rsq_query_result_write", "rsq_ctx_set_result_text", "rsq_ctx_set_row_cells", "rsq_db_result_text_report", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
     "rsq_measure_read_bandwidth",
@@ -435,6 +436,11 @@ class Context:
         """where results become text under mode 0 and the statement loop's `tofile`: 0 on the host (the default), 1 on the device
         (rsq_ctx_set_result_text)"""
         self._check(self._L.rsq_ctx_set_result_text(self.h, where))
+
+    def set_row_cells(self, mode: int):
+        """the register aggregation's second form, rows into per-lane LDS cells: -1 chosen by the executions' kernel times (the default),
+        0 not generated for statements compiled from now on, 1 in every launch that fits it (rsq_ctx_set_row_cells)"""
+        self._check(self._L.rsq_ctx_set_row_cells(self.h, mode))
 
     def set_rowstore_bridge(self, where: int):
         """where row stores are transposed under mode 0 (and so by rsq_table_from_rowstore): 0 on the host (the default), 1 on the
