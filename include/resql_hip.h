@@ -434,6 +434,43 @@ int  rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where);
  * gets no second form at all) and at every launch: 0 or 1 set later holds from the next execution on, for compiled statements too
  * (0 then runs form 0 of the two-form text, whatever the statement had measured or the plan memo remembered). */
 int  rsq_ctx_set_row_cells(rsq_ctx* ctx, int32_t mode);
+/* ORDER BY ... LIMIT k over a materialisation (a plan without an aggregation whose root is an ORDER BY with a LIMIT), optionally
+ * decided from rows the DEVICE selects (opt-in: rsq_ctx_set_order_limit).  The host path copies every column of every materialised row
+ * to the host, packs tuples, runs the reference's quicksort over all of them and drops what lies behind row k; it stays the definition
+ * of the answer.  The device path rests on the rule the aggregation tails use: the k first rows of the reference's sorted order are
+ * determined by the sort keys alone unless rows among the leading k + 1 tie on ALL keys.  With want = k + 1, it finds T, the want-th
+ * largest image of the first key (resql_amd/csrc/order_limit.h: key ^ 2^63, complemented for ascending order, the cell read at its own
+ * width) by an MSB-first radix select over the key's column, takes the candidates - every row with image >= T, in SCAN ORDER: one count
+ * per 256-row block, the toolkit's exclusive scan, a gather by ballot ranks - and writes their scan positions and their cells of every
+ * materialised column (numbers at their width, strings as spans of their column width) into compact columns of at most
+ * capacity = max(4 * want, 65536) rows.  Only those come back, through pinned memory; the host packs them into tuples with the function
+ * the full path packs all rows with, partial-sorts the leading want of them by the full key list, and - where every adjacent pair of
+ * those is strictly ordered - the first min(k, rows) are the result relation.  The full path runs, over the columns that are still on
+ * the device, where the report says so: FEW_ROWS 4 * k >= rows, OVERFLOW more candidates than capacity (many rows share the first
+ * key's leading value), TIES, and SHAPE: the plan is not eligible (an aggregation, no LIMIT, a LIMIT beyond 2^20, a LIMIT on the
+ * materialisation itself, a first key that is not a materialised INT / DATE / BIGINT / DECIMAL attribute, more than 32 columns) or the
+ * execution is not (a shard of rsq_multi_*, rsq_query_execute_partial).  0: host (the default - the launches and bytes of earlier
+ * versions), 1: device; else RSQ_ERR_INVALID naming "order_limit".  A setter, not a field: rsq_config keeps its size.  Read at every
+ * execution: it holds for statements compiled earlier too.  The device and pinned buffers are the context's arenas', kept by the
+ * query between executions and given back with it. */
+int  rsq_ctx_set_order_limit(rsq_ctx* ctx, int32_t where);
+enum rsq_order_limit_fallback { RSQ_ORDER_LIMIT_FALLBACK_NONE = 0, RSQ_ORDER_LIMIT_FALLBACK_SHAPE = 1, RSQ_ORDER_LIMIT_FALLBACK_FEW_ROWS = 2,
+                                RSQ_ORDER_LIMIT_FALLBACK_OVERFLOW = 3, RSQ_ORDER_LIMIT_FALLBACK_TIES = 4 };
+typedef struct rsq_order_limit_report {
+    uint32_t struct_size;            /* sizeof(rsq_order_limit_report), set by the caller: no more than that many bytes are written */
+    int32_t  planned;                /* 1: the compiled plan is of the eligible shape (known after compile, also on a compile-only context) */
+    int32_t  path;                   /* of the last execution - 0: the host sorted everything; 1: decided from device-selected candidates */
+    int32_t  fallback_reason;        /* rsq_order_limit_fallback: why an execution under setting 1 took the host path (0: it did not) */
+    int32_t  first_key_column;       /* planned: the materialised column the first ORDER BY expression names (else -1) */
+    int32_t  key_is32;               /* ... compared as signed 32 bits (INT, DATE); 0: as signed 64 bits (BIGINT, DECIMAL) */
+    int32_t  descending;             /* ... DESC */
+    int32_t  reserved;
+    int64_t  rows, want, candidates, capacity;      /* materialised rows, k + 1, rows with image >= T (exact, also above capacity), candidate rows the buffers hold */
+    /* ms.  select_ms: HIP events around the selection and gather kernels; copy_ms: the host's wait for the candidate count and the
+     * copy of positions and candidate columns; tail_ms: tuples, partial sort, tie check (on the host path: 0 - rsq_report.finalize_time_ms) */
+    double   select_ms, copy_ms, tail_ms;
+} rsq_order_limit_report;
+int  rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out);
 /* The slot order of the reference's aggregation hash table (allocateHashTable / ht_put / growHashTable, src/qlib/hash.h:225-287,
  * 330-419) after inserting n groups with the given Values::hash values in this order into a table allocated for min_size
  * entries: out[k] = index of the group in the k-th occupied slot.  parallel != 0 takes the cluster-parallel replay the engine's
@@ -498,6 +535,16 @@ int   rsq_prim_merge_group_rows(rsq_ctx* ctx, const int64_t* rows /* [n * stride
 int   rsq_prim_topk_select(rsq_ctx* ctx, const int64_t* rows /* [n_rows * stride] */, int64_t n_rows, int64_t rows_upper_bound, int32_t stride,
                            int32_t key_word, int32_t is32, int32_t desc, int64_t want, int32_t form, const uint64_t* image_range /* [2], form 1 */,
                            int64_t capacity, int64_t* cand_out /* [capacity * stride] */, uint32_t* cand_count, uint32_t* notes);
+/* The same pre-selection over a COLUMN, as ORDER BY ... LIMIT over a materialisation runs it (order_limit.hip, rsq_ctx_set_order_limit):
+ * n keys of key_width 4 (signed 32 bits, sign-extended) or 8 bytes; *threshold_image receives T, the want-th largest image (0 where
+ * n < want: every row is a candidate); *cand_count the number of rows with image >= T, exact also above capacity; positions_out
+ * [capacity] their row numbers in ascending order and payload_out [capacity * payload_width] those rows' cells of the one payload column
+ * (payload_width 1..4096 bytes per row, any value: the gather's byte path), both 0xff bytes before the launch and behind the first
+ * min(count, capacity) candidates.  Requires 0 <= n < 2^32, want >= 1, 1 <= capacity < 2^31. */
+int   rsq_prim_column_topk(rsq_ctx* ctx, const void* key /* [n * key_width] */, int32_t key_width, int64_t n, int32_t desc, int64_t want,
+                           int64_t capacity, const void* payload /* [n * payload_width] */, int32_t payload_width,
+                           uint32_t* positions_out /* [capacity] */, void* payload_out /* [capacity * payload_width] */, uint64_t* cand_count,
+                           uint64_t* threshold_image, uint32_t* notes);
 /* What the statistics pass left beside a column (aot_kernels.hip computeColumnStats), copied back as it lies: which 0 the narrow image
  * (rows values of `width` bytes, each the row's value minus `base`), 1 the dictionary's entries (as many as the column has, each as wide as
  * the column, in memcmp order), 2 the dictionary codes (one byte per row).  info = {width in bytes (0: no narrow image), base, dictionary
@@ -561,6 +608,7 @@ int  rsq_db_adopt_table(rsq_db* db, rsq_table* table);
 int  rsq_db_report(const rsq_db* db, rsq_report* out);          /* of the last SELECT */
 int  rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out);      /* of the last BULK INSERT (out->struct_size set by the caller) */
 int  rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out);      /* of the last SELECT that `tofile` wrote (likewise) */
+int  rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out);      /* of the last SELECT (likewise) */
 void rsq_db_destroy(rsq_db* db);
 
 /* ---- one host process, N GPUs ------------------------------------------------------------------

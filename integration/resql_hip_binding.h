@@ -206,6 +206,9 @@ public:
     // Where deviceTable transposes a Relation's tuples - whole Relations and the tails of grown ones alike: 0 on one host thread (the
     // default), 1 on the device (rsq_ctx_set_rowstore_bridge; same columns, same statistics).  rsq_table_from_rowstore obeys it.
     void setRowstoreBridge(int where) { check(rsq_ctx_set_rowstore_bridge(ctx_, where)); }
+    // where an ORDER BY ... LIMIT k over a materialisation is decided: 0 the host sorts every row (the default), 1 from the candidates
+    // the device selects (rsq_ctx_set_order_limit; same relation).  Read at every execution, also of statements compiled earlier.
+    void setOrderLimit(int where) { check(rsq_ctx_set_order_limit(ctx_, where)); }
 
     // BULK INSERT (execute.h:332-388) straight into device columns: the Relation object stays the table's identity
     // (plans scan it), its rows live on the GPU only.  Same field rules as the reference's loop (csrc/tbl.cpp).  A second

@@ -685,6 +685,26 @@ int rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where) {
     });
 }
 
+int rsq_ctx_set_order_limit(rsq_ctx* ctx, int32_t where) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid("order_limit is " + std::to_string(where) + " (0: ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1: decides from candidates selected on the device)");
+        C(ctx)->orderLimit = where;
+    });
+}
+
+int rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out) {
+    if (!q || !out) return RSQ_ERR_INVALID;
+    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
+    return guarded(h->ctx, [&] {
+        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_order_limit_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_order_limit_report)");
+        rsq_order_limit_report r{};
+        queryOrderLimitReport(*h->q, &r);
+        r.struct_size = out->struct_size;
+        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    });
+}
+
 int rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t n, uint64_t min_size, uint32_t* out) {
     if (!ctx || n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
@@ -918,6 +938,38 @@ int rsq_prim_topk_select(rsq_ctx* ctx, const int64_t* rows, int64_t n_rows, int6
     });
 }
 
+int rsq_prim_column_topk(rsq_ctx* ctx, const void* key, int32_t key_width, int64_t n, int32_t desc, int64_t want, int64_t capacity, const void* payload,
+                         int32_t payload_width, uint32_t* positions_out, void* payload_out, uint64_t* cand_count, uint64_t* threshold_image, uint32_t* notes) {
+    if (!ctx || !notes || !positions_out || !payload_out || !cand_count || !threshold_image || n < 0 || (n > 0 && (!key || !payload))) return RSQ_ERR_INVALID;
+    *notes = 0;
+    // (the kernels trust these: a cell's address comes from its width, a candidate's from the capacity; row numbers are 32 bits)
+    if ((key_width != 4 && key_width != 8) || n > 0xffffffffll || want < 1 || want > 0xffffffffll || capacity < 1 || capacity >= kPrimMaxItems ||
+        payload_width < 1 || payload_width > 4096)
+        return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        const uint32_t before = primErrWord(c);
+        struct Held {       // given back however the call ends, once the stream has drained
+            Context& c; OrderLimitBuffers b;
+            ~Held() { (void)hipStreamSynchronize(c.stream); b.release(c); }
+        } held{c, {}};
+        PrimBuffers pb(c);
+        unsigned char* dKey = pb.take<unsigned char>((size_t)n * (size_t)key_width);
+        unsigned char* dPayload = pb.take<unsigned char>((size_t)n * (size_t)payload_width);
+        if (n) {
+            RSQ_HIP(hipMemcpyAsync(dKey, key, (size_t)n * (size_t)key_width, hipMemcpyHostToDevice, c.stream));
+            RSQ_HIP(hipMemcpyAsync(dPayload, payload, (size_t)n * (size_t)payload_width, hipMemcpyHostToDevice, c.stream));
+        }
+        held.b.ensure(c, n, capacity, {payload_width});
+        OrderLimitSelection s;
+        orderLimitSelect(c, held.b, dKey, key_width, desc != 0, n, (uint32_t)want, {dPayload}, true, s);
+        memcpy(positions_out, s.positions, (size_t)capacity * 4);
+        memcpy(payload_out, s.cols[0], (size_t)capacity * (size_t)payload_width);
+        *cand_count = s.candidates; *threshold_image = s.threshold;
+        primNotes(c, before, notes);
+    });
+}
+
 int rsq_ref_emission_order(const uint64_t* hashes, int64_t n, uint64_t min_size, int32_t parallel, uint32_t* out) {
     if (n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     try {
@@ -980,6 +1032,7 @@ struct rsq_db {
     rsq_report lastReport{};
     rsq_tbl_load_report lastLoad{};          // of the last BULK INSERT
     rsq_result_text_report lastText{};       // of the last SELECT that `tofile` wrote
+    rsq_order_limit_report lastOrderLimit{}; // of the last SELECT
     // DBConfig / JitConfig as the control variables set them (execute.h:23-27, JitContextFlounder.h:86-109)
     bool showPlan = false, writeResultsToFile = false;
     uint16_t numThreads = 1;
@@ -1189,6 +1242,14 @@ int rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out) {
     return RSQ_OK;
 }
 
+int rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out) {
+    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
+    rsq_order_limit_report r = db->lastOrderLimit;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return RSQ_OK;
+}
+
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
 int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_view* result) {
@@ -1278,6 +1339,7 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
     selectStatus = rsq_query_execute(db->last);
     if (selectStatus != RSQ_OK) return selectStatus;
     rsq_query_report(db->last, &db->lastReport);
+    queryOrderLimitReport(*QH(db->last)->q, &db->lastOrderLimit);
     rsq_result_view view;
     selectStatus = rsq_query_result(db->last, &view);
     if (selectStatus != RSQ_OK) return selectStatus;

@@ -161,6 +161,7 @@ Query::~Query() {
     if (hInlineRows) ctx.freePinned(hInlineRows);
     if (dPipeStats) ctx.free(dPipeStats);
     if (dGroupCount) ctx.free(dGroupCount);
+    orderLimit.buffers.release(ctx);
     if (dTopkImages) ctx.free(dTopkImages);
     if (dTopkHists) ctx.free(dTopkHists);
     if (dCandRows) ctx.free(dCandRows);
@@ -569,6 +570,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     }
     const double tBuilt0 = nowMs();
     buildPipelines(*q);
+    planOrderLimit(*q);
     const double tBuilt = nowMs();
     // A plan shape whose specialised kernels are not in the code-object cache starts on the pre-compiled generic pipeline
     // (generic.cpp) while hiprtc builds them on a host thread; RSQ_FORCE_GENERIC=1 keeps every eligible plan there (tests),
@@ -770,6 +772,38 @@ static bool fusedEligible(const Query& q) {
 // materialised columns) back, but leaves the tail to the root, which merges all shards' groups first (tail.cpp runTailMerged)
 static void tailUnlessHeld(Query& q) { if (!q.holdTail) runTail(q); }
 
+// ORDER BY ... LIMIT k over a materialisation whose columns stand complete in q.dMatCols (whichever tier wrote them), under
+// rsq_ctx_set_order_limit = 1: the device selects the candidates (order_limit.hip), only they come back, and the tail decides from them
+// (tail.cpp runOrderLimitTail).  False: the host path follows over all of q.dMatCols - they are untouched - and the report says why.
+static bool orderLimitOnDevice(Query& q) {
+    Context& ctx = q.ctx;
+    rsq_order_limit_report& r = q.orderLimit.report;
+    if (ctx.orderLimit != 1) return false;
+    r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_SHAPE;
+    const int64_t n = q.matRows;
+    if (!r.planned || q.holdTail || n >= ((int64_t)1 << 32) || q.dMatCols.size() != q.matSchema.size()) return false;
+    const int64_t limit = q.root->limit, want = limit + 1;
+    const int64_t capacity = std::max<int64_t>(4 * want, 65536);
+    r.rows = n; r.want = want; r.capacity = capacity;
+    if (4 * limit >= n) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_FEW_ROWS; return false; }      // (the rule of tail.cpp runTailOn)
+    std::vector<int32_t> widths;
+    std::vector<const void*> src;
+    for (size_t c = 0; c < q.matSchema.size(); c++) { widths.push_back(columnWidth(q.matSchema[c].type)); src.push_back(q.dMatCols[c]); }
+    OrderLimitBuffers& b = q.orderLimit.buffers;
+    b.ensure(ctx, n, capacity, widths);
+    OrderLimitSelection s;
+    orderLimitSelect(ctx, b, q.dMatCols[(size_t)r.first_key_column], r.key_is32 ? 4 : 8, r.descending != 0, n, (uint32_t)want, src, false, s);
+    q.report.num_kernels += 10;      // six digit histograms, the threshold, the counts, their scan, the gather
+    r.candidates = (int64_t)s.candidates; r.select_ms = s.selectMs; r.copy_ms = s.copyMs;
+    if (s.candidates > (uint64_t)capacity) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_OVERFLOW; return false; }
+    const double t0 = nowMs();
+    const bool decided = runOrderLimitTail(q, s.cols.data(), (size_t)s.candidates);
+    r.tail_ms = nowMs() - t0;
+    if (!decided) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_TIES; return false; }
+    r.path = 1; r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_NONE;
+    return true;
+}
+
 void fetchHeldGroupRows(Query& q) {
     if (q.nGroupRows <= 0) return;
     ensureHostGroupRows(q, (size_t)q.nGroupRows * (size_t)q.groupRowWords);
@@ -940,6 +974,12 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
+    {   // the execution's part of the ORDER BY ... LIMIT report: the host path, under setting 1 for want of the shape until orderLimitOnDevice says otherwise
+        rsq_order_limit_report& r = q.orderLimit.report;
+        r.path = 0; r.fallback_reason = ctx.orderLimit == 1 ? RSQ_ORDER_LIMIT_FALLBACK_SHAPE : RSQ_ORDER_LIMIT_FALLBACK_NONE;
+        r.rows = r.want = r.candidates = r.capacity = 0;
+        r.select_ms = r.copy_ms = r.tail_ms = 0;
+    }
     runSubQueries(q);
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
         // the full kernels are in the cache now: the quick tier's are replaced (same arguments, same tables - nothing else changes).
@@ -1643,6 +1683,12 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         }
         if (denseMode(q)) tableFromPinned(q);
         else if (q.matOp && !q.agg) {
+            if (orderLimitOnDevice(q)) {          // (rsq_ctx_set_order_limit: the candidates decided the answer, no column travels whole)
+                q.report.finalize_time_ms = nowMs() - t1;
+                q.report.execution_time_ms = nowMs() - t0;
+                execTrace();
+                return;
+            }
             q.hMatCols.resize(q.matSchema.size());
             for (size_t c = 0; c < q.matSchema.size(); c++) {
                 size_t bytes = (size_t)q.matRows * (size_t)columnWidth(q.matSchema[c].type);
@@ -1941,6 +1987,7 @@ void queryReport(const Query& q, rsq_report* out) {
     resolveKernelTime(const_cast<Query&>(q));
     *out = q.report;
 }
+void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out) { *out = q.orderLimit.report; }
 int32_t queryNestedLoopsSlices(const Query& q) {
     for (const NljState& n : q.nljs) if (n.sub.query && n.outerSrc) return n.slices;      // (the top one: the others run inside its inner side)
     return 0;

@@ -224,6 +224,7 @@ struct Context {
     bool shardCompile = false;
     int32_t resultText = 0;                    // rsq_ctx_set_result_text: 0 results become text on the host, 1 on the device (result_text.hip)
     int32_t rowstoreBridge = 0;                // rsq_ctx_set_rowstore_bridge: 0 row stores are transposed on the host, 1 on the device (rowstore_device.hip)
+    int32_t orderLimit = 0;                    // rsq_ctx_set_order_limit: 0 ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1 decides from device-selected candidates (order_limit.hip)
 };
 
 rsq_config readConfig(const rsq_config* cfg, bool multiBase = false);      // api.cpp: the host's struct (struct_size bytes), validated
@@ -386,6 +387,38 @@ std::unique_ptr<Table> rowstoreToDevice(Context& ctx, const rsq_table_desc& sche
                                         const uint8_t* const* blocks, const size_t* contentSize, int32_t nBlocks, int64_t nRows, int64_t chunkBytes,
                                         rsq_rowstore_report& rep);
 
+// order_limit.hip: the rows that decide an ORDER BY ... LIMIT k over column-wise rows (rsq_ctx_set_order_limit, rsq_prim_column_topk):
+// T = the want-th largest image (order_limit.h) of the key column by an MSB-first radix select, then every row with image >= T in scan
+// order - its position and its cell of every column - into compact candidate columns of `capacity` rows.
+enum { ORDER_LIMIT_MAX_COLUMNS = 32 };
+// device and pinned buffers of a selection, from the context's arenas; their owner keeps them between selections and releases them
+struct OrderLimitBuffers {
+    uint32_t* dScratch = nullptr;              // the digit histograms, then the threshold
+    uint32_t* dCounts = nullptr;               // candidates per 256-row block, and a trailing zero
+    uint64_t* dOffs = nullptr;                 // their exclusive scan: dOffs[blocks] = all candidates
+    void* dScanTemp = nullptr; size_t scanBytes = 0;
+    int64_t blocks = 0;                        // 256-row blocks the three above provide for
+    uint32_t* dPositions = nullptr;            // [capacity] scan positions of the candidates
+    std::vector<void*> dCols;                  // [capacity] cells per column, at widths[c] bytes
+    std::vector<int32_t> widths;
+    int64_t capacity = 0;
+    uint8_t* pinned = nullptr; size_t pinnedBytes = 0;      // [status: 16 bytes][positions][columns], each part a multiple of 16 bytes
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    void ensure(Context& ctx, int64_t nRows, int64_t capacity, const std::vector<int32_t>& widths);
+    void release(Context& ctx);
+};
+struct OrderLimitSelection {
+    uint64_t candidates = 0, threshold = 0;    // rows with image >= threshold: exact, also above capacity (then nothing was copied)
+    const uint32_t* positions = nullptr;       // host views of the first min(candidates, capacity) candidates (pinned memory of the buffers)
+    std::vector<const uint8_t*> cols;
+    double selectMs = 0, copyMs = 0;           // HIP events around the kernels; the host's wait for the count and the copies
+};
+// key: nRows cells of keyWidth 4 or 8 in device memory; src[c]: nRows cells of b.widths[c] bytes.  everything: positions and columns are
+// filled with 0xff bytes first and come back whole, whatever the count (the primitive's contract); else only what was selected,
+// and nothing when the candidates exceed the capacity.  0 <= nRows < 2^32, want >= 1; b.ensure()d for nRows and these widths.
+void orderLimitSelect(Context& ctx, OrderLimitBuffers& b, const void* key, int keyWidth, bool desc, int64_t nRows, uint32_t want,
+                      const std::vector<const void*>& src, bool everything, OrderLimitSelection& out);
+
 // ---- query ------------------------------------------------------------------------------------
 struct Query;
 Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables);
@@ -430,6 +463,7 @@ void mergeGathered(Query& q, const void* gathered, int nRanks);
 void partialBuffer(Query& q, void** dptr, int64_t* nMin, int64_t* nMax, int64_t* nSum);
 void queryResult(Query& q, rsq_result_view* out);
 void queryReport(const Query& q, rsq_report* out);
+void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out);      // (struct_size is the caller's business: api.cpp)
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset);
 int32_t queryNestedLoopsSlices(const Query& q);      // S of the most recent execution's top nested-loops pipeline (0: none, or not executed yet)
 const char* querySource(const Query& q);

@@ -418,6 +418,9 @@ struct Query {
     bool matWarmRun = false;               // waiting for the total; the total then arrives with the status words and must equal the remembered one
     const uint64_t* dMatTotal = nullptr;   // (where it stands: the last offset of the scan)
     std::vector<std::vector<uint8_t>> hMatCols;
+    // ORDER BY ... LIMIT k at the root, decided from candidates selected on the device (rsq_ctx_set_order_limit; tail.cpp planOrderLimit,
+    // engine.cpp orderLimitOnDevice, order_limit.hip): the report's plan fields are set when the statement is compiled, the others by every execution
+    struct { rsq_order_limit_report report{}; OrderLimitBuffers buffers; } orderLimit;
 
     // compacted group rows read back from a join-entry aggregation: [nGroups][groupWords]
     int64_t* dGroupRows = nullptr;
@@ -580,6 +583,10 @@ bool planRowsDeviceTail(Query& q, RowTailKeys& keys, RowTailCols& cols, int& tup
 void runRowsTailSort(Query& q, uint8_t* tuples, int64_t& rows);
 // tail.cpp: is the first ORDER BY key of an `ORDER BY ... LIMIT k` above the aggregation one word of the group rows?
 void planDeviceTopK(Query& q);
+// tail.cpp: is the plan an ORDER BY ... LIMIT k over a materialisation whose first key the device can order?  (the report's plan fields)
+void planOrderLimit(Query& q);
+// tail.cpp: the answer from the candidates' columns, or false where rows among the leading k + 1 tie on every key
+bool runOrderLimitTail(Query& q, const uint8_t* const* candCols, size_t nCand);
 
 // ---- engine_pipelines.cpp: one pipeline on the device, by sink (called from executeQuery) --------------------------------------
 inline int64_t nextPow2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return p; }

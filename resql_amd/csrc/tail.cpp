@@ -12,6 +12,7 @@
 
 #include "engine_internal.h"
 #include "hostpar.h"
+#include "order_limit.h"
 
 namespace rsq {
 
@@ -343,6 +344,28 @@ void mergeSpaceEquivalentGroups(Query& q, Groups& G) {
 
 }  // namespace
 
+// the OrderByOp above a materialisation (the topmost, if there are several), or null; anything else above it is refused
+static OpNode* materializeOrderBy(const Query& q) {
+    OpNode* orderBy = nullptr;
+    for (OpNode* o = q.matOp->parent; o; o = o->parent) {
+        if (o->tag == RSQ_OP_ORDERBY) orderBy = o;
+        else failUnsupported("operator above a materialisation other than order by");
+    }
+    return orderBy;
+}
+
+// its sort keys as fields of the materialised tuple
+static std::vector<OrderRequest> materializeOrderRequests(const Schema& cur, OpNode* orderBy) {
+    std::vector<OrderRequest> reqs;
+    for (Expr* e : orderBy->exprs) {
+        const std::string& nm = e->child->symbol;
+        bool found = false;
+        for (auto& a : cur) if (a.name == nm) { reqs.push_back({schemaOffset(cur, nm), a.type, e->tag != RSQ_E_DESC}); found = true; break; }
+        if (!found) failType("Order By attribute not found.");
+    }
+    return reqs;
+}
+
 // plans without aggregation: the device delivered the materialised columns in scan order; pack ReSQL tuples and
 // apply ORDER BY / LIMIT of an OrderByOp above (orderby.h:87-136)
 static void runMaterializeTail(Query& q) {
@@ -352,45 +375,90 @@ static void runMaterializeTail(Query& q) {
     const size_t n = (size_t)q.matRows;
     q.resultTuples.assign(n * ts, 0);
     q.resultRows = (int64_t)n;
-    std::vector<int> colOff(cur.size());
-    { int off = 0; for (size_t c = 0; c < cur.size(); c++) { colOff[c] = off; off += sizeInTuple(cur[c].type, true); } }
+    std::vector<Type> types;
+    std::vector<const uint8_t*> cols;
+    for (size_t c = 0; c < cur.size(); c++) { types.push_back(cur[c].type); cols.push_back(q.hMatCols[c].data()); }
     // rows are independent: split them over the host threads (20 M tuples took 150 ms on one)
     parallelFor(n, tailThreads(n), [&](size_t lo, size_t hi, int) {
-        std::vector<char> strbuf;
-        for (size_t c = 0; c < cur.size(); c++) {
-            const Type& t = cur[c].type;
-            const size_t w = (size_t)columnWidth(t);
-            const uint8_t* src = q.hMatCols[c].data();
-            if (t.isString()) strbuf.assign(w + 1, 0);
-            for (size_t r = lo; r < hi; r++) {
-                uint8_t* dst = &q.resultTuples[r * ts + (size_t)colOff[c]];
-                if (t.isString()) {
-                    memcpy(strbuf.data(), src + r * w, w); strbuf[w] = 0;
-                    Val v; v.s = strbuf.data();
-                    storeValue(dst, v, t);
-                } else memcpy(dst, src + r * w, w);      // same little-endian value widths as the packed tuple
-            }
-        }
+        if (lo < hi) columnsToTuples(types, cols.data(), lo, hi, &q.resultTuples[lo * ts], ts);
     });
-    OpNode* orderBy = nullptr;
-    for (OpNode* o = q.matOp->parent; o; o = o->parent) {
-        if (o->tag == RSQ_OP_ORDERBY) orderBy = o;
-        else failUnsupported("operator above a materialisation other than order by");
-    }
+    OpNode* orderBy = materializeOrderBy(q);
     if (orderBy) {
-        std::vector<OrderRequest> reqs;
-        for (Expr* e : orderBy->exprs) {
-            const std::string& nm = e->child->symbol;
-            bool found = false;
-            for (auto& a : cur) if (a.name == nm) { reqs.push_back({schemaOffset(cur, nm), a.type, e->tag != RSQ_E_DESC}); found = true; break; }
-            if (!found) failType("Order By attribute not found.");
-        }
+        const std::vector<OrderRequest> reqs = materializeOrderRequests(cur, orderBy);
         refQuicksort(q.resultTuples.data(), q.resultRows, ts, reqs);
         if (orderBy->hasLimit && q.resultRows > orderBy->limit) {
             q.resultRows = orderBy->limit;
             q.resultTuples.resize((size_t)q.resultRows * ts);
         }
     }
+}
+
+// `ORDER BY ... LIMIT k` at the root of a plan WITHOUT an aggregation (rsq_ctx_set_order_limit): can the rows that decide the answer be
+// selected on the device from the materialised columns (order_limit.hip)?  The first sort key must be a materialised attribute the
+// device can order - INT / DATE as signed 32 bits, BIGINT / DECIMAL as signed 64 bits, the order of compareTyped; any other first key
+// (a string, BOOL, CHAR(1)) keeps the host path, and a name the materialisation does not hold keeps the reference's error.  Later keys
+// may be of any type: the host compares them.  Fills the compile-time fields of the query's report.
+void planOrderLimit(Query& q) {
+    rsq_order_limit_report& r = q.orderLimit.report;
+    r = rsq_order_limit_report{};
+    r.first_key_column = -1;
+    if (q.agg || !q.matOp || !q.root || q.root->tag != RSQ_OP_ORDERBY || q.matOp->parent != q.root) return;
+    const OpNode* orderBy = q.root;
+    if (!orderBy->hasLimit || orderBy->limit < 0 || orderBy->limit > (1 << 20) || q.matOp->hasLimit || orderBy->exprs.empty()) return;
+    if (q.matSchema.empty() || q.matSchema.size() > (size_t)ORDER_LIMIT_MAX_COLUMNS) return;
+    const Expr* first = orderBy->exprs[0];
+    if (!first->child) return;
+    for (size_t c = 0; c < q.matSchema.size(); c++) {
+        if (q.matSchema[c].name != first->child->symbol) continue;
+        const Type& t = q.matSchema[c].type;
+        if (t.tag == RSQ_INT || t.tag == RSQ_DATE) r.key_is32 = 1;
+        else if (t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) return;
+        r.first_key_column = (int32_t)c;
+        r.descending = first->tag == RSQ_E_DESC;
+        r.planned = 1;
+        return;
+    }
+}
+
+// The decision of runTailOn's candidate path over the rows the device selected: candCols are the candidates' cells of every
+// materialised column, in scan order - every row whose first key is at or in front of the (k + 1)-th leading value, so the rows that
+// lead the full lexicographic order are among them.  True: the leading min(k + 1, candidates) rows are strictly ordered by the full
+// key list, and the first min(k, candidates) of them are the result relation.  False: rows among them tie on all keys - the answer is
+// the reference's quicksort order over the scan order, which takes every row.
+bool runOrderLimitTail(Query& q, const uint8_t* const* candCols, size_t nCand) {
+    const Schema& cur = q.matSchema;
+    OpNode* orderBy = materializeOrderBy(q);
+    const std::vector<OrderRequest> reqs = materializeOrderRequests(cur, orderBy);
+    const size_t ts = (size_t)schemaTupleSize(cur), k = (size_t)orderBy->limit;
+    std::vector<Type> types;
+    for (auto& a : cur) types.push_back(a.type);
+    std::vector<uint8_t> all(nCand * ts, 0);
+    parallelFor(nCand, tailThreads(nCand), [&](size_t lo, size_t hi, int) {
+        if (lo < hi) columnsToTuples(types, candCols, lo, hi, &all[lo * ts], ts);
+    });
+    auto before = [&](const uint8_t* a, const uint8_t* b) {
+        for (const auto& o : reqs) {
+            int c = compareTyped(o.type, a + o.offset, b + o.offset);
+            if (o.asc) { if (c < 0) return true; if (c > 0) return false; }
+            else { if (c > 0) return true; if (c < 0) return false; }
+        }
+        return false;
+    };
+    const size_t lead = std::min(k + 1, nCand);
+    std::vector<size_t> idx(nCand);
+    for (size_t i = 0; i < nCand; i++) idx[i] = i;
+    std::partial_sort(idx.begin(), idx.begin() + (long)lead, idx.end(), [&](size_t a, size_t b) { return before(&all[a * ts], &all[b * ts]); });
+    for (size_t i = 0; i + 1 < lead; i++)
+        if (!before(&all[idx[i] * ts], &all[idx[i + 1] * ts])) return false;      // sorted, so "not before" means equal keys
+    const size_t out = std::min(k, nCand);
+    q.resultSchema = cur;
+    q.resultTuples.resize(out * ts);
+    for (size_t i = 0; i < out; i++) memcpy(&q.resultTuples[i * ts], &all[idx[i] * ts], ts);
+    q.resultRows = (int64_t)out;
+    q.tailNeedsAllGroups = false;
+    q.resultInPinned = false;
+    q.resultDev = nullptr;
+    return true;
 }
 
 // Device-side pre-selection for `ORDER BY ... LIMIT k` (orderby.h:87-93 sorts everything, then applyLimit): possible when

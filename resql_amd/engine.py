@@ -102,6 +102,22 @@ TEXT_HOST, TEXT_DEVICE = 1, 2      # rsq_result_text_options.mode (0: the contex
 TEXT_FALLBACK_NONE, TEXT_FALLBACK_NO_DEVICE, TEXT_FALLBACK_SCHEMA, TEXT_FALLBACK_DOES_NOT_FIT = range(4)
 
 
+class rsq_order_limit_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
+                ("first_key_column", C.c_int32), ("key_is32", C.c_int32), ("descending", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("want", C.c_int64), ("candidates", C.c_int64), ("capacity", C.c_int64),
+                ("select_ms", C.c_double), ("copy_ms", C.c_double), ("tail_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+ORDER_LIMIT_HOST, ORDER_LIMIT_DEVICE = 0, 1      # Context.set_order_limit
+# rsq_order_limit_fallback: why an execution under set_order_limit(1) sorted every row on the host
+(ORDER_LIMIT_FALLBACK_NONE, ORDER_LIMIT_FALLBACK_SHAPE, ORDER_LIMIT_FALLBACK_FEW_ROWS, ORDER_LIMIT_FALLBACK_OVERFLOW,
+ ORDER_LIMIT_FALLBACK_TIES) = range(5)
+
+
 class rsq_memory_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("device_slab_bytes", C.c_uint64), ("device_used_bytes", C.c_uint64),
                 ("device_slab_allocs", C.c_uint64), ("pinned_slab_bytes", C.c_uint64), ("pinned_used_bytes", C.c_uint64),
@@ -213,6 +229,10 @@ def lib():
         L.rsq_ctx_set_result_text.argtypes = [vp, i32]
         L.rsq_ctx_set_row_cells.argtypes = [vp, i32]
         L.rsq_db_result_text_report.argtypes = [vp, C.POINTER(rsq_result_text_report)]
+        L.rsq_ctx_set_order_limit.argtypes = [vp, i32]
+        L.rsq_query_order_limit_report.argtypes = [vp, C.POINTER(rsq_order_limit_report)]
+        L.rsq_db_order_limit_report.argtypes = [vp, C.POINTER(rsq_order_limit_report)]
+        L.rsq_prim_column_topk.argtypes = [vp, vp, i32, i64, i32, i64, i64, vp, i32, vp, vp, vp, vp, vp]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
         L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
@@ -278,7 +298,8 @@ EXPORTED_SYMBOLS = [
     "rsq_query_finalize", "rsq_query_merge_gathered", "rsq_query_finalize_host", "rsq_query_bind_partial", "rsq_query_partial_layout", "rsq_query_result", "rsq_query_report", "rsq_query_kernel_time_stats", "rsq_query_nested_loops_slices", "rsq_nested_loops_slices", "rsq_query_source", "rsq_query_explain",
     "rsq_query_destroy", "rsq_serialize_expr", "rsq_result_serialize", "rsq_free", "rsq_query_result_text", "rsq_query_result_write", "rsq_ctx_set_result_text", "rsq_ctx_set_row_cells", "rsq_db_result_text_report", "rsq_ref_emission_order", "rsq_ref_emission_order_device",
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
-    "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select",
+    "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select", "rsq_prim_column_topk",
+    "rsq_ctx_set_order_limit", "rsq_query_order_limit_report", "rsq_db_order_limit_report",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_load_report", "rsq_db_destroy",
@@ -431,6 +452,28 @@ class Context:
                                                  1 if is32 else 0, 1 if desc else 0, want, form, None if rng is None else rng.ctypes.data, capacity,
                                                  cand.ctypes.data, C.addressof(count), C.addressof(notes)))
         return cand, count.value, notes.value
+
+    def prim_column_topk(self, key: np.ndarray, desc: bool, want: int, capacity: int, payload: np.ndarray):
+        """ORDER BY ... LIMIT pre-selection over a column (rsq_prim_column_topk): key int32 or int64 [n], payload uint8 [n, width]:
+        (positions uint32 [capacity] and payload rows uint8 [capacity, width], 0xff bytes where nothing was written; the number of rows
+        with image >= T; T; notes)"""
+        key = np.ascontiguousarray(key)
+        if key.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise ValueError("prim_column_topk: the key column is int32 or int64")
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(len(key), -1)
+        width = payload.shape[1]
+        positions = np.zeros(capacity, dtype=np.uint32)
+        out = np.zeros((capacity, width), dtype=np.uint8)
+        count, threshold, notes = C.c_uint64(0xffffffffffffffff), C.c_uint64(0), C.c_uint32(0xffffffff)
+        self._check(self._L.rsq_prim_column_topk(self.h, key.ctypes.data, key.dtype.itemsize, len(key), 1 if desc else 0, want, capacity,
+                                                 payload.ctypes.data, width, positions.ctypes.data, out.ctypes.data, C.addressof(count),
+                                                 C.addressof(threshold), C.addressof(notes)))
+        return positions, out, count.value, threshold.value, notes.value
+
+    def set_order_limit(self, where: int):
+        """where an ORDER BY ... LIMIT k over a materialisation is decided: 0 the host sorts every row (the default), 1 from candidates
+        the device selects (rsq_ctx_set_order_limit).  Read at every execution; Query.order_limit_report says which path ran and why"""
+        self._check(self._L.rsq_ctx_set_order_limit(self.h, where))
 
     def set_result_text(self, where: int):
         """where results become text under mode 0 and the statement loop's `tofile`: 0 on the host (the default), 1 on the device
@@ -773,6 +816,13 @@ class Query:
         self.ctx._check(self.ctx._L.rsq_query_report(self.h, C.byref(r)))
         return r
 
+    def order_limit_report(self) -> dict:
+        """rsq_order_limit_report: whether the plan is an ORDER BY ... LIMIT the device can pre-select for, and for the last execution
+        which path decided the answer, why, rows, candidates and the phases"""
+        r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
+        self.ctx._check(self.ctx._L.rsq_query_order_limit_report(self.h, C.byref(r)))
+        return r.as_dict()
+
     def kernel_time_stats(self, reset: bool = False):
         """(device ms summed over the executions since the last reset, number of executions)"""
         s, n = C.c_double(0), C.c_uint64(0)
@@ -853,6 +903,13 @@ class Database:
         """rsq_result_text_report of the last SELECT that `tofile` wrote: which path wrote qres.tbl, why, rows, chunks, phase times"""
         r = rsq_result_text_report(C.sizeof(rsq_result_text_report))
         self.ctx._check(self.ctx._L.rsq_db_result_text_report(self.h, C.byref(r)))
+        return r.as_dict()
+
+    @property
+    def order_limit_report(self) -> dict:
+        """rsq_order_limit_report of the last SELECT: which path decided its ORDER BY ... LIMIT, why, rows, candidates, phase times"""
+        r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
+        self.ctx._check(self.ctx._L.rsq_db_order_limit_report(self.h, C.byref(r)))
         return r.as_dict()
 
     def execute_script(self, text: str):
