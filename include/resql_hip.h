@@ -397,8 +397,12 @@ void  rsq_free(void* p);
  * the tile - and the text comes back through pinned staging.  Device and pinned memory are the context's arenas' and are given back
  * however the call ends.  The call takes the host path - reported, never an error - where the context has no device, the schema
  * is outside the device form (more than 64 columns, CHAR of length 0, a DECIMAL scale above 18, a row whose text may exceed
- * 64 KiB), or a chunk of one row does not fit max_device_bytes.  The tuples are always uploaded from the host copy the result
- * view hands out (tuples_from_device stays 0: reading a device tail's buffer in place is not built).
+ * 64 KiB), or a chunk of one row does not fit max_device_bytes.  Where the materialisation's device tail (rsq_ctx_set_result_pack)
+ * made the result and no ORDER BY reordered it on the host, the kernels read the tuples in the query's own device buffer, chunk by
+ * chunk at any byte offset: no tuple buffer is allocated, nothing is uploaded, tuples_from_device is 1 and upload_ms 0.  That buffer is
+ * the query's from the execution until its next execution or its destruction, whatever other statements run in between.  Every other
+ * result - the aggregation tails' among them, whose arena space is not the query's to keep - is uploaded from the host copy the result
+ * view hands out (tuples_from_device 0).
  * Options and report carry struct_size like rsq_config: the library reads / writes no more than that many bytes.  A query that has
  * not been executed answers as rsq_query_result does (a relation of no rows).  The handles of several GPUs keep the host text. */
 typedef struct rsq_result_text_options {
@@ -471,6 +475,39 @@ typedef struct rsq_order_limit_report {
     double   select_ms, copy_ms, tail_ms;
 } rsq_order_limit_report;
 int  rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out);
+/* The result tuples of a materialisation (a plan without an aggregation: every SELECT of columns), optionally packed on the DEVICE
+ * (opt-in: rsq_ctx_set_result_pack).  The host path copies every output column to the host on its own, zero-fills the relation and
+ * packs ReSQL tuples on the worker pool; it stays the definition of the bytes.  The device path packs all rows in one launch
+ * (resql_amd/csrc/result_pack.h holds the bytes of a field for both sides: a number's cell, CHAR(1)'s byte and a zero, a string cut at
+ * its first NUL with zeros behind it - every byte of every tuple is written), copies the tuples once into pinned memory, which the
+ * result view then hands out, and keeps them on the device for rsq_query_result_text / _write and `tofile`.  An ORDER BY above the
+ * materialisation that rsq_ctx_set_order_limit did not decide runs the reference's quicksort over the pinned tuples in place
+ * (sorted_on_host; the device's copy is then not in the result's order and is not read).  An execution under setting 1 takes the host
+ * path - reported, never an error - for SHAPE: an aggregation, no materialisation, more than 64 materialised columns, a shard of
+ * rsq_multi_*, rsq_query_execute_partial, a sub-query's own execution (a nested-loops inner side, a derived table); SMALL: no rows,
+ * or output columns in host-mapped memory (results of up to 256 KB of cells per column: the host has them already); DOES_NOT_FIT:
+ * 2^32 rows or more, rows x tuple size above 2 GiB (rpack::MAX_TUPLE_BYTES), or that many bytes not free on the device with 1 GiB to
+ * spare; ORDER_LIMIT: rsq_ctx_set_order_limit decided the answer from its candidates and no materialised row was packed at all.
+ * 0: host (the default - the launches, copies and bytes of earlier versions), 1: device; else RSQ_ERR_INVALID naming "result_pack".
+ * A setter, not a field: rsq_config keeps its size.  Read at every execution: it holds for statements compiled earlier too.  The
+ * device and pinned buffers are the context's arenas', kept by the query between executions, grown on demand and given back with it
+ * and not before: a query that has run under setting 1 keeps them (up to 2 GiB each) beside the host path's buffers while later
+ * executions run under setting 0 or fall back. */
+int  rsq_ctx_set_result_pack(rsq_ctx* ctx, int32_t where);
+enum rsq_result_pack_fallback { RSQ_RESULT_PACK_FALLBACK_NONE = 0, RSQ_RESULT_PACK_FALLBACK_SHAPE = 1, RSQ_RESULT_PACK_FALLBACK_SMALL = 2,
+                                RSQ_RESULT_PACK_FALLBACK_DOES_NOT_FIT = 3, RSQ_RESULT_PACK_FALLBACK_ORDER_LIMIT = 4 };
+typedef struct rsq_result_pack_report {
+    uint32_t struct_size;            /* sizeof(rsq_result_pack_report), set by the caller: no more than that many bytes are written */
+    int32_t  planned;                /* 1: the compiled plan is of the eligible shape (known after compile, also on a compile-only context) */
+    int32_t  path;                   /* of the last execution - 0: the host packed the tuples; 1: the device did */
+    int32_t  fallback_reason;        /* rsq_result_pack_fallback: why an execution under setting 1 took the host path (0: it did not) */
+    int32_t  sorted_on_host;         /* 1: an ORDER BY above the materialisation ran the reference's quicksort over the delivered tuples */
+    int32_t  tuple_size;             /* the packed relation: bytes per tuple, ... */
+    int64_t  rows, tuple_bytes;      /* ... its rows (behind ORDER BY's LIMIT) and rows x tuple_size (planned shapes; else 0) */
+    /* ms, device path.  kernel_ms: HIP events around the pack kernel; copy_ms: the host's wait and the copy of the tuples; sort_ms: the host's sort */
+    double   kernel_ms, copy_ms, sort_ms;
+} rsq_result_pack_report;
+int  rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out);
 /* The slot order of the reference's aggregation hash table (allocateHashTable / ht_put / growHashTable, src/qlib/hash.h:225-287,
  * 330-419) after inserting n groups with the given Values::hash values in this order into a table allocated for min_size
  * entries: out[k] = index of the group in the k-th occupied slot.  parallel != 0 takes the cluster-parallel replay the engine's
@@ -545,6 +582,12 @@ int   rsq_prim_column_topk(rsq_ctx* ctx, const void* key /* [n * key_width] */, 
                            int64_t capacity, const void* payload /* [n * payload_width] */, int32_t payload_width,
                            uint32_t* positions_out /* [capacity] */, void* payload_out /* [capacity * payload_width] */, uint64_t* cand_count,
                            uint64_t* threshold_image, uint32_t* notes);
+/* The materialisation's device tail over host columns (result_pack.hip, rsq_ctx_set_result_pack): columns[c] holds n_rows cells of
+ * types[c] at the column's width (BOOL / CHAR(1) 1, INT / DATE 4, BIGINT / DECIMAL 8, CHAR(n) / VARCHAR(n) n bytes); each is uploaded
+ * into a device buffer that ends with its last cell, and the kernel packs the tuples into a device buffer of n_rows x tuple size + 64
+ * bytes filled with 0xEE before the launch.  out receives all of it, the 64 guard bytes included: out_bytes must be exactly that.
+ * 1 to 64 columns, 0 <= n_rows < 2^31, at most 2 GiB of tuples. */
+int   rsq_prim_pack_tuples(rsq_ctx* ctx, const void* const* columns, const rsq_type* types, int32_t n_cols, int64_t n_rows, void* out, int64_t out_bytes);
 /* What the statistics pass left beside a column (aot_kernels.hip computeColumnStats), copied back as it lies: which 0 the narrow image
  * (rows values of `width` bytes, each the row's value minus `base`), 1 the dictionary's entries (as many as the column has, each as wide as
  * the column, in memcmp order), 2 the dictionary codes (one byte per row).  info = {width in bytes (0: no narrow image), base, dictionary
@@ -609,6 +652,7 @@ int  rsq_db_report(const rsq_db* db, rsq_report* out);          /* of the last S
 int  rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out);      /* of the last BULK INSERT (out->struct_size set by the caller) */
 int  rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out);      /* of the last SELECT that `tofile` wrote (likewise) */
 int  rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out);      /* of the last SELECT (likewise) */
+int  rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out);      /* of the last SELECT (likewise) */
 void rsq_db_destroy(rsq_db* db);
 
 /* ---- one host process, N GPUs ------------------------------------------------------------------

@@ -209,6 +209,9 @@ public:
     // where an ORDER BY ... LIMIT k over a materialisation is decided: 0 the host sorts every row (the default), 1 from the candidates
     // the device selects (rsq_ctx_set_order_limit; same relation).  Read at every execution, also of statements compiled earlier.
     void setOrderLimit(int where) { check(rsq_ctx_set_order_limit(ctx_, where)); }
+    // where a materialisation's result tuples are packed: 0 on the host from columns copied one by one (the default), 1 on the device,
+    // copied once (rsq_ctx_set_result_pack; same relation).  Read at every execution, also of statements compiled earlier.
+    void setResultPack(int where) { check(rsq_ctx_set_result_pack(ctx_, where)); }
 
     // BULK INSERT (execute.h:332-388) straight into device columns: the Relation object stays the table's identity
     // (plans scan it), its rows live on the GPU only.  Same field rules as the reference's loop (csrc/tbl.cpp).  A second

@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "sqlfront.h"
 #include "hostref.h"
+#include "result_pack.h"
 
 using namespace rsq;
 
@@ -644,7 +645,7 @@ int rsq_query_result_text(rsq_query* q, const rsq_result_text_options* options, 
         queryResult(*QH(q)->q, &view);
         TextOut out;
         rsq_result_text_report rep{};
-        writeResultText(cx, view, opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
+        writeResultText(cx, view, queryResultDeviceTuples(*QH(q)->q), opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
         handTextReport(rep, report);
         *text_bytes = (int64_t)out.size;
         *text = out.release();
@@ -663,7 +664,7 @@ int rsq_query_result_write(rsq_query* q, const char* path, const rsq_result_text
         out.file = fopen(path, "w");
         if (!out.file) failInvalid(std::string("Could not open file ") + path);
         rsq_result_text_report rep{};
-        writeResultText(cx, view, opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
+        writeResultText(cx, view, queryResultDeviceTuples(*QH(q)->q), opt.mode == 2 || (opt.mode == 0 && cx.resultText == 1), opt.chunk_rows, opt.max_device_bytes, out, rep);
         out.closeFile();
         handTextReport(rep, report);
     });
@@ -700,6 +701,26 @@ int rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out
         if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_order_limit_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_order_limit_report)");
         rsq_order_limit_report r{};
         queryOrderLimitReport(*h->q, &r);
+        r.struct_size = out->struct_size;
+        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    });
+}
+
+int rsq_ctx_set_result_pack(rsq_ctx* ctx, int32_t where) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid("result_pack is " + std::to_string(where) + " (0: a materialisation's result tuples are packed on the host, 1: on the device)");
+        C(ctx)->resultPack = where;
+    });
+}
+
+int rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out) {
+    if (!q || !out) return RSQ_ERR_INVALID;
+    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
+    return guarded(h->ctx, [&] {
+        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_result_pack_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_result_pack_report)");
+        rsq_result_pack_report r{};
+        queryResultPackReport(*h->q, &r);
         r.struct_size = out->struct_size;
         memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
     });
@@ -970,6 +991,33 @@ int rsq_prim_column_topk(rsq_ctx* ctx, const void* key, int32_t key_width, int64
     });
 }
 
+int rsq_prim_pack_tuples(rsq_ctx* ctx, const void* const* columns, const rsq_type* types, int32_t n_cols, int64_t n_rows, void* out, int64_t out_bytes) {
+    if (!ctx || !columns || !types || !out || n_cols < 1 || n_cols > (int32_t)rpack::MAX_COLUMNS || n_rows < 0 || n_rows >= kPrimMaxItems) return RSQ_ERR_INVALID;
+    for (int32_t c = 0; c < n_cols; c++) if (n_rows > 0 && !columns[c]) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        std::vector<Type> ty;
+        for (int32_t i = 0; i < n_cols; i++) ty.push_back(Type::fromC(types[i]));
+        const int64_t ts = packTupleSize(ty);
+        if (!rpack::fitsDevice(n_rows, ts, INT64_MAX)) failInvalid("rsq_prim_pack_tuples: " + std::to_string((long long)n_rows) + " tuples of " + std::to_string((long long)ts) + " bytes are more than 2 GiB");
+        const size_t bytes = (size_t)n_rows * (size_t)ts, guard = 64;
+        if (out_bytes != (int64_t)(bytes + guard)) failInvalid("rsq_prim_pack_tuples: out_bytes is " + std::to_string((long long)out_bytes) + ", the tuples and their guard take " + std::to_string(bytes + guard));
+        PrimBuffers pb(c);
+        std::vector<const void*> dCols;
+        for (int32_t i = 0; i < n_cols; i++) {
+            const size_t b = (size_t)n_rows * (size_t)columnWidth(ty[(size_t)i]);
+            unsigned char* d = pb.take<unsigned char>(b);
+            if (b) RSQ_HIP(hipMemcpyAsync(d, columns[i], b, hipMemcpyHostToDevice, c.stream));
+            dCols.push_back(d);
+        }
+        unsigned char* dOut = pb.take<unsigned char>(bytes + guard);
+        RSQ_HIP(hipMemsetAsync(dOut, 0xEE, bytes + guard, c.stream));
+        packTuples(c, ty, dCols.data(), n_rows, dOut);
+        RSQ_HIP(hipMemcpyAsync(out, dOut, bytes + guard, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+    });
+}
+
 int rsq_ref_emission_order(const uint64_t* hashes, int64_t n, uint64_t min_size, int32_t parallel, uint32_t* out) {
     if (n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     try {
@@ -1033,6 +1081,7 @@ struct rsq_db {
     rsq_tbl_load_report lastLoad{};          // of the last BULK INSERT
     rsq_result_text_report lastText{};       // of the last SELECT that `tofile` wrote
     rsq_order_limit_report lastOrderLimit{}; // of the last SELECT
+    rsq_result_pack_report lastResultPack{}; // of the last SELECT
     // DBConfig / JitConfig as the control variables set them (execute.h:23-27, JitContextFlounder.h:86-109)
     bool showPlan = false, writeResultsToFile = false;
     uint16_t numThreads = 1;
@@ -1250,6 +1299,14 @@ int rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out) {
     return RSQ_OK;
 }
 
+int rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out) {
+    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
+    rsq_result_pack_report r = db->lastResultPack;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return RSQ_OK;
+}
+
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
 int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_view* result) {
@@ -1340,6 +1397,7 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
     if (selectStatus != RSQ_OK) return selectStatus;
     rsq_query_report(db->last, &db->lastReport);
     queryOrderLimitReport(*QH(db->last)->q, &db->lastOrderLimit);
+    queryResultPackReport(*QH(db->last)->q, &db->lastResultPack);
     rsq_result_view view;
     selectStatus = rsq_query_result(db->last, &view);
     if (selectStatus != RSQ_OK) return selectStatus;
@@ -1348,7 +1406,7 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
             TextOut out;
             out.file = fopen("qres.tbl", "w");
             if (!out.file) failInvalid("Could not open file qres.tbl");
-            writeResultText(*db->ctx, view, db->ctx->resultText == 1, 0, 0, out, db->lastText);          // (the context's setting at 0: serializeResultView, as ever)
+            writeResultText(*db->ctx, view, queryResultDeviceTuples(*QH(db->last)->q), db->ctx->resultText == 1, 0, 0, out, db->lastText);          // (the context's setting at 0: serializeResultView, as ever)
             out.closeFile();
         });
         if (selectStatus != RSQ_OK) return selectStatus;

@@ -8,6 +8,7 @@
 #include <sstream>
 
 #include "engine_internal.h"
+#include "result_pack.h"
 
 namespace rsq {
 
@@ -162,6 +163,10 @@ Query::~Query() {
     if (dPipeStats) ctx.free(dPipeStats);
     if (dGroupCount) ctx.free(dGroupCount);
     orderLimit.buffers.release(ctx);
+    if (resultPack.dev) ctx.free(resultPack.dev);
+    if (resultPack.pinned) ctx.freePinned(resultPack.pinned);
+    if (resultPack.ev0) ctx.giveEvent(resultPack.ev0);
+    if (resultPack.ev1) ctx.giveEvent(resultPack.ev1);
     if (dTopkImages) ctx.free(dTopkImages);
     if (dTopkHists) ctx.free(dTopkHists);
     if (dCandRows) ctx.free(dCandRows);
@@ -448,7 +453,9 @@ static Query* compileSubQuery(Context& ctx, const rsq_plan_desc& plan, int at, r
     rsq_plan_desc sub = plan;
     sub.ops = ops.data(); sub.n_ops = (int32_t)ops.size(); sub.root = root;
     sub.request_all = 1; sub.has_limit = 0; sub.limit = 0;
-    return compileQuery(ctx, sub, tables, nTables);
+    Query* q = compileQuery(ctx, sub, tables, nTables);
+    q->subQuery = true;          // (rsq_ctx_set_result_pack: its columns or host tuples are what the outer statement reads)
+    return q;
 }
 
 // The inner side of a nested-loops join: the sub-query of its left subtree
@@ -571,6 +578,8 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     const double tBuilt0 = nowMs();
     buildPipelines(*q);
     planOrderLimit(*q);
+    q->resultPack.report = rsq_result_pack_report{};
+    q->resultPack.report.planned = !q->agg && q->matOp && !q->matSchema.empty() && q->matSchema.size() <= (size_t)rpack::MAX_COLUMNS;
     const double tBuilt = nowMs();
     // A plan shape whose specialised kernels are not in the code-object cache starts on the pre-compiled generic pipeline
     // (generic.cpp) while hiprtc builds them on a host thread; RSQ_FORCE_GENERIC=1 keeps every eligible plan there (tests),
@@ -804,6 +813,81 @@ static bool orderLimitOnDevice(Query& q) {
     return true;
 }
 
+static void resultPackHostRelation(Query& q) {      // the result-pack report's relation where the host made it
+    rsq_result_pack_report& r = q.resultPack.report;
+    if (!r.planned || q.holdTail) return;
+    r.tuple_size = schemaTupleSize(q.resultSchema); r.rows = q.resultRows; r.tuple_bytes = r.rows * (int64_t)r.tuple_size;
+}
+
+// A materialisation without an aggregation whose columns stand complete in q.dMatCols (whichever tier wrote them), under
+// rsq_ctx_set_result_pack = 1: one launch packs all rows into the query's device buffer (result_pack.hip), one copy brings the tuples
+// into its pinned buffer, and an ORDER BY above runs over them there.  q.hMatCols is neither filled nor read.  False: the host path
+// follows over q.dMatCols - they are untouched - and the report says why.
+static bool resultPackOnDevice(Query& q) {
+    Context& ctx = q.ctx;
+    auto& st = q.resultPack;
+    rsq_result_pack_report& r = st.report;
+    if (ctx.resultPack != 1) return false;
+    r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_SHAPE;
+    if (!r.planned || q.holdTail || q.subQuery || q.dMatCols.size() != q.matSchema.size()) return false;
+    std::vector<Type> types;
+    for (auto& a : q.matSchema) types.push_back(a.type);
+    const int64_t n = q.matRows, ts = packTupleSize(types);
+    bool mapped = false;          // (allocMatCols' form for small capacities: the host has the cells when the stream completes)
+    for (void* m : q.hMatMapped) mapped = mapped || m != nullptr;
+    if (n <= 0 || mapped) { r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_SMALL; return false; }
+    const size_t bytes = (size_t)n * (size_t)ts;          // (at most rpack::MAX_TUPLE_BYTES where fitsDevice says yes)
+    int64_t freeBytes = INT64_MAX;          // what the query holds already is not asked for again
+    if (st.devBytes < bytes) {
+        size_t freeNow = 0, total = 0;
+        RSQ_HIP(hipMemGetInfo(&freeNow, &total));
+        freeBytes = (int64_t)std::min<size_t>(freeNow, (size_t)INT64_MAX);
+    }
+    if (!rpack::fitsDevice(n, ts, freeBytes)) { r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_DOES_NOT_FIT; return false; }
+    q.resultInPinned = false; q.resultDev = nullptr; q.resultRows = 0;          // the last result's tuples go with their buffers' contents
+    if (st.devBytes < bytes) {
+        if (st.dev) ctx.free(st.dev);
+        st.dev = nullptr; st.devBytes = 0;
+        st.dev = (uint8_t*)ctx.alloc(bytes);
+        st.devBytes = bytes;
+    }
+    if (st.pinnedBytes < bytes) {
+        if (st.pinned) ctx.freePinned(st.pinned);
+        st.pinned = nullptr; st.pinnedBytes = 0;
+        st.pinned = (uint8_t*)ctx.allocPinned(bytes);
+        st.pinnedBytes = bytes;
+    }
+    if (!st.ev0) st.ev0 = ctx.takeEvent();
+    if (!st.ev1) st.ev1 = ctx.takeEvent();
+    RSQ_HIP(hipEventRecord(st.ev0, ctx.stream));
+    packTuples(ctx, types, q.dMatCols.data(), n, st.dev);
+    RSQ_HIP(hipEventRecord(st.ev1, ctx.stream));
+    q.report.num_kernels += 1;
+    const double t0 = nowMs();
+    RSQ_HIP(hipMemcpyAsync(st.pinned, st.dev, bytes, hipMemcpyDeviceToHost, ctx.stream));
+    uint32_t err = 0;
+    RSQ_HIP(hipMemcpyAsync(&err, ctx.dErr, 4, hipMemcpyDeviceToHost, ctx.stream));
+    waitForStream(ctx);
+    r.copy_ms = nowMs() - t0;
+    if (err) { ctx.errWordClean = false; checkDeviceError(err); }
+    float ms = 0;
+    RSQ_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+    r.kernel_ms = ms;
+    q.tailNeedsAllGroups = false;
+    q.resultSchema = q.matSchema;
+    int64_t rows = n;
+    const double t1 = nowMs();
+    const bool sorted = runMaterializeSort(q, st.pinned, rows);
+    if (sorted) r.sort_ms = nowMs() - t1;
+    q.resultRows = rows;
+    q.resultPinned = st.pinned;
+    q.resultInPinned = true;
+    q.resultDev = sorted ? nullptr : st.dev;      // (sorted on the host: the device's tuples are not the result's order)
+    r.path = 1; r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_NONE; r.sorted_on_host = sorted ? 1 : 0;
+    r.tuple_size = (int32_t)ts; r.rows = rows; r.tuple_bytes = rows * ts;
+    return true;
+}
+
 void fetchHeldGroupRows(Query& q) {
     if (q.nGroupRows <= 0) return;
     ensureHostGroupRows(q, (size_t)q.nGroupRows * (size_t)q.groupRowWords);
@@ -899,6 +983,8 @@ void writeDerivedFrom(Query& q, DerivedState& d, Query& s, bool deviceTuples) {
     const int64_t n = s.resultRows;
     d.sub.ensureColumns(ctx, t.cols, std::max<int64_t>(n, 1), std::max<int64_t>(n + n / 8, 64));      // (an empty table has its columns too)
     for (size_t c = 0; c < cols.size(); c++) { cols[c].out = d.sub.dCols[c]; t.cols[c].dptr = d.sub.dCols[c]; }
+    // (two producers of resultDev, told apart by pointer: derived sub-queries always have an aggregation, and a sub-query's materialisation
+    // never takes the result-pack tail - RSQ_RESULT_PACK_FALLBACK_SHAPE - so its buffer is not a third case here)
     const uint8_t* tuples = deviceTuples && s.resultInPinned ? s.resultDev : nullptr;
     if (tuples) {      // (the device tail's layout must be the one the writer decodes)
         const int devTuple = tuples == s.dtRows ? s.dtTupleSize : s.rtTupleSize;
@@ -979,6 +1065,12 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         r.path = 0; r.fallback_reason = ctx.orderLimit == 1 ? RSQ_ORDER_LIMIT_FALLBACK_SHAPE : RSQ_ORDER_LIMIT_FALLBACK_NONE;
         r.rows = r.want = r.candidates = r.capacity = 0;
         r.select_ms = r.copy_ms = r.tail_ms = 0;
+    }
+    {   // ... and of the result-pack report: likewise - held tails, partial executions and sub-queries never reach resultPackOnDevice
+        rsq_result_pack_report& r = q.resultPack.report;
+        r.path = 0; r.fallback_reason = ctx.resultPack == 1 ? RSQ_RESULT_PACK_FALLBACK_SHAPE : RSQ_RESULT_PACK_FALLBACK_NONE;
+        r.sorted_on_host = 0; r.tuple_size = 0; r.rows = r.tuple_bytes = 0;
+        r.kernel_ms = r.copy_ms = r.sort_ms = 0;
     }
     runSubQueries(q);
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
@@ -1684,6 +1776,14 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         if (denseMode(q)) tableFromPinned(q);
         else if (q.matOp && !q.agg) {
             if (orderLimitOnDevice(q)) {          // (rsq_ctx_set_order_limit: the candidates decided the answer, no column travels whole)
+                if (ctx.resultPack == 1) q.resultPack.report.fallback_reason = RSQ_RESULT_PACK_FALLBACK_ORDER_LIMIT;      // (no materialised row is packed at all)
+                resultPackHostRelation(q);
+                q.report.finalize_time_ms = nowMs() - t1;
+                q.report.execution_time_ms = nowMs() - t0;
+                execTrace();
+                return;
+            }
+            if (resultPackOnDevice(q)) {          // (rsq_ctx_set_result_pack: the tuples are made on the device and copied once)
                 q.report.finalize_time_ms = nowMs() - t1;
                 q.report.execution_time_ms = nowMs() - t0;
                 execTrace();
@@ -1754,6 +1854,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
             return;
         }
         tailUnlessHeld(q);
+        resultPackHostRelation(q);
         q.report.finalize_time_ms = nowMs() - t1;
     }
     q.report.execution_time_ms = nowMs() - t0;
@@ -1988,6 +2089,11 @@ void queryReport(const Query& q, rsq_report* out) {
     *out = q.report;
 }
 void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out) { *out = q.orderLimit.report; }
+void queryResultPackReport(const Query& q, rsq_result_pack_report* out) { *out = q.resultPack.report; }
+const uint8_t* queryResultDeviceTuples(const Query& q) {
+    // (the query-owned pack buffer only: the aggregation tails' buffers are arena space another statement may be handed)
+    return q.resultInPinned && q.resultDev && q.resultDev == q.resultPack.dev ? q.resultDev : nullptr;
+}
 int32_t queryNestedLoopsSlices(const Query& q) {
     for (const NljState& n : q.nljs) if (n.sub.query && n.outerSrc) return n.slices;      // (the top one: the others run inside its inner side)
     return 0;

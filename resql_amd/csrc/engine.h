@@ -224,6 +224,7 @@ struct Context {
     bool shardCompile = false;
     int32_t resultText = 0;                    // rsq_ctx_set_result_text: 0 results become text on the host, 1 on the device (result_text.hip)
     int32_t rowstoreBridge = 0;                // rsq_ctx_set_rowstore_bridge: 0 row stores are transposed on the host, 1 on the device (rowstore_device.hip)
+    int32_t resultPack = 0;                    // rsq_ctx_set_result_pack: 0 a materialisation's result tuples are packed on the host, 1 on the device (result_pack.hip)
     int32_t orderLimit = 0;                    // rsq_ctx_set_order_limit: 0 ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1 decides from device-selected candidates (order_limit.hip)
 };
 
@@ -419,6 +420,12 @@ struct OrderLimitSelection {
 void orderLimitSelect(Context& ctx, OrderLimitBuffers& b, const void* key, int keyWidth, bool desc, int64_t nRows, uint32_t want,
                       const std::vector<const void*>& src, bool everything, OrderLimitSelection& out);
 
+// result_pack.hip: n rows of struct-of-arrays columns (dCols[c]: nRows cells of columnWidth(types[c]) bytes, device memory) packed into
+// ReSQL tuples at dTuples (nRows x packTupleSize(types) bytes, every byte written) by one launch on the context's stream
+// (rsq_ctx_set_result_pack, rsq_prim_pack_tuples).  1 to rpack::MAX_COLUMNS columns, 0 <= nRows < 2^32.
+int packTupleSize(const std::vector<Type>& types);
+void packTuples(Context& ctx, const std::vector<Type>& types, const void* const* dCols, int64_t nRows, uint8_t* dTuples);
+
 // ---- query ------------------------------------------------------------------------------------
 struct Query;
 Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables);
@@ -464,6 +471,10 @@ void partialBuffer(Query& q, void** dptr, int64_t* nMin, int64_t* nMax, int64_t*
 void queryResult(Query& q, rsq_result_view* out);
 void queryReport(const Query& q, rsq_report* out);
 void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out);      // (struct_size is the caller's business: api.cpp)
+void queryResultPackReport(const Query& q, rsq_result_pack_report* out);      // (likewise)
+// the result view's tuples in device memory, in the view's order, where the materialisation's device tail left them (rsq_ctx_set_result_pack);
+// null: they are on the host only.  Valid until the query's next execution or its destruction.
+const uint8_t* queryResultDeviceTuples(const Query& q);
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset);
 int32_t queryNestedLoopsSlices(const Query& q);      // S of the most recent execution's top nested-loops pipeline (0: none, or not executed yet)
 const char* querySource(const Query& q);
@@ -483,6 +494,7 @@ struct TextOut {
     ~TextOut() { if (file) fclose(file); ::free(buf); }
 };
 // device == false, or a device path that cannot take the view (rep.fallback_reason says why): serializeResultView.  rep is filled either way.
-void writeResultText(Context& ctx, const rsq_result_view& v, bool device, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep);
+// devTuples: the view's tuples in device memory of ctx (queryResultDeviceTuples), or null - the device path then uploads v.tuples
+void writeResultText(Context& ctx, const rsq_result_view& v, const uint8_t* devTuples, bool device, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep);
 
 }  // namespace rsq

@@ -421,6 +421,12 @@ struct Query {
     // ORDER BY ... LIMIT k at the root, decided from candidates selected on the device (rsq_ctx_set_order_limit; tail.cpp planOrderLimit,
     // engine.cpp orderLimitOnDevice, order_limit.hip): the report's plan fields are set when the statement is compiled, the others by every execution
     struct { rsq_order_limit_report report{}; OrderLimitBuffers buffers; } orderLimit;
+    // the materialisation's device tail (rsq_ctx_set_result_pack; engine.cpp resultPackOnDevice, result_pack.hip): `planned` is set when the
+    // statement is compiled, the rest by every execution.  dev and pinned hold the packed tuples; they are the context's arenas', kept
+    // between executions, grown on demand and given back with the query - so q.resultDev == dev stays valid until this query's next execution
+    struct { rsq_result_pack_report report{}; uint8_t* dev = nullptr; size_t devBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0;
+             hipEvent_t ev0 = nullptr, ev1 = nullptr; } resultPack;
+    bool subQuery = false;                 // compiled by compileSubQuery: a nested-loops inner side or a derived table, whose packed result nobody reads from the device tail
 
     // compacted group rows read back from a join-entry aggregation: [nGroups][groupWords]
     int64_t* dGroupRows = nullptr;
@@ -585,6 +591,9 @@ void runRowsTailSort(Query& q, uint8_t* tuples, int64_t& rows);
 void planDeviceTopK(Query& q);
 // tail.cpp: is the plan an ORDER BY ... LIMIT k over a materialisation whose first key the device can order?  (the report's plan fields)
 void planOrderLimit(Query& q);
+// tail.cpp: the ORDER BY above the materialisation (if any) over its packed tuples in place - the reference's quicksort, then the LIMIT
+// cuts `rows`.  True: there is one.  Both tails of a materialisation call it: the host's and the device's (engine.cpp resultPackOnDevice).
+bool runMaterializeSort(Query& q, uint8_t* tuples, int64_t& rows);
 // tail.cpp: the answer from the candidates' columns, or false where rows among the leading k + 1 tie on every key
 bool runOrderLimitTail(Query& q, const uint8_t* const* candCols, size_t nCand);
 

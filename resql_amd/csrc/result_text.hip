@@ -1,6 +1,7 @@
 // result_text.hip — a result relation's '.tbl' text written on the device (rsq_ctx_set_result_text, rsq_query_result_text / _write, the
 // statement loop's `tofile`).  serializeResultView (engine.cpp) stays the definition of the text; the cells' text is result_text.h's,
-// which is checked against it.  The tuples are uploaded in chunks of rows; per chunk:
+// which is checked against it.  The tuples are uploaded in chunks of rows - or, where the materialisation's device tail left them in the
+// query's own device buffer (rsq_ctx_set_result_pack), read there, a chunk beginning at any byte offset; per chunk:
 //   k_text_lengths   one lane per row, TEXT_GROUP_ROWS per workgroup: rowLen[row] = the row's text length (one terminator per cell, one
 //                    newline), groupBytes[workgroup] = the workgroup's total            -> exclusiveScanCounts: every workgroup's first byte
 //   k_text_write     the same geometry: the rows' starts from a scan of rowLen inside the workgroup; where the workgroup's span fits the
@@ -157,14 +158,14 @@ bool textSchemaOf(const rsq_result_view& v, TextSchema& sch, int64_t* rowBound) 
     return true;
 }
 
-// device memory of a chunk of `rows` rows: tuples, text (its upper bound, rounded up to whole 16-byte groups), row lengths, the workgroups' totals
+// device memory of a chunk of `rows` rows: tuples (tupleSize 0: they are on the device already), text (its upper bound, rounded up to whole 16-byte groups), row lengths, the workgroups' totals
 // with their trailing slot, their offsets, the scan's temporary
 size_t chunkDeviceBytes(int64_t rows, int64_t tupleSize, int64_t rowBound) {
     const int64_t groups = (rows + TEXT_GROUP_ROWS - 1) / TEXT_GROUP_ROWS;
     return (size_t)(rows * tupleSize + 16) + (size_t)(rows * rowBound + 32) + (size_t)rows * 4 + (size_t)(groups + 1) * 12 + 64 + scanTempBytes(groups + 1);
 }
 
-bool textOnDevice(Context& ctx, const rsq_result_view& v, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep) {
+bool textOnDevice(Context& ctx, const rsq_result_view& v, const uint8_t* devTuples, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep) {
     if (ctx.device < 0) { rep.fallback_reason = RSQ_TEXT_FALLBACK_NO_DEVICE; return false; }
     TextSchema sch{};
     int64_t rowBound = 0;
@@ -182,14 +183,15 @@ bool textOnDevice(Context& ctx, const rsq_result_view& v, int64_t chunkRows, int
     int64_t rows = chunkRows > 0 ? chunkRows : std::max<int64_t>(TEXT_GROUP_ROWS, ((int64_t)64 << 20) / rowBound);
     rows = std::min<int64_t>(rows, (int64_t)0xffffffffll / rowBound);
     rows = std::max<int64_t>(1, std::min<int64_t>(rows, nRows));
-    while (rows > 1 && chunkDeviceBytes(rows, v.tuple_size, rowBound) > limit) rows /= 2;
-    if (chunkDeviceBytes(rows, v.tuple_size, rowBound) > limit) { rep.fallback_reason = RSQ_TEXT_FALLBACK_DOES_NOT_FIT; return false; }
-    rep.path = 1; rep.rows = nRows;
+    const int64_t uploaded = devTuples ? 0 : v.tuple_size;          // bytes per row the chunk's tuple buffer takes
+    while (rows > 1 && chunkDeviceBytes(rows, uploaded, rowBound) > limit) rows /= 2;
+    if (chunkDeviceBytes(rows, uploaded, rowBound) > limit) { rep.fallback_reason = RSQ_TEXT_FALLBACK_DOES_NOT_FIT; return false; }
+    rep.path = 1; rep.rows = nRows; rep.tuples_from_device = devTuples ? 1 : 0;
     if (nRows == 0) return true;
 
     TextWork w(ctx);
     const int64_t groupsMax = (rows + TEXT_GROUP_ROWS - 1) / TEXT_GROUP_ROWS;
-    unsigned char* dTuples = (unsigned char*)w.device((size_t)(rows * v.tuple_size + 16));
+    unsigned char* dTuples = devTuples ? nullptr : (unsigned char*)w.device((size_t)(rows * v.tuple_size + 16));
     unsigned char* dText = (unsigned char*)w.device((size_t)(rows * rowBound + 32));
     unsigned* dRowLen = (unsigned*)w.device((size_t)rows * 4);
     unsigned* dGroupBytes = (unsigned*)w.device((size_t)(groupsMax + 1) * 4);
@@ -200,13 +202,15 @@ bool textOnDevice(Context& ctx, const rsq_result_view& v, int64_t chunkRows, int
     for (int64_t r0 = 0; r0 < nRows; r0 += rows) {
         const int64_t n = std::min<int64_t>(rows, nRows - r0);
         const int64_t groups = (n + TEXT_GROUP_ROWS - 1) / TEXT_GROUP_ROWS;
+        // the chunk's tuples: uploaded, or where they lie (the kernels address tuples + row x tupleSize per lane; rtxt:: loads cells at any byte address - unaligned 4- and 8-byte loads)
+        const unsigned char* chunk = devTuples ? devTuples + (size_t)r0 * (size_t)v.tuple_size : dTuples;
         RSQ_HIP(hipEventRecord(w.ev[0], ctx.stream));
-        if (v.tuple_size > 0) RSQ_HIP(hipMemcpyAsync(dTuples, v.tuples + (size_t)r0 * (size_t)v.tuple_size, (size_t)n * (size_t)v.tuple_size, hipMemcpyHostToDevice, ctx.stream));
+        if (!devTuples && v.tuple_size > 0) RSQ_HIP(hipMemcpyAsync(dTuples, v.tuples + (size_t)r0 * (size_t)v.tuple_size, (size_t)n * (size_t)v.tuple_size, hipMemcpyHostToDevice, ctx.stream));
         RSQ_HIP(hipEventRecord(w.ev[1], ctx.stream));
         RSQ_HIP(hipMemsetAsync(dGroupBytes + groups, 0, 4, ctx.stream));          // (the trailing slot: dGroupStart[groups] = the chunk's bytes)
-        hipLaunchKernelGGL(k_text_lengths, dim3((unsigned)groups), dim3(TEXT_GROUP_ROWS), 0, ctx.stream, (const unsigned char*)dTuples, (i64)n, sch, dRowLen, dGroupBytes);
+        hipLaunchKernelGGL(k_text_lengths, dim3((unsigned)groups), dim3(TEXT_GROUP_ROWS), 0, ctx.stream, chunk, (i64)n, sch, dRowLen, dGroupBytes);
         exclusiveScanCounts(ctx, dGroupBytes, dGroupStart, groups + 1, dTemp, scanTempBytes(groups + 1));
-        hipLaunchKernelGGL(k_text_write, dim3((unsigned)groups), dim3(TEXT_GROUP_ROWS), 0, ctx.stream, (const unsigned char*)dTuples, (i64)n, sch, (const unsigned*)dRowLen,
+        hipLaunchKernelGGL(k_text_write, dim3((unsigned)groups), dim3(TEXT_GROUP_ROWS), 0, ctx.stream, chunk, (i64)n, sch, (const unsigned*)dRowLen,
                            (const u64*)dGroupStart, dText);
         RSQ_HIP(hipGetLastError());
         RSQ_HIP(hipEventRecord(w.ev[2], ctx.stream));
@@ -218,7 +222,7 @@ bool textOnDevice(Context& ctx, const rsq_result_view& v, int64_t chunkRows, int
         RSQ_HIP(hipEventRecord(w.ev[3], ctx.stream));
         RSQ_HIP(hipStreamSynchronize(ctx.stream));
         float ms = 0;
-        RSQ_HIP(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); rep.upload_ms += ms;
+        if (!devTuples) { RSQ_HIP(hipEventElapsedTime(&ms, w.ev[0], w.ev[1])); rep.upload_ms += ms; }
         RSQ_HIP(hipEventElapsedTime(&ms, w.ev[1], w.ev[2])); rep.kernel_ms += ms;
         RSQ_HIP(hipEventElapsedTime(&ms, w.ev[2], w.ev[3])); rep.download_ms += ms;
         const auto t0 = std::chrono::steady_clock::now();
@@ -232,10 +236,10 @@ bool textOnDevice(Context& ctx, const rsq_result_view& v, int64_t chunkRows, int
 
 }  // namespace
 
-void writeResultText(Context& ctx, const rsq_result_view& v, bool device, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep) {
+void writeResultText(Context& ctx, const rsq_result_view& v, const uint8_t* devTuples, bool device, int64_t chunkRows, int64_t maxDeviceBytes, TextOut& out, rsq_result_text_report& rep) {
     const auto started = std::chrono::steady_clock::now();
     rep = rsq_result_text_report{};
-    if (!device || !textOnDevice(ctx, v, chunkRows, maxDeviceBytes, out, rep)) {
+    if (!device || !textOnDevice(ctx, v, devTuples, chunkRows, maxDeviceBytes, out, rep)) {
         // the host path: all of it (a device path gives up before it has written anything; its reason stays in the report)
         const std::string text = serializeResultView(v);
         out.append(text.data(), text.size());

@@ -366,6 +366,15 @@ static std::vector<OrderRequest> materializeOrderRequests(const Schema& cur, OpN
     return reqs;
 }
 
+bool runMaterializeSort(Query& q, uint8_t* tuples, int64_t& rows) {
+    OpNode* orderBy = materializeOrderBy(q);
+    if (!orderBy) return false;
+    const std::vector<OrderRequest> reqs = materializeOrderRequests(q.matSchema, orderBy);
+    refQuicksort(tuples, rows, (size_t)schemaTupleSize(q.matSchema), reqs);
+    if (orderBy->hasLimit && rows > orderBy->limit) rows = orderBy->limit;
+    return true;
+}
+
 // plans without aggregation: the device delivered the materialised columns in scan order; pack ReSQL tuples and
 // apply ORDER BY / LIMIT of an OrderByOp above (orderby.h:87-136)
 static void runMaterializeTail(Query& q) {
@@ -382,15 +391,7 @@ static void runMaterializeTail(Query& q) {
     parallelFor(n, tailThreads(n), [&](size_t lo, size_t hi, int) {
         if (lo < hi) columnsToTuples(types, cols.data(), lo, hi, &q.resultTuples[lo * ts], ts);
     });
-    OpNode* orderBy = materializeOrderBy(q);
-    if (orderBy) {
-        const std::vector<OrderRequest> reqs = materializeOrderRequests(cur, orderBy);
-        refQuicksort(q.resultTuples.data(), q.resultRows, ts, reqs);
-        if (orderBy->hasLimit && q.resultRows > orderBy->limit) {
-            q.resultRows = orderBy->limit;
-            q.resultTuples.resize((size_t)q.resultRows * ts);
-        }
-    }
+    if (runMaterializeSort(q, q.resultTuples.data(), q.resultRows)) q.resultTuples.resize((size_t)q.resultRows * ts);
 }
 
 // `ORDER BY ... LIMIT k` at the root of a plan WITHOUT an aggregation (rsq_ctx_set_order_limit): can the rows that decide the answer be

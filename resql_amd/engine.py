@@ -118,6 +118,21 @@ ORDER_LIMIT_HOST, ORDER_LIMIT_DEVICE = 0, 1      # Context.set_order_limit
  ORDER_LIMIT_FALLBACK_TIES) = range(5)
 
 
+class rsq_result_pack_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
+                ("sorted_on_host", C.c_int32), ("tuple_size", C.c_int32), ("rows", C.c_int64), ("tuple_bytes", C.c_int64),
+                ("kernel_ms", C.c_double), ("copy_ms", C.c_double), ("sort_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+RESULT_PACK_HOST, RESULT_PACK_DEVICE = 0, 1      # Context.set_result_pack
+# rsq_result_pack_fallback: why an execution under set_result_pack(1) packed its result tuples on the host
+(RESULT_PACK_FALLBACK_NONE, RESULT_PACK_FALLBACK_SHAPE, RESULT_PACK_FALLBACK_SMALL, RESULT_PACK_FALLBACK_DOES_NOT_FIT,
+ RESULT_PACK_FALLBACK_ORDER_LIMIT) = range(5)
+
+
 class rsq_memory_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("device_slab_bytes", C.c_uint64), ("device_used_bytes", C.c_uint64),
                 ("device_slab_allocs", C.c_uint64), ("pinned_slab_bytes", C.c_uint64), ("pinned_used_bytes", C.c_uint64),
@@ -233,6 +248,10 @@ def lib():
         L.rsq_query_order_limit_report.argtypes = [vp, C.POINTER(rsq_order_limit_report)]
         L.rsq_db_order_limit_report.argtypes = [vp, C.POINTER(rsq_order_limit_report)]
         L.rsq_prim_column_topk.argtypes = [vp, vp, i32, i64, i32, i64, i64, vp, i32, vp, vp, vp, vp, vp]
+        L.rsq_ctx_set_result_pack.argtypes = [vp, i32]
+        L.rsq_query_result_pack_report.argtypes = [vp, C.POINTER(rsq_result_pack_report)]
+        L.rsq_db_result_pack_report.argtypes = [vp, C.POINTER(rsq_result_pack_report)]
+        L.rsq_prim_pack_tuples.argtypes = [vp, vp, vp, i32, i64, vp, i64]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
         L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
@@ -300,6 +319,7 @@ EXPORTED_SYMBOLS = [
     "rsq_prim_exclusive_scan", "rsq_prim_rank_index", "rsq_prim_rank_place",
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select", "rsq_prim_column_topk",
     "rsq_ctx_set_order_limit", "rsq_query_order_limit_report", "rsq_db_order_limit_report",
+    "rsq_ctx_set_result_pack", "rsq_query_result_pack_report", "rsq_db_result_pack_report", "rsq_prim_pack_tuples",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_load_report", "rsq_db_destroy",
@@ -469,6 +489,29 @@ class Context:
                                                  payload.ctypes.data, width, positions.ctypes.data, out.ctypes.data, C.addressof(count),
                                                  C.addressof(threshold), C.addressof(notes)))
         return positions, out, count.value, threshold.value, notes.value
+
+    def prim_pack_tuples(self, columns, types) -> np.ndarray:
+        """the materialisation's device tail over host columns (rsq_prim_pack_tuples): columns[c] the cells of types[c] (plan.SqlType) as
+        a contiguous array of n_rows x width bytes; returns the device's buffer as uint8 [n_rows * tuple size + 64] - the packed tuples
+        and, behind them, 64 guard bytes that are still 0xEE where the kernel kept to its range"""
+        cols = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in columns]
+        if len(cols) != len(types) or not cols:
+            raise ValueError("prim_pack_tuples: one column per type")
+        n = len(cols[0]) // types[0].width
+        for c, t in zip(cols, types):
+            if len(c) != n * t.width:
+                raise ValueError("prim_pack_tuples: every column holds n_rows cells of its type's width")
+        ts = sum(2 if (t.tag == P.CHAR and t.len == 1) else t.width + 1 if t.tag in (P.CHAR, P.VARCHAR) else t.width for t in types)
+        out = np.zeros(n * ts + 64, dtype=np.uint8)
+        ptrs = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+        ctypes_ = (P.rsq_type * len(types))(*[t.c() for t in types])
+        self._check(self._L.rsq_prim_pack_tuples(self.h, ptrs, ctypes_, len(types), n, out.ctypes.data, len(out)))
+        return out
+
+    def set_result_pack(self, where: int):
+        """where a materialisation's result tuples are packed: 0 on the host from columns copied one by one (the default), 1 on the
+        device, copied once (rsq_ctx_set_result_pack).  Read at every execution; Query.result_pack_report says which path ran and why"""
+        self._check(self._L.rsq_ctx_set_result_pack(self.h, where))
 
     def set_order_limit(self, where: int):
         """where an ORDER BY ... LIMIT k over a materialisation is decided: 0 the host sorts every row (the default), 1 from candidates
@@ -823,6 +866,13 @@ class Query:
         self.ctx._check(self.ctx._L.rsq_query_order_limit_report(self.h, C.byref(r)))
         return r.as_dict()
 
+    def result_pack_report(self) -> dict:
+        """rsq_result_pack_report: whether the plan is a materialisation the device can pack, and for the last execution which side
+        packed the result tuples, why, whether the host sorted them, the relation's size and the phases"""
+        r = rsq_result_pack_report(C.sizeof(rsq_result_pack_report))
+        self.ctx._check(self.ctx._L.rsq_query_result_pack_report(self.h, C.byref(r)))
+        return r.as_dict()
+
     def kernel_time_stats(self, reset: bool = False):
         """(device ms summed over the executions since the last reset, number of executions)"""
         s, n = C.c_double(0), C.c_uint64(0)
@@ -910,6 +960,12 @@ class Database:
         """rsq_order_limit_report of the last SELECT: which path decided its ORDER BY ... LIMIT, why, rows, candidates, phase times"""
         r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
         self.ctx._check(self.ctx._L.rsq_db_order_limit_report(self.h, C.byref(r)))
+        return r.as_dict()
+
+    def result_pack_report(self) -> dict:
+        """rsq_result_pack_report of the last SELECT: which side packed its result tuples, why, the relation's size, phase times"""
+        r = rsq_result_pack_report(C.sizeof(rsq_result_pack_report))
+        self.ctx._check(self.ctx._L.rsq_db_result_pack_report(self.h, C.byref(r)))
         return r.as_dict()
 
     def execute_script(self, text: str):
