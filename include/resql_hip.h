@@ -398,7 +398,8 @@ void  rsq_free(void* p);
  * however the call ends.  The call takes the host path - reported, never an error - where the context has no device, the schema
  * is outside the device form (more than 64 columns, CHAR of length 0, a DECIMAL scale above 18, a row whose text may exceed
  * 64 KiB), or a chunk of one row does not fit max_device_bytes.  Where the materialisation's device tail (rsq_ctx_set_result_pack)
- * made the result and no ORDER BY reordered it on the host, the kernels read the tuples in the query's own device buffer, chunk by
+ * made the result and no ORDER BY reordered it on the host, or the device sort (rsq_ctx_set_order_sort) delivered it in the ORDER BY's
+ * order, the kernels read the tuples in the query's own device buffer, chunk by
  * chunk at any byte offset: no tuple buffer is allocated, nothing is uploaded, tuples_from_device is 1 and upload_ms 0.  That buffer is
  * the query's from the execution until its next execution or its destruction, whatever other statements run in between.  Every other
  * result - the aggregation tails' among them, whose arena space is not the query's to keep - is uploaded from the host copy the result
@@ -508,6 +509,51 @@ typedef struct rsq_result_pack_report {
     double   kernel_ms, copy_ms, sort_ms;
 } rsq_result_pack_report;
 int  rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out);
+/* ORDER BY over a materialisation (a plan without an aggregation whose root is an ORDER BY directly above the MATERIALIZE, with any
+ * LIMIT or none), optionally sorted on the DEVICE (opt-in: rsq_ctx_set_order_sort).  The host path packs every materialised row into a
+ * tuple and runs the reference's quicksort over all of them on one thread; it stays the definition of the answer.  The device path
+ * rests on the rule the aggregation tails and rsq_ctx_set_order_limit use: the reference's sorted order is determined by the sort keys
+ * alone wherever no two adjacent rows of it tie on ALL keys.  Every key's cell becomes an image in which "earlier" is "smaller"
+ * (resql_amd/csrc/order_sort.h: the complement of order_limit.h's image, the cell read at its own width); one pass finds every key's
+ * least and greatest image; key j then takes 64 - clz(max_j - min_j) bits, the keys' (image - min) are concatenated, first key most
+ * significant, and the string is cut into 64-bit words from its least significant end; the rows are ordered by a stable LSD radix sort
+ * over the words (8 bits a pass, only the bits a word holds), so the device's order is "keys, then scan order"; a kernel counts the
+ * positions among the leading `lead` rows - all rows without a LIMIT, min(rows, k + 1) with LIMIT k - whose row and successor are equal
+ * on every key; all rows are packed into tuples in scan order (the kernel of rsq_ctx_set_result_pack, whatever that setting says) and
+ * the leading out_rows = min(rows, k) tuples are gathered in the order into a device buffer the query keeps, copied once into pinned
+ * memory, which the result view hands out, and read in place by rsq_query_result_text / _write and `tofile` (tuples_from_device 1).
+ * An execution under setting 1 takes the host path - reported, never an error, the materialised columns untouched - for SHAPE: the
+ * plan is not eligible (an aggregation, no ORDER BY at the root directly above the materialisation, a LIMIT on the materialisation
+ * itself, no key or more than 8, a key that is not a materialised INT / DATE / BIGINT / DECIMAL attribute - strings, CHAR(1) and BOOL
+ * compare by rules that are not a byte order -, more than 64 materialised columns) or the execution is not (a shard of rsq_multi_*,
+ * rsq_query_execute_partial, a sub-query's own execution); SMALL: no rows, or output columns in host-mapped memory; DOES_NOT_FIT:
+ * 2^32 rows or more, rows x tuple size above 2 GiB, or the sort's and the tuples' buffers not free on the device with 1 GiB to spare
+ * (order_sort.h fitsDevice, asked before anything is allocated); TIES: tied_pairs > 0 - the passes have been paid and the host's
+ * quicksort over all tuples follows, through rsq_ctx_set_result_pack where that is set; ORDER_LIMIT: rsq_ctx_set_order_limit decided the
+ * answer first (where it fell back - FEW_ROWS, OVERFLOW, TIES, a LIMIT above 2^20 - this path runs next).
+ * 0: host (the default - the launches, copies and bytes of earlier versions), 1: device; else RSQ_ERR_INVALID naming "order_sort".
+ * A setter, not a field: rsq_config keeps its size.  Read at every execution: it holds for statements compiled earlier too.  The
+ * device and pinned buffers are the context's arenas', kept by the query between executions, grown on demand and given back with it. */
+int  rsq_ctx_set_order_sort(rsq_ctx* ctx, int32_t where);
+enum rsq_order_sort_fallback { RSQ_ORDER_SORT_FALLBACK_NONE = 0, RSQ_ORDER_SORT_FALLBACK_SHAPE = 1, RSQ_ORDER_SORT_FALLBACK_SMALL = 2,
+                               RSQ_ORDER_SORT_FALLBACK_DOES_NOT_FIT = 3, RSQ_ORDER_SORT_FALLBACK_TIES = 4, RSQ_ORDER_SORT_FALLBACK_ORDER_LIMIT = 5 };
+typedef struct rsq_order_sort_report {
+    uint32_t struct_size;            /* sizeof(rsq_order_sort_report), set by the caller: no more than that many bytes are written */
+    int32_t  planned;                /* 1: the compiled plan is of the eligible shape (known after compile, also on a compile-only context) */
+    int32_t  path;                   /* of the last execution - 0: the host sorted the tuples; 1: the device ordered the rows */
+    int32_t  fallback_reason;        /* rsq_order_sort_fallback: why an execution under setting 1 took the host path (0: it did not) */
+    int32_t  keys;                   /* planned: the ORDER BY's keys (else 0) */
+    int32_t  key_bits[8];            /* of the last device sort: bits key j takes in the composite key (0: it does not vary) */
+    int32_t  total_bits, words, passes;      /* ... their sum, its 64-bit words, the 8-bit radix passes taken */
+    int32_t  tuple_size;             /* bytes per tuple of the materialised relation */
+    int32_t  reserved;
+    int64_t  rows, lead, out_rows;   /* materialised rows; leading rows checked for ties; rows of the result relation */
+    int64_t  tied_pairs;             /* positions i, i + 1 < lead, whose rows are equal on every key */
+    /* ms, device path.  range_ms, sort_ms (key words, passes, tie count), pack_ms, gather_ms: HIP events around the kernels; copy_ms: the
+     * host's wait and the copy of the tuples */
+    double   range_ms, sort_ms, pack_ms, gather_ms, copy_ms;
+} rsq_order_sort_report;
+int  rsq_query_order_sort_report(const rsq_query* q, rsq_order_sort_report* out);
 /* The slot order of the reference's aggregation hash table (allocateHashTable / ht_put / growHashTable, src/qlib/hash.h:225-287,
  * 330-419) after inserting n groups with the given Values::hash values in this order into a table allocated for min_size
  * entries: out[k] = index of the group in the k-th occupied slot.  parallel != 0 takes the cluster-parallel replay the engine's
@@ -588,6 +634,19 @@ int   rsq_prim_column_topk(rsq_ctx* ctx, const void* key /* [n * key_width] */, 
  * bytes filled with 0xEE before the launch.  out receives all of it, the 64 guard bytes included: out_bytes must be exactly that.
  * 1 to 64 columns, 0 <= n_rows < 2^31, at most 2 GiB of tuples. */
 int   rsq_prim_pack_tuples(rsq_ctx* ctx, const void* const* columns, const rsq_type* types, int32_t n_cols, int64_t n_rows, void* out, int64_t out_bytes);
+/* The device's order of column-wise rows (order_sort.hip, rsq_ctx_set_order_sort): columns[c] holds n_rows cells of types[c] at the
+ * column's width; key_columns[j] names the j-th sort key, an INT / DATE / BIGINT / DECIMAL column, descending[j] != 0 its direction;
+ * 1 to 8 keys.  perm_out[i] = the row that is i-th by "keys, then scan order"; *tied_pairs = the positions i, i + 1 < lead, whose rows
+ * are equal on every key; key_bits[j] the bits key j takes in the composite key (8 entries are written), *words its 64-bit words.  Where
+ * no key varies and lead > 1 nothing is sorted: the identity and lead - 1.  0 <= lead <= n_rows < 2^31. */
+int   rsq_prim_sort_rows(rsq_ctx* ctx, const void* const* columns, const rsq_type* types, int32_t n_cols, const int32_t* key_columns,
+                         const int32_t* descending, int32_t n_keys, int64_t n_rows, int64_t lead, uint32_t* perm_out /* [n_rows] */,
+                         int64_t* tied_pairs, int32_t* key_bits /* [8] */, int32_t* words);
+/* out tuple i = tuple perm[i] of `tuples` (n_rows tuples of tuple_size bytes) for i < n_out (order_sort.hip k_os_gather_tuples); every
+ * perm[i] must be below n_rows.  The device's output buffer holds n_out x tuple_size + 64 bytes filled with 0xEE before the launch; out
+ * receives all of it, the 64 guard bytes included: out_bytes must be exactly that.  0 <= n_out <= n_rows < 2^31, at most 2 GiB of tuples. */
+int   rsq_prim_gather_tuples(rsq_ctx* ctx, const void* tuples, int32_t tuple_size, int64_t n_rows, const uint32_t* perm, int64_t n_out,
+                             void* out, int64_t out_bytes);
 /* What the statistics pass left beside a column (aot_kernels.hip computeColumnStats), copied back as it lies: which 0 the narrow image
  * (rows values of `width` bytes, each the row's value minus `base`), 1 the dictionary's entries (as many as the column has, each as wide as
  * the column, in memcmp order), 2 the dictionary codes (one byte per row).  info = {width in bytes (0: no narrow image), base, dictionary
@@ -653,6 +712,7 @@ int  rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out);      /* of 
 int  rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out);      /* of the last SELECT that `tofile` wrote (likewise) */
 int  rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out);      /* of the last SELECT (likewise) */
 int  rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out);      /* of the last SELECT (likewise) */
+int  rsq_db_order_sort_report(const rsq_db* db, rsq_order_sort_report* out);        /* of the last SELECT (likewise) */
 void rsq_db_destroy(rsq_db* db);
 
 /* ---- one host process, N GPUs ------------------------------------------------------------------

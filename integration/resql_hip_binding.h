@@ -212,6 +212,10 @@ public:
     // where a materialisation's result tuples are packed: 0 on the host from columns copied one by one (the default), 1 on the device,
     // copied once (rsq_ctx_set_result_pack; same relation).  Read at every execution, also of statements compiled earlier.
     void setResultPack(int where) { check(rsq_ctx_set_result_pack(ctx_, where)); }
+    // where an ORDER BY over a materialisation is sorted: 0 the host's quicksort over all tuples (the default), 1 the device orders the
+    // rows by their keys and delivers the tuples in that order (rsq_ctx_set_order_sort; same relation - rows that tie on every key take the
+    // host path).  Read at every execution, also of statements compiled earlier.
+    void setOrderSort(int where) { check(rsq_ctx_set_order_sort(ctx_, where)); }
 
     // BULK INSERT (execute.h:332-388) straight into device columns: the Relation object stays the table's identity
     // (plans scan it), its rows live on the GPU only.  Same field rules as the reference's loop (csrc/tbl.cpp).  A second

@@ -10,6 +10,7 @@
 #include "sqlfront.h"
 #include "hostref.h"
 #include "result_pack.h"
+#include "order_sort.h"
 
 using namespace rsq;
 
@@ -726,6 +727,26 @@ int rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out
     });
 }
 
+int rsq_ctx_set_order_sort(rsq_ctx* ctx, int32_t where) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid("order_sort is " + std::to_string(where) + " (0: an ORDER BY over a materialisation sorts the tuples on the host, 1: the device orders the rows)");
+        C(ctx)->orderSort = where;
+    });
+}
+
+int rsq_query_order_sort_report(const rsq_query* q, rsq_order_sort_report* out) {
+    if (!q || !out) return RSQ_ERR_INVALID;
+    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
+    return guarded(h->ctx, [&] {
+        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_order_sort_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_order_sort_report)");
+        rsq_order_sort_report r{};
+        queryOrderSortReport(*h->q, &r);
+        r.struct_size = out->struct_size;
+        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    });
+}
+
 int rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t n, uint64_t min_size, uint32_t* out) {
     if (!ctx || n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     return guarded(C(ctx), [&] {
@@ -1018,6 +1039,73 @@ int rsq_prim_pack_tuples(rsq_ctx* ctx, const void* const* columns, const rsq_typ
     });
 }
 
+int rsq_prim_sort_rows(rsq_ctx* ctx, const void* const* columns, const rsq_type* types, int32_t n_cols, const int32_t* key_columns, const int32_t* descending,
+                       int32_t n_keys, int64_t n_rows, int64_t lead, uint32_t* perm_out, int64_t* tied_pairs, int32_t* key_bits, int32_t* words) {
+    if (!ctx || !columns || !types || !key_columns || !descending || !tied_pairs || !key_bits || !words || n_cols < 1 || n_cols > (int32_t)rpack::MAX_COLUMNS ||
+        n_keys < 1 || n_keys > (int32_t)osort::MAX_KEYS || n_rows < 0 || n_rows >= kPrimMaxItems || lead < 0 || lead > n_rows || (n_rows > 0 && !perm_out))
+        return RSQ_ERR_INVALID;
+    for (int32_t k = 0; k < n_keys; k++) if (key_columns[k] < 0 || key_columns[k] >= n_cols || (n_rows > 0 && !columns[key_columns[k]])) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        std::vector<int> width;
+        for (int32_t k = 0; k < n_keys; k++) {
+            const Type t = Type::fromC(types[key_columns[k]]);
+            if (t.tag != RSQ_INT && t.tag != RSQ_DATE && t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) failInvalid("rsq_prim_sort_rows: key " + std::to_string(k) + " is not an INT, DATE, BIGINT or DECIMAL column");
+            width.push_back(columnWidth(t));
+        }
+        *tied_pairs = 0; *words = 0;
+        for (int k = 0; k < (int)osort::MAX_KEYS; k++) key_bits[k] = 0;
+        if (n_rows == 0) return;
+        PrimBuffers pb(c);
+        std::vector<OrderSortKey> keys;
+        for (int32_t k = 0; k < n_keys; k++) {          // (the key columns only: the sort reads no other)
+            const size_t b = (size_t)n_rows * (size_t)width[(size_t)k];
+            unsigned char* d = pb.take<unsigned char>(b);
+            RSQ_HIP(hipMemcpyAsync(d, columns[key_columns[k]], b, hipMemcpyHostToDevice, c.stream));
+            keys.push_back(OrderSortKey{d, width[(size_t)k], descending[k] != 0});
+        }
+        OrderSortBuffers b;
+        struct Release { Context& c; OrderSortBuffers& b; ~Release() { (void)hipStreamSynchronize(c.stream); b.release(c); } } release{c, b};
+        b.ensure(c, n_rows);
+        OrderSortOutcome o;
+        orderSortRows(c, b, keys.data(), n_keys, n_rows, lead, o);
+        for (int32_t k = 0; k < n_keys; k++) key_bits[k] = o.bits[k];
+        *words = o.words;
+        if (!o.sorted) {
+            for (int64_t i = 0; i < n_rows; i++) perm_out[i] = (uint32_t)i;
+            *tied_pairs = o.tiedPairs;
+            primSync(c);
+            return;
+        }
+        uint32_t ties = 0;
+        RSQ_HIP(hipMemcpyAsync(perm_out, o.dPerm, (size_t)n_rows * 4, hipMemcpyDeviceToHost, c.stream));
+        if (lead > 1) RSQ_HIP(hipMemcpyAsync(&ties, o.dTies, 4, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+        *tied_pairs = ties;
+    });
+}
+
+int rsq_prim_gather_tuples(rsq_ctx* ctx, const void* tuples, int32_t tuple_size, int64_t n_rows, const uint32_t* perm, int64_t n_out, void* out, int64_t out_bytes) {
+    if (!ctx || !out || tuple_size < 1 || n_rows < 0 || n_rows >= kPrimMaxItems || n_out < 0 || n_out > n_rows || (n_rows > 0 && !tuples) || (n_out > 0 && !perm)) return RSQ_ERR_INVALID;
+    for (int64_t i = 0; i < n_out; i++) if ((int64_t)perm[i] >= n_rows) return RSQ_ERR_INVALID;          // (the kernel trusts the permutation)
+    return guarded(C(ctx), [&] {
+        Context& c = primContext(ctx);
+        if (!rpack::fitsDevice(n_rows, tuple_size, INT64_MAX)) failInvalid("rsq_prim_gather_tuples: " + std::to_string((long long)n_rows) + " tuples of " + std::to_string(tuple_size) + " bytes are more than 2 GiB");
+        const size_t inBytes = (size_t)n_rows * (size_t)tuple_size, bytes = (size_t)n_out * (size_t)tuple_size, guard = 64;
+        if (out_bytes != (int64_t)(bytes + guard)) failInvalid("rsq_prim_gather_tuples: out_bytes is " + std::to_string((long long)out_bytes) + ", the tuples and their guard take " + std::to_string(bytes + guard));
+        PrimBuffers pb(c);
+        unsigned char* dIn = pb.take<unsigned char>(inBytes);
+        uint32_t* dPerm = pb.take<uint32_t>((size_t)n_out);
+        unsigned char* dOut = pb.take<unsigned char>(bytes + guard);
+        if (inBytes) RSQ_HIP(hipMemcpyAsync(dIn, tuples, inBytes, hipMemcpyHostToDevice, c.stream));
+        if (n_out) RSQ_HIP(hipMemcpyAsync(dPerm, perm, (size_t)n_out * 4, hipMemcpyHostToDevice, c.stream));
+        RSQ_HIP(hipMemsetAsync(dOut, 0xEE, bytes + guard, c.stream));
+        gatherTuples(c, dIn, dOut, dPerm, tuple_size, n_out);
+        RSQ_HIP(hipMemcpyAsync(out, dOut, bytes + guard, hipMemcpyDeviceToHost, c.stream));
+        primSync(c);
+    });
+}
+
 int rsq_ref_emission_order(const uint64_t* hashes, int64_t n, uint64_t min_size, int32_t parallel, uint32_t* out) {
     if (n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
     try {
@@ -1082,6 +1170,7 @@ struct rsq_db {
     rsq_result_text_report lastText{};       // of the last SELECT that `tofile` wrote
     rsq_order_limit_report lastOrderLimit{}; // of the last SELECT
     rsq_result_pack_report lastResultPack{}; // of the last SELECT
+    rsq_order_sort_report lastOrderSort{};   // of the last SELECT
     // DBConfig / JitConfig as the control variables set them (execute.h:23-27, JitContextFlounder.h:86-109)
     bool showPlan = false, writeResultsToFile = false;
     uint16_t numThreads = 1;
@@ -1307,6 +1396,14 @@ int rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out) {
     return RSQ_OK;
 }
 
+int rsq_db_order_sort_report(const rsq_db* db, rsq_order_sort_report* out) {
+    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
+    rsq_order_sort_report r = db->lastOrderSort;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return RSQ_OK;
+}
+
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
 int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_view* result) {
@@ -1398,6 +1495,7 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
     rsq_query_report(db->last, &db->lastReport);
     queryOrderLimitReport(*QH(db->last)->q, &db->lastOrderLimit);
     queryResultPackReport(*QH(db->last)->q, &db->lastResultPack);
+    queryOrderSortReport(*QH(db->last)->q, &db->lastOrderSort);
     rsq_result_view view;
     selectStatus = rsq_query_result(db->last, &view);
     if (selectStatus != RSQ_OK) return selectStatus;

@@ -225,6 +225,7 @@ struct Context {
     int32_t resultText = 0;                    // rsq_ctx_set_result_text: 0 results become text on the host, 1 on the device (result_text.hip)
     int32_t rowstoreBridge = 0;                // rsq_ctx_set_rowstore_bridge: 0 row stores are transposed on the host, 1 on the device (rowstore_device.hip)
     int32_t resultPack = 0;                    // rsq_ctx_set_result_pack: 0 a materialisation's result tuples are packed on the host, 1 on the device (result_pack.hip)
+    int32_t orderSort = 0;                     // rsq_ctx_set_order_sort: 0 an ORDER BY over a materialisation sorts the tuples on the host, 1 the device orders the rows and delivers the tuples (order_sort.hip)
     int32_t orderLimit = 0;                    // rsq_ctx_set_order_limit: 0 ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1 decides from device-selected candidates (order_limit.hip)
 };
 
@@ -426,6 +427,36 @@ void orderLimitSelect(Context& ctx, OrderLimitBuffers& b, const void* key, int k
 int packTupleSize(const std::vector<Type>& types);
 void packTuples(Context& ctx, const std::vector<Type>& types, const void* const* dCols, int64_t nRows, uint8_t* dTuples);
 
+// order_sort.hip: the rows of column-wise keys ordered on the device (rsq_ctx_set_order_sort, rsq_prim_sort_rows): the composite key of
+// order_sort.h, an LSD radix sort over its 64-bit words (radixSortPairs), and the tuples gathered in that order.
+// device and pinned buffers of a sort, from the context's arenas; their owner keeps them between sorts and releases them
+struct OrderSortBuffers {
+    uint64_t* dKeys[2] = {nullptr, nullptr};   // [rows] the word being sorted, both sides of the passes
+    uint32_t* dPerm[2] = {nullptr, nullptr};   // [rows] the permutation, likewise
+    void* dTemp = nullptr; size_t tempBytes = 0;      // radixSortTempBytes(rows)
+    int64_t rows = 0;                          // rows the five above provide for
+    uint64_t* dStatus = nullptr;               // [8] least images, [8] greatest images, the tie count
+    uint64_t* hStatus = nullptr;               // pinned: the images as they come back
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // range [0, 1], sort and ties [2, 3]; [4], [5] are the owner's
+    void ensure(Context& ctx, int64_t nRows);
+    void release(Context& ctx);
+};
+struct OrderSortKey { const void* ptr; int width; bool desc; };      // nRows cells of 4 (signed 32 bits) or 8 (signed 64 bits) bytes in device memory
+struct OrderSortOutcome {
+    int bits[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // per key: 64 - clz(greatest image - least image)
+    int totalBits = 0, words = 0, passes = 0;  // of the composite key; the 8-bit radix passes its words take
+    int launches = 0;                          // kernels launched
+    bool sorted = true;                        // false: no key varies and lead > 1 - nothing was sorted, tiedPairs = lead - 1, dPerm is null
+    int64_t tiedPairs = 0;                     // (where sorted is false; else the count is at dTies when the stream has drained)
+    const uint32_t* dPerm = nullptr;           // [nRows] row dPerm[i] is the i-th of the order "keys, then scan order"
+    const uint32_t* dTies = nullptr;           // positions i, i + 1 < lead, whose rows dPerm[i] and dPerm[i + 1] are equal on every key
+};
+// 1 to 8 keys, 1 <= nRows < 2^32, 0 <= lead <= nRows; b.ensure()d for nRows.  Waits for the stream once (the keys' ranges decide the passes).
+void orderSortRows(Context& ctx, OrderSortBuffers& b, const OrderSortKey* keys, int nKeys, int64_t nRows, int64_t lead, OrderSortOutcome& out);
+// dOut tuple i = dIn tuple dPerm[i] for i < outRows, tuples of tupleSize bytes at any byte address; every dPerm[i] is below the tuples at
+// dIn.  One launch on the context's stream; nothing outside [dOut, dOut + outRows x tupleSize) is written.  0 <= outRows < 2^32.
+void gatherTuples(Context& ctx, const uint8_t* dIn, uint8_t* dOut, const uint32_t* dPerm, int tupleSize, int64_t outRows);
+
 // ---- query ------------------------------------------------------------------------------------
 struct Query;
 Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* tables, int nTables);
@@ -472,7 +503,9 @@ void queryResult(Query& q, rsq_result_view* out);
 void queryReport(const Query& q, rsq_report* out);
 void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out);      // (struct_size is the caller's business: api.cpp)
 void queryResultPackReport(const Query& q, rsq_result_pack_report* out);      // (likewise)
-// the result view's tuples in device memory, in the view's order, where the materialisation's device tail left them (rsq_ctx_set_result_pack);
+void queryOrderSortReport(const Query& q, rsq_order_sort_report* out);        // (likewise)
+// the result view's tuples in device memory, in the view's order, where the materialisation's device tail left them (rsq_ctx_set_result_pack,
+// rsq_ctx_set_order_sort);
 // null: they are on the host only.  Valid until the query's next execution or its destruction.
 const uint8_t* queryResultDeviceTuples(const Query& q);
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset);

@@ -426,6 +426,12 @@ struct Query {
     // between executions, grown on demand and given back with the query - so q.resultDev == dev stays valid until this query's next execution
     struct { rsq_result_pack_report report{}; uint8_t* dev = nullptr; size_t devBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0;
              hipEvent_t ev0 = nullptr, ev1 = nullptr; } resultPack;
+    // ORDER BY above the materialisation, sorted on the device (rsq_ctx_set_order_sort; tail.cpp planOrderSort, engine.cpp orderSortOnDevice,
+    // order_sort.hip): `planned`, `keys` and keyCols / keyDesc are set when the statement is compiled, the rest by every execution.  dScan holds
+    // the tuples in scan order, dOut and pinned the result's; all are the context's arenas', kept between executions, grown on demand and
+    // given back with the query - so q.resultDev == dOut stays valid until this query's next execution
+    struct { rsq_order_sort_report report{}; OrderSortBuffers buffers; std::vector<int> keyCols; std::vector<bool> keyDesc;
+             uint8_t* dScan = nullptr; size_t scanBytes = 0; uint8_t* dOut = nullptr; size_t outBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0; } orderSort;
     bool subQuery = false;                 // compiled by compileSubQuery: a nested-loops inner side or a derived table, whose packed result nobody reads from the device tail
 
     // compacted group rows read back from a join-entry aggregation: [nGroups][groupWords]
@@ -591,6 +597,8 @@ void runRowsTailSort(Query& q, uint8_t* tuples, int64_t& rows);
 void planDeviceTopK(Query& q);
 // tail.cpp: is the plan an ORDER BY ... LIMIT k over a materialisation whose first key the device can order?  (the report's plan fields)
 void planOrderLimit(Query& q);
+// tail.cpp: is the plan an ORDER BY directly above a materialisation whose every key the device can order?  (the report's plan fields, the key columns)
+void planOrderSort(Query& q);
 // tail.cpp: the ORDER BY above the materialisation (if any) over its packed tuples in place - the reference's quicksort, then the LIMIT
 // cuts `rows`.  True: there is one.  Both tails of a materialisation call it: the host's and the device's (engine.cpp resultPackOnDevice).
 bool runMaterializeSort(Query& q, uint8_t* tuples, int64_t& rows);

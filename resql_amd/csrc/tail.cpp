@@ -13,6 +13,7 @@
 #include "engine_internal.h"
 #include "hostpar.h"
 #include "order_limit.h"
+#include "order_sort.h"
 
 namespace rsq {
 
@@ -419,6 +420,36 @@ void planOrderLimit(Query& q) {
         r.planned = 1;
         return;
     }
+}
+
+// ORDER BY at the root of a plan WITHOUT an aggregation, directly above the materialisation, with any LIMIT or none
+// (rsq_ctx_set_order_sort): can the device order the rows by the whole key list (order_sort.hip)?  Every key must be, as
+// materializeOrderRequests resolves it - by name, the first attribute that carries it -, a materialised attribute the device can order:
+// INT / DATE as signed 32 bits, BIGINT / DECIMAL as signed 64 bits, the order of compareTyped.  A string, CHAR(1) or BOOL key anywhere in
+// the list keeps the host path (compareTyped orders strings by (int)(int8_t)strcmp(...), which is not a byte order and is not restated),
+// and a name the materialisation does not hold keeps the reference's error.  Fills the compile-time fields of the query's report.
+void planOrderSort(Query& q) {
+    rsq_order_sort_report& r = q.orderSort.report;
+    r = rsq_order_sort_report{};
+    q.orderSort.keyCols.clear(); q.orderSort.keyDesc.clear();
+    if (q.agg || !q.matOp || !q.root || q.root->tag != RSQ_OP_ORDERBY || q.matOp->parent != q.root) return;
+    const OpNode* orderBy = q.root;
+    if ((orderBy->hasLimit && orderBy->limit < 0) || q.matOp->hasLimit || orderBy->exprs.empty() || orderBy->exprs.size() > (size_t)osort::MAX_KEYS) return;
+    if (q.matSchema.empty() || q.matSchema.size() > (size_t)rpack::MAX_COLUMNS) return;
+    std::vector<int> cols;
+    std::vector<bool> desc;
+    for (const Expr* e : orderBy->exprs) {
+        if (!e->child) return;
+        int at = -1;
+        for (size_t c = 0; c < q.matSchema.size() && at < 0; c++) if (q.matSchema[c].name == e->child->symbol) at = (int)c;
+        if (at < 0) return;
+        const Type& t = q.matSchema[(size_t)at].type;
+        if (t.tag != RSQ_INT && t.tag != RSQ_DATE && t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) return;
+        cols.push_back(at); desc.push_back(e->tag == RSQ_E_DESC);
+    }
+    q.orderSort.keyCols = cols; q.orderSort.keyDesc = desc;
+    r.keys = (int32_t)cols.size();
+    r.planned = 1;
 }
 
 // The decision of runTailOn's candidate path over the rows the device selected: candCols are the candidates' cells of every

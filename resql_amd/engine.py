@@ -133,6 +133,25 @@ RESULT_PACK_HOST, RESULT_PACK_DEVICE = 0, 1      # Context.set_result_pack
  RESULT_PACK_FALLBACK_ORDER_LIMIT) = range(5)
 
 
+class rsq_order_sort_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
+                ("keys", C.c_int32), ("key_bits", C.c_int32 * 8), ("total_bits", C.c_int32), ("words", C.c_int32), ("passes", C.c_int32),
+                ("tuple_size", C.c_int32), ("reserved", C.c_int32), ("rows", C.c_int64), ("lead", C.c_int64), ("out_rows", C.c_int64),
+                ("tied_pairs", C.c_int64), ("range_ms", C.c_double), ("sort_ms", C.c_double), ("pack_ms", C.c_double),
+                ("gather_ms", C.c_double), ("copy_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+        d["key_bits"] = list(self.key_bits)
+        return d
+
+
+ORDER_SORT_HOST, ORDER_SORT_DEVICE = 0, 1      # Context.set_order_sort
+# rsq_order_sort_fallback: why an execution under set_order_sort(1) sorted its tuples on the host
+(ORDER_SORT_FALLBACK_NONE, ORDER_SORT_FALLBACK_SHAPE, ORDER_SORT_FALLBACK_SMALL, ORDER_SORT_FALLBACK_DOES_NOT_FIT,
+ ORDER_SORT_FALLBACK_TIES, ORDER_SORT_FALLBACK_ORDER_LIMIT) = range(6)
+
+
 class rsq_memory_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("device_slab_bytes", C.c_uint64), ("device_used_bytes", C.c_uint64),
                 ("device_slab_allocs", C.c_uint64), ("pinned_slab_bytes", C.c_uint64), ("pinned_used_bytes", C.c_uint64),
@@ -252,6 +271,11 @@ def lib():
         L.rsq_query_result_pack_report.argtypes = [vp, C.POINTER(rsq_result_pack_report)]
         L.rsq_db_result_pack_report.argtypes = [vp, C.POINTER(rsq_result_pack_report)]
         L.rsq_prim_pack_tuples.argtypes = [vp, vp, vp, i32, i64, vp, i64]
+        L.rsq_ctx_set_order_sort.argtypes = [vp, i32]
+        L.rsq_query_order_sort_report.argtypes = [vp, C.POINTER(rsq_order_sort_report)]
+        L.rsq_db_order_sort_report.argtypes = [vp, C.POINTER(rsq_order_sort_report)]
+        L.rsq_prim_sort_rows.argtypes = [vp, vp, vp, i32, vp, vp, i32, i64, i64, vp, vp, vp, vp]
+        L.rsq_prim_gather_tuples.argtypes = [vp, vp, i32, i64, vp, i64, vp, i64]
         L.rsq_ref_emission_order.argtypes = [vp, i64, C.c_uint64, i32, vp]
         L.rsq_ref_emission_order_device.argtypes = [vp, vp, i64, C.c_uint64, vp]
         L.rsq_prim_exclusive_scan.argtypes = [vp, vp, i64, i32, vp, vp]
@@ -320,6 +344,7 @@ EXPORTED_SYMBOLS = [
     "rsq_prim_radix_sort_pairs", "rsq_prim_running_min", "rsq_prim_merge_group_rows", "rsq_prim_topk_select", "rsq_prim_column_topk",
     "rsq_ctx_set_order_limit", "rsq_query_order_limit_report", "rsq_db_order_limit_report",
     "rsq_ctx_set_result_pack", "rsq_query_result_pack_report", "rsq_db_result_pack_report", "rsq_prim_pack_tuples",
+    "rsq_ctx_set_order_sort", "rsq_query_order_sort_report", "rsq_db_order_sort_report", "rsq_prim_sort_rows", "rsq_prim_gather_tuples",
     "rsq_measure_read_bandwidth",
     "rsq_sql_plan_select", "rsq_sql_plan_desc", "rsq_sql_plan_destroy", "rsq_sql_plan_text", "rsq_sql_compile", "rsq_sql_describe",
     "rsq_db_create", "rsq_db_execute", "rsq_db_message", "rsq_db_adopt_table", "rsq_db_report", "rsq_db_load_report", "rsq_db_destroy",
@@ -507,6 +532,44 @@ class Context:
         ctypes_ = (P.rsq_type * len(types))(*[t.c() for t in types])
         self._check(self._L.rsq_prim_pack_tuples(self.h, ptrs, ctypes_, len(types), n, out.ctypes.data, len(out)))
         return out
+
+    def prim_sort_rows(self, columns, types, key_columns, descending, lead=None):
+        """the device's order of column-wise rows (rsq_prim_sort_rows): columns[c] the cells of types[c] (plan.SqlType) as a contiguous
+        array of n_rows x width bytes, key_columns / descending the sort keys.  Returns (perm uint32 [n_rows], tied pairs among the
+        leading `lead` rows (default: all), bits per key [8], 64-bit words of the composite key)"""
+        cols = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in columns]
+        if len(cols) != len(types) or not cols or len(key_columns) != len(descending):
+            raise ValueError("prim_sort_rows: one column per type, one direction per key")
+        n = len(cols[0]) // types[0].width
+        for c, t in zip(cols, types):
+            if len(c) != n * t.width:
+                raise ValueError("prim_sort_rows: every column holds n_rows cells of its type's width")
+        perm = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        ptrs = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+        ctypes_ = (P.rsq_type * len(types))(*[t.c() for t in types])
+        kc = (C.c_int32 * len(key_columns))(*key_columns)
+        kd = (C.c_int32 * len(descending))(*[1 if d else 0 for d in descending])
+        ties, words, bits = C.c_int64(-1), C.c_int32(-1), (C.c_int32 * 8)()
+        self._check(self._L.rsq_prim_sort_rows(self.h, ptrs, ctypes_, len(types), kc, kd, len(key_columns), n, n if lead is None else lead,
+                                               perm.ctypes.data, C.addressof(ties), C.addressof(bits), C.addressof(words)))
+        return perm[:n], ties.value, list(bits), words.value
+
+    def prim_gather_tuples(self, tuples, tuple_size: int, perm, n_out: int) -> np.ndarray:
+        """out tuple i = tuple perm[i] for i < n_out on the device (rsq_prim_gather_tuples): tuples uint8 [n_rows * tuple_size]; returns
+        the device's buffer as uint8 [n_out * tuple_size + 64] - the gathered tuples and, behind them, 64 guard bytes that are still
+        0xEE where the kernel kept to its range"""
+        tuples = np.ascontiguousarray(tuples).view(np.uint8).reshape(-1)
+        perm = np.ascontiguousarray(perm, dtype=np.uint32)
+        n = len(tuples) // tuple_size
+        out = np.zeros(n_out * tuple_size + 64, dtype=np.uint8)
+        self._check(self._L.rsq_prim_gather_tuples(self.h, tuples.ctypes.data, tuple_size, n, perm.ctypes.data, n_out, out.ctypes.data, len(out)))
+        return out
+
+    def set_order_sort(self, where: int):
+        """where an ORDER BY over a materialisation is sorted: 0 the host's quicksort over all tuples (the default), 1 the device orders
+        the rows by their keys and delivers the tuples (rsq_ctx_set_order_sort).  Read at every execution; Query.order_sort_report says
+        which path ran and why"""
+        self._check(self._L.rsq_ctx_set_order_sort(self.h, where))
 
     def set_result_pack(self, where: int):
         """where a materialisation's result tuples are packed: 0 on the host from columns copied one by one (the default), 1 on the
@@ -866,6 +929,13 @@ class Query:
         self.ctx._check(self.ctx._L.rsq_query_order_limit_report(self.h, C.byref(r)))
         return r.as_dict()
 
+    def order_sort_report(self) -> dict:
+        """rsq_order_sort_report: whether the plan is an ORDER BY the device can sort, and for the last execution which side sorted,
+        why, the composite key's bits, words and passes, the rows, the tied pairs and the phases"""
+        r = rsq_order_sort_report(C.sizeof(rsq_order_sort_report))
+        self.ctx._check(self.ctx._L.rsq_query_order_sort_report(self.h, C.byref(r)))
+        return r.as_dict()
+
     def result_pack_report(self) -> dict:
         """rsq_result_pack_report: whether the plan is a materialisation the device can pack, and for the last execution which side
         packed the result tuples, why, whether the host sorted them, the relation's size and the phases"""
@@ -960,6 +1030,12 @@ class Database:
         """rsq_order_limit_report of the last SELECT: which path decided its ORDER BY ... LIMIT, why, rows, candidates, phase times"""
         r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
         self.ctx._check(self.ctx._L.rsq_db_order_limit_report(self.h, C.byref(r)))
+        return r.as_dict()
+
+    def order_sort_report(self) -> dict:
+        """rsq_order_sort_report of the last SELECT: which side sorted its ORDER BY, why, the composite key, the rows, phase times"""
+        r = rsq_order_sort_report(C.sizeof(rsq_order_sort_report))
+        self.ctx._check(self.ctx._L.rsq_db_order_sort_report(self.h, C.byref(r)))
         return r.as_dict()
 
     def result_pack_report(self) -> dict:

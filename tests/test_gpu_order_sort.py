@@ -1,0 +1,252 @@
+"""ORDER BY over a materialisation sorted on the device (Context.set_order_sort(1); order_sort.hip, engine.cpp orderSortOnDevice).  The
+device path is never compared with itself: every statement is held against (a) the CPU oracle, text and tuples byte for byte, and (b)
+the same compiled statement with the setter at 0, tuples and launches.  Every case names the path and the fallback reason it expects
+(tests/ordersortcases.py) - none may fall back silently - and is executed twice under setting 1, so the warm materialisation and the
+query's kept buffers are covered.  The reference's own answers (tests/golden/order_sort_reference.json) come through the statement loop."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from resql_amd import engine, tpch_full
+from oracle import orc
+
+import ordersortcases as S
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def world(gpu_ctx):
+    host = {k: make() for k, make in S.TABLES.items()}
+    tabs = {k: gpu_ctx.table(v) for k, v in host.items()}
+    yield gpu_ctx, tabs, host
+    for t in tabs.values():
+        t.close()
+
+
+@pytest.fixture(scope="module")
+def oracle_answers(world):
+    """the CPU oracle's answer per statement, computed once"""
+    ctx, tabs, host = world
+    memo = {}
+
+    def answer(sql, name):
+        if sql not in memo:
+            memo[sql] = orc.execute(ctx.sql_plan(sql, [tabs[name]], [host[name]]))
+        return memo[sql]
+    return answer
+
+
+@pytest.fixture(autouse=True)
+def setters_back_at_the_default(gpu_ctx):
+    yield
+    gpu_ctx.set_order_sort(engine.ORDER_SORT_HOST)          # (the context is the session's)
+    gpu_ctx.set_order_limit(engine.ORDER_LIMIT_HOST)
+    gpu_ctx.set_result_pack(engine.RESULT_PACK_HOST)
+    gpu_ctx.set_result_text(0)
+
+
+def launches_of(rep):
+    """kernels of a device sort: the range, one key kernel per word (one where there is none), five per radix pass (histogram, three of
+    the scan, scatter), the tie count where lead > 1, the pack, the gather where rows come back"""
+    return 1 + max(rep["words"], 1) + 5 * rep["passes"] + (rep["lead"] > 1) + 1 + (rep["out_rows"] > 0)
+
+
+def held_against_both_yardsticks(world, oracle_answers, sql, name, order_limit, path, reason):
+    """-> (the statement's report under setting 1, the oracle's result)"""
+    ctx, tabs, host = world
+    want = oracle_answers(sql, name)
+    q = ctx.sql_compile(sql, [tabs[name]])
+    try:
+        assert q.order_sort_report()["planned"] == (0 if reason == S.SHAPE else 1)
+        ctx.set_order_limit(order_limit)
+        ctx.set_order_sort(engine.ORDER_SORT_HOST)
+        q.execute()
+        q.execute()          # (the second is warm, as every execution under setting 1 below)
+        base, rep0, kernels0 = q.result(), q.order_sort_report(), q.report().num_kernels
+        assert base.text == want.text and base.tuples == want.tuples, sql
+        assert rep0["path"] == 0 and rep0["fallback_reason"] == S.NONE and rep0["rows"] == 0 and rep0["sort_ms"] == 0 and rep0["passes"] == 0
+        base_text, text0 = q.result_text(mode=engine.TEXT_DEVICE)          # (the device's text of the host's tuples, uploaded)
+        assert text0["tuples_from_device"] == 0 and base_text.decode("latin1") == want.text.split("\n", 1)[1]
+        ctx.set_order_sort(engine.ORDER_SORT_DEVICE)
+        for execution in range(2):
+            q.execute()
+            got, rep = q.result(), q.order_sort_report()
+            assert got.text == want.text and got.tuples == want.tuples, (sql, execution)
+            assert got.text == base.text and got.tuples == base.tuples
+            assert (rep["path"], rep["fallback_reason"]) == (path, reason), (sql, execution, rep)
+            sorted_here = path == 1 or (reason == S.TIES and rep["total_bits"] > 0)
+            if reason == S.ORDER_LIMIT:
+                assert q.report().num_kernels == kernels0          # (order_limit's launches, which setting 0 made too)
+            elif path == 1:
+                assert q.report().num_kernels == kernels0 + launches_of(rep), (sql, rep)
+            elif not sorted_here:
+                assert q.report().num_kernels == kernels0 and rep["passes"] == 0 and rep["sort_ms"] == 0
+            text, text_rep = q.result_text(mode=engine.TEXT_DEVICE)
+            assert text == base_text
+            assert text_rep["tuples_from_device"] == path
+        ctx.set_order_sort(engine.ORDER_SORT_HOST)          # whatever ran before: the host's tuples, the launches of before, no device pointer left over
+        q.execute()
+        again, rep0 = q.result(), q.order_sort_report()
+        assert again.tuples == want.tuples and (rep0["path"], rep0["fallback_reason"]) == (0, S.NONE) and q.report().num_kernels == kernels0
+        assert q.result_text(mode=engine.TEXT_DEVICE)[1]["tuples_from_device"] == 0
+        return rep, want
+    finally:
+        q.close()
+
+
+@pytest.mark.parametrize("sql,name,order_limit,path,reason", S.DEVICE, ids=[str(i) for i in range(len(S.DEVICE))])
+def test_sorted_on_the_device(world, oracle_answers, sql, name, order_limit, path, reason):
+    rep, want = held_against_both_yardsticks(world, oracle_answers, sql, name, order_limit, path, reason)
+    host = world[2][name]
+    if reason == S.ORDER_LIMIT:
+        assert rep["rows"] == 0 and rep["passes"] == 0 and rep["sort_ms"] == 0
+        return
+    limit = int(sql.rsplit("limit ", 1)[1]) if " limit " in sql else None
+    rows = rep["rows"]
+    if " where " in sql:
+        assert rows == int((host.col("f").data < 80).sum())
+    else:
+        assert rows == host.n_rows
+    assert rep["lead"] == (rows if limit is None else min(rows, limit + 1)) and rep["out_rows"] == (rows if limit is None else min(rows, limit)) == want.n_rows
+    assert rep["tied_pairs"] == 0 and rep["tuple_size"] * want.n_rows == len(want.tuples)
+    assert rep["total_bits"] == sum(rep["key_bits"]) and rep["words"] == (rep["total_bits"] + 63) // 64 and rep["passes"] >= (rep["total_bits"] + 7) // 8
+    assert rep["range_ms"] > 0 and rep["sort_ms"] > 0 and rep["pack_ms"] > 0 and rep["copy_ms"] > 0 and (rep["gather_ms"] > 0 or want.n_rows == 0)
+    if name == "wide":
+        assert rep["key_bits"][:2] == [64, 17] and rep["words"] == 2 and rep["passes"] == 8 + 3
+    if name == "same":          # the first key does not vary: the unique key alone decides
+        assert rep["key_bits"][:2] == [0, 17] and rep["words"] == 1
+    if sql.startswith("select k, u, c25, v from t order by k, u"):          # the bits are numpy's
+        k, u = host.col("k").data, host.col("u").data
+        _, _, bits, words = S.expected_order([k, u], [False, False], 0)
+        assert rep["key_bits"] == bits and rep["words"] == words == 1
+
+
+@pytest.mark.parametrize("sql,name,order_limit,path,reason", S.HOST, ids=[str(i) for i in range(len(S.HOST))])
+def test_the_host_path_runs_and_says_why(world, oracle_answers, sql, name, order_limit, path, reason):
+    rep, want = held_against_both_yardsticks(world, oracle_answers, sql, name, order_limit, path, reason)
+    host = world[2][name]
+    if reason == S.SHAPE:
+        assert rep["rows"] == 0 and rep["keys"] == 0 and rep["range_ms"] == 0
+    elif reason == S.SMALL:          # decided before anything is launched
+        assert rep["rows"] == (0 if " where " in sql else host.n_rows) and rep["range_ms"] == 0 and rep["passes"] == 0
+    else:                            # TIES: the passes have been paid; the count is numpy's
+        limit = int(sql.rsplit("limit ", 1)[1]) if " limit " in sql else None
+        lead = host.n_rows if limit is None else limit + 1
+        key = host.col(sql.split("order by ")[1].split()[0]).data
+        _, tied, bits, _ = S.expected_order([key], [False], lead)
+        assert tied > 0 and (rep["tied_pairs"], rep["lead"], rep["key_bits"]) == (tied, lead, bits)
+        assert rep["sort_ms"] > 0 and rep["passes"] == (bits[0] + 7) // 8 and want.n_rows == (host.n_rows if limit is None else limit)
+
+
+def test_ties_then_result_pack_packs_and_the_host_sorts(world, oracle_answers):
+    """where this path falls back, result_pack behaves as it does without it: its own pack, the host's sort, sorted_on_host"""
+    ctx, tabs, host = world
+    sql, name = S.HOST[0][0], S.HOST[0][1]
+    want = oracle_answers(sql, name)
+    q = ctx.sql_compile(sql, [tabs[name]])
+    try:
+        ctx.set_result_pack(engine.RESULT_PACK_DEVICE)
+        q.execute()
+        alone = q.result_pack_report()
+        assert q.result().tuples == want.tuples and (alone["path"], alone["sorted_on_host"]) == (1, 1)
+        ctx.set_order_sort(engine.ORDER_SORT_DEVICE)
+        q.execute()
+        rep, pack = q.order_sort_report(), q.result_pack_report()
+        assert q.result().tuples == want.tuples
+        assert (rep["path"], rep["fallback_reason"]) == (0, S.TIES) and (pack["path"], pack["sorted_on_host"], pack["rows"]) == (1, 1, alone["rows"])
+        assert q.result_text(mode=engine.TEXT_DEVICE)[1]["tuples_from_device"] == 0
+    finally:
+        q.close()
+
+
+def test_the_setter_is_read_at_every_execution(world, oracle_answers):
+    """compiled under 0, flipped between executions: each execution follows the value it finds"""
+    ctx, tabs, host = world
+    sql, name = S.DEVICE[2][0], S.DEVICE[2][1]
+    want = oracle_answers(sql, name)
+    q = ctx.sql_compile(sql, [tabs[name]])
+    try:
+        for where in (0, 1, 1, 0, 1, 0):
+            ctx.set_order_sort(where)
+            q.execute()
+            got, rep = q.result(), q.order_sort_report()
+            assert got.text == want.text and got.tuples == want.tuples
+            assert (rep["path"], rep["fallback_reason"]) == (where, S.NONE) and (rep["passes"] > 0) == (where == 1)
+    finally:
+        q.close()
+
+
+def test_partial_execution_answers_as_before_and_reports_the_shape(world):
+    ctx, tabs, _ = world
+    q = ctx.sql_compile(S.DEVICE[0][0], [tabs["t"]])
+    try:
+        errors = []
+        for where in (engine.ORDER_SORT_HOST, engine.ORDER_SORT_DEVICE):
+            ctx.set_order_sort(where)
+            with pytest.raises(engine.EngineError) as e:
+                q.execute_partial()
+            errors.append((e.value.status, str(e.value)))
+        assert errors[0] == errors[1] and errors[0][0] == 3
+        rep = q.order_sort_report()
+        assert rep["planned"] == 1 and rep["path"] == 0 and rep["fallback_reason"] == S.SHAPE
+    finally:
+        q.close()
+
+
+def test_the_text_is_read_in_place_and_tofile_writes_the_defaults_bytes(gpu_ctx, tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)                                   # tofile writes "qres.tbl" into the working directory
+    sql = "select w, u, s from wide order by w desc, u"
+    files, reports = [], []
+    other = engine.Context(device=0)
+    try:
+        other.set_order_sort(engine.ORDER_SORT_DEVICE)
+        other.set_result_text(1)
+        for ctx in (gpu_ctx, other):
+            db = engine.Database(ctx)
+            try:
+                db.add_table(ctx.table(S.wide_table()))
+                db.execute("tofile=true")
+                res = db.execute(sql)
+                assert res.n_rows == S.ROWS
+                with open("qres.tbl", "rb") as f:
+                    files.append(f.read())
+                reports.append((db.order_sort_report(), db.result_text_report))
+                os.remove("qres.tbl")
+            finally:
+                db.close()
+    finally:
+        other.close()
+    assert files[0] == files[1] and files[0].count(b"\n") == S.ROWS
+    (sort0, text0), (sort1, text1) = reports
+    assert (sort0["planned"], sort0["path"], text0["path"], text0["tuples_from_device"]) == (1, 0, 0, 0)
+    assert (sort1["planned"], sort1["path"], sort1["fallback_reason"], sort1["out_rows"]) == (1, 1, S.NONE, S.ROWS)
+    assert (text1["path"], text1["tuples_from_device"], text1["upload_ms"], text1["text_bytes"]) == (1, 1, 0, len(files[1]))
+
+
+def test_the_reference_answers_through_the_statement_loop(gpu_ctx):
+    """what the unmodified reference answers for six statements of the eligible shape over the eight-table database, from
+    Database.execute under setting 1, each on the path its case names"""
+    with open(os.path.join(ROOT, "tests", "golden", "order_sort_reference.json")) as f:
+        gold = json.load(f)
+    tables = tpch_full.database(gold["sf"])
+    db = engine.Database(gpu_ctx)
+    try:
+        for k in gold["tables"]:
+            db.add_table(gpu_ctx.table(tables[k]))
+        gpu_ctx.set_order_sort(engine.ORDER_SORT_DEVICE)
+        for case, (sql, path, reason) in zip(gold["cases"], S.GOLD):
+            assert case["sql"] == sql
+            got = db.execute(sql)
+            rep = db.order_sort_report()
+            assert S.gold_matches(case, got.text) and got.n_rows == case["rows"], sql
+            assert (rep["planned"], rep["path"], rep["fallback_reason"]) == (1, path, reason), (sql, rep)
+            assert rep["tied_pairs"] == 0 and (path == 0 or rep["out_rows"] == case["rows"])
+        gpu_ctx.set_order_sort(engine.ORDER_SORT_HOST)
+        got = db.execute(gold["cases"][0]["sql"])
+        assert S.gold_matches(gold["cases"][0], got.text) and db.order_sort_report()["path"] == 0
+    finally:
+        db.close()
