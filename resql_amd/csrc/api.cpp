@@ -196,6 +196,29 @@ Context& primContext(rsq_ctx* ctx) {
 const int64_t kPrimMaxRankBlocks = (int64_t)1171 * RSQ_RANK_CHUNK_BLOCKS;      // a key domain of 2^28 bits (k_rank_blocks_chained)
 const int64_t kPrimMaxItems = (int64_t)1 << 31;      // pairs, values, rows of one call: the kernels' tile and row indices are 32 bits
 const int32_t kPrimMaxStride = 4096;                 // words of a group row (a merge)
+
+// A report handed out: the caller's struct_size bytes of it, struct_size kept (a host built against an older header receives the
+// fields it knows).  False: struct_size is not one a header of this library can have given.
+template <typename R>
+bool copyReportOut(const R& report, R* out) {
+    if (out->struct_size < 8 || out->struct_size > 4096) return false;
+    R r = report;
+    r.struct_size = out->struct_size;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    return true;
+}
+
+// rsq_query_<what>_report: the last execution's, of one of the materialisation's device tails (engine_mattail.cpp)
+template <typename R>
+int queryReportOut(const rsq_query* q, R* out, const char* type) {
+    if (!q || !out) return RSQ_ERR_INVALID;
+    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
+    return guarded(h->ctx, [&] {
+        R r{};
+        queryReport(*h->q, &r);
+        if (!copyReportOut(r, out)) failInvalid(std::string(type) + ".struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(" + type + ")");
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -679,73 +702,31 @@ int rsq_ctx_set_row_cells(rsq_ctx* ctx, int32_t mode) {
     });
 }
 
+// a context's setting of 0 or 1; the refusal of any other value says `name` and, in parentheses, what the two `mean`
+static int setZeroOrOne(rsq_ctx* ctx, int32_t Context::* member, int32_t where, const char* name, const char* means) {
+    if (!ctx) return RSQ_ERR_INVALID;
+    return guarded(C(ctx), [&] {
+        if (where != 0 && where != 1) failInvalid(std::string(name) + " is " + std::to_string(where) + " (" + means + ")");
+        C(ctx)->*member = where;
+    });
+}
+
 int rsq_ctx_set_result_text(rsq_ctx* ctx, int32_t where) {
-    if (!ctx) return RSQ_ERR_INVALID;
-    return guarded(C(ctx), [&] {
-        if (where != 0 && where != 1) failInvalid("result_text is " + std::to_string(where) + " (0: results become text on the host, 1: on the device)");
-        C(ctx)->resultText = where;
-    });
+    return setZeroOrOne(ctx, &Context::resultText, where, "result_text", "0: results become text on the host, 1: on the device");
 }
-
 int rsq_ctx_set_order_limit(rsq_ctx* ctx, int32_t where) {
-    if (!ctx) return RSQ_ERR_INVALID;
-    return guarded(C(ctx), [&] {
-        if (where != 0 && where != 1) failInvalid("order_limit is " + std::to_string(where) + " (0: ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1: decides from candidates selected on the device)");
-        C(ctx)->orderLimit = where;
-    });
+    return setZeroOrOne(ctx, &Context::orderLimit, where, "order_limit", "0: ORDER BY ... LIMIT over a materialisation sorts every row on the host, 1: decides from candidates selected on the device");
 }
-
-int rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out) {
-    if (!q || !out) return RSQ_ERR_INVALID;
-    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
-    return guarded(h->ctx, [&] {
-        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_order_limit_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_order_limit_report)");
-        rsq_order_limit_report r{};
-        queryOrderLimitReport(*h->q, &r);
-        r.struct_size = out->struct_size;
-        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    });
-}
-
 int rsq_ctx_set_result_pack(rsq_ctx* ctx, int32_t where) {
-    if (!ctx) return RSQ_ERR_INVALID;
-    return guarded(C(ctx), [&] {
-        if (where != 0 && where != 1) failInvalid("result_pack is " + std::to_string(where) + " (0: a materialisation's result tuples are packed on the host, 1: on the device)");
-        C(ctx)->resultPack = where;
-    });
+    return setZeroOrOne(ctx, &Context::resultPack, where, "result_pack", "0: a materialisation's result tuples are packed on the host, 1: on the device");
 }
-
-int rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out) {
-    if (!q || !out) return RSQ_ERR_INVALID;
-    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
-    return guarded(h->ctx, [&] {
-        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_result_pack_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_result_pack_report)");
-        rsq_result_pack_report r{};
-        queryResultPackReport(*h->q, &r);
-        r.struct_size = out->struct_size;
-        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    });
-}
-
 int rsq_ctx_set_order_sort(rsq_ctx* ctx, int32_t where) {
-    if (!ctx) return RSQ_ERR_INVALID;
-    return guarded(C(ctx), [&] {
-        if (where != 0 && where != 1) failInvalid("order_sort is " + std::to_string(where) + " (0: an ORDER BY over a materialisation sorts the tuples on the host, 1: the device orders the rows)");
-        C(ctx)->orderSort = where;
-    });
+    return setZeroOrOne(ctx, &Context::orderSort, where, "order_sort", "0: an ORDER BY over a materialisation sorts the tuples on the host, 1: the device orders the rows");
 }
 
-int rsq_query_order_sort_report(const rsq_query* q, rsq_order_sort_report* out) {
-    if (!q || !out) return RSQ_ERR_INVALID;
-    const QueryHandle* h = reinterpret_cast<const QueryHandle*>(q);
-    return guarded(h->ctx, [&] {
-        if (out->struct_size < 8 || out->struct_size > 4096) failInvalid("rsq_order_sort_report.struct_size is " + std::to_string(out->struct_size) + ": set it to sizeof(rsq_order_sort_report)");
-        rsq_order_sort_report r{};
-        queryOrderSortReport(*h->q, &r);
-        r.struct_size = out->struct_size;
-        memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    });
-}
+int rsq_query_order_limit_report(const rsq_query* q, rsq_order_limit_report* out) { return queryReportOut(q, out, "rsq_order_limit_report"); }
+int rsq_query_result_pack_report(const rsq_query* q, rsq_result_pack_report* out) { return queryReportOut(q, out, "rsq_result_pack_report"); }
+int rsq_query_order_sort_report(const rsq_query* q, rsq_order_sort_report* out) { return queryReportOut(q, out, "rsq_order_sort_report"); }
 
 int rsq_ref_emission_order_device(rsq_ctx* ctx, const uint64_t* hashes, int64_t n, uint64_t min_size, uint32_t* out) {
     if (!ctx || n < 0 || (n > 0 && (!hashes || !out))) return RSQ_ERR_INVALID;
@@ -1049,9 +1030,8 @@ int rsq_prim_sort_rows(rsq_ctx* ctx, const void* const* columns, const rsq_type*
         Context& c = primContext(ctx);
         std::vector<int> width;
         for (int32_t k = 0; k < n_keys; k++) {
-            const Type t = Type::fromC(types[key_columns[k]]);
-            if (t.tag != RSQ_INT && t.tag != RSQ_DATE && t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) failInvalid("rsq_prim_sort_rows: key " + std::to_string(k) + " is not an INT, DATE, BIGINT or DECIMAL column");
-            width.push_back(columnWidth(t));
+            width.push_back(deviceOrderWidth(Type::fromC(types[key_columns[k]])));
+            if (!width.back()) failInvalid("rsq_prim_sort_rows: key " + std::to_string(k) + " is not an INT, DATE, BIGINT or DECIMAL column");
         }
         *tied_pairs = 0; *words = 0;
         for (int k = 0; k < (int)osort::MAX_KEYS; k++) key_bits[k] = 0;
@@ -1181,6 +1161,10 @@ struct rsq_db {
 }  // extern "C"
 
 namespace {
+
+// rsq_db_<what>_report: the report the statement loop kept (no message: RSQ_ERR_INVALID alone)
+template <typename R>
+int dbReportOut(const rsq_db* db, R rsq_db::* last, R* out) { return db && out && copyReportOut(db->*last, out) ? RSQ_OK : RSQ_ERR_INVALID; }
 
 // setBoolVar / setIntVar (execute.h:407-451): spaces are removed from the line, the variable name may stand anywhere in it
 // (rfind), the line is either the bare name (prints the value) or name=value
@@ -1364,45 +1348,11 @@ int rsq_db_report(const rsq_db* db, rsq_report* out) {
     return RSQ_OK;
 }
 
-int rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out) {
-    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
-    rsq_tbl_load_report r = db->lastLoad;
-    r.struct_size = out->struct_size;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    return RSQ_OK;
-}
-
-int rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out) {
-    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
-    rsq_result_text_report r = db->lastText;
-    r.struct_size = out->struct_size;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    return RSQ_OK;
-}
-
-int rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out) {
-    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
-    rsq_order_limit_report r = db->lastOrderLimit;
-    r.struct_size = out->struct_size;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    return RSQ_OK;
-}
-
-int rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out) {
-    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
-    rsq_result_pack_report r = db->lastResultPack;
-    r.struct_size = out->struct_size;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    return RSQ_OK;
-}
-
-int rsq_db_order_sort_report(const rsq_db* db, rsq_order_sort_report* out) {
-    if (!db || !out || out->struct_size < 8 || out->struct_size > 4096) return RSQ_ERR_INVALID;
-    rsq_order_sort_report r = db->lastOrderSort;
-    r.struct_size = out->struct_size;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
-    return RSQ_OK;
-}
+int rsq_db_load_report(const rsq_db* db, rsq_tbl_load_report* out) { return dbReportOut(db, &rsq_db::lastLoad, out); }
+int rsq_db_result_text_report(const rsq_db* db, rsq_result_text_report* out) { return dbReportOut(db, &rsq_db::lastText, out); }
+int rsq_db_order_limit_report(const rsq_db* db, rsq_order_limit_report* out) { return dbReportOut(db, &rsq_db::lastOrderLimit, out); }
+int rsq_db_result_pack_report(const rsq_db* db, rsq_result_pack_report* out) { return dbReportOut(db, &rsq_db::lastResultPack, out); }
+int rsq_db_order_sort_report(const rsq_db* db, rsq_order_sort_report* out) { return dbReportOut(db, &rsq_db::lastOrderSort, out); }
 
 const char* rsq_db_message(const rsq_db* db) { return db ? db->message.c_str() : ""; }
 
@@ -1493,9 +1443,9 @@ int rsq_db_execute(rsq_db* db, const char* sqlText, int32_t* kind, rsq_result_vi
     selectStatus = rsq_query_execute(db->last);
     if (selectStatus != RSQ_OK) return selectStatus;
     rsq_query_report(db->last, &db->lastReport);
-    queryOrderLimitReport(*QH(db->last)->q, &db->lastOrderLimit);
-    queryResultPackReport(*QH(db->last)->q, &db->lastResultPack);
-    queryOrderSortReport(*QH(db->last)->q, &db->lastOrderSort);
+    queryReport(*QH(db->last)->q, &db->lastOrderLimit);
+    queryReport(*QH(db->last)->q, &db->lastResultPack);
+    queryReport(*QH(db->last)->q, &db->lastOrderSort);
     rsq_result_view view;
     selectStatus = rsq_query_result(db->last, &view);
     if (selectStatus != RSQ_OK) return selectStatus;

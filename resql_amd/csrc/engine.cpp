@@ -8,8 +8,6 @@
 #include <sstream>
 
 #include "engine_internal.h"
-#include "result_pack.h"
-#include "order_sort.h"
 
 namespace rsq {
 
@@ -163,15 +161,7 @@ Query::~Query() {
     if (hInlineRows) ctx.freePinned(hInlineRows);
     if (dPipeStats) ctx.free(dPipeStats);
     if (dGroupCount) ctx.free(dGroupCount);
-    orderLimit.buffers.release(ctx);
-    orderSort.buffers.release(ctx);
-    if (orderSort.dScan) ctx.free(orderSort.dScan);
-    if (orderSort.dOut) ctx.free(orderSort.dOut);
-    if (orderSort.pinned) ctx.freePinned(orderSort.pinned);
-    if (resultPack.dev) ctx.free(resultPack.dev);
-    if (resultPack.pinned) ctx.freePinned(resultPack.pinned);
-    if (resultPack.ev0) ctx.giveEvent(resultPack.ev0);
-    if (resultPack.ev1) ctx.giveEvent(resultPack.ev1);
+    releaseMaterializeTails(*this);
     if (dTopkImages) ctx.free(dTopkImages);
     if (dTopkHists) ctx.free(dTopkHists);
     if (dCandRows) ctx.free(dCandRows);
@@ -582,10 +572,7 @@ Query* compileQuery(Context& ctx, const rsq_plan_desc& plan, rsq_table* const* t
     }
     const double tBuilt0 = nowMs();
     buildPipelines(*q);
-    planOrderLimit(*q);
-    planOrderSort(*q);
-    q->resultPack.report = rsq_result_pack_report{};
-    q->resultPack.report.planned = !q->agg && q->matOp && !q->matSchema.empty() && q->matSchema.size() <= (size_t)rpack::MAX_COLUMNS;
+    planMaterializeTails(*q);
     const double tBuilt = nowMs();
     // A plan shape whose specialised kernels are not in the code-object cache starts on the pre-compiled generic pipeline
     // (generic.cpp) while hiprtc builds them on a host thread; RSQ_FORCE_GENERIC=1 keeps every eligible plan there (tests),
@@ -787,216 +774,6 @@ static bool fusedEligible(const Query& q) {
 // materialised columns) back, but leaves the tail to the root, which merges all shards' groups first (tail.cpp runTailMerged)
 static void tailUnlessHeld(Query& q) { if (!q.holdTail) runTail(q); }
 
-// ORDER BY ... LIMIT k over a materialisation whose columns stand complete in q.dMatCols (whichever tier wrote them), under
-// rsq_ctx_set_order_limit = 1: the device selects the candidates (order_limit.hip), only they come back, and the tail decides from them
-// (tail.cpp runOrderLimitTail).  False: the host path follows over all of q.dMatCols - they are untouched - and the report says why.
-static bool orderLimitOnDevice(Query& q) {
-    Context& ctx = q.ctx;
-    rsq_order_limit_report& r = q.orderLimit.report;
-    if (ctx.orderLimit != 1) return false;
-    r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_SHAPE;
-    const int64_t n = q.matRows;
-    if (!r.planned || q.holdTail || n >= ((int64_t)1 << 32) || q.dMatCols.size() != q.matSchema.size()) return false;
-    const int64_t limit = q.root->limit, want = limit + 1;
-    const int64_t capacity = std::max<int64_t>(4 * want, 65536);
-    r.rows = n; r.want = want; r.capacity = capacity;
-    if (4 * limit >= n) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_FEW_ROWS; return false; }      // (the rule of tail.cpp runTailOn)
-    std::vector<int32_t> widths;
-    std::vector<const void*> src;
-    for (size_t c = 0; c < q.matSchema.size(); c++) { widths.push_back(columnWidth(q.matSchema[c].type)); src.push_back(q.dMatCols[c]); }
-    OrderLimitBuffers& b = q.orderLimit.buffers;
-    b.ensure(ctx, n, capacity, widths);
-    OrderLimitSelection s;
-    orderLimitSelect(ctx, b, q.dMatCols[(size_t)r.first_key_column], r.key_is32 ? 4 : 8, r.descending != 0, n, (uint32_t)want, src, false, s);
-    q.report.num_kernels += 10;      // six digit histograms, the threshold, the counts, their scan, the gather
-    r.candidates = (int64_t)s.candidates; r.select_ms = s.selectMs; r.copy_ms = s.copyMs;
-    if (s.candidates > (uint64_t)capacity) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_OVERFLOW; return false; }
-    const double t0 = nowMs();
-    const bool decided = runOrderLimitTail(q, s.cols.data(), (size_t)s.candidates);
-    r.tail_ms = nowMs() - t0;
-    if (!decided) { r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_TIES; return false; }
-    r.path = 1; r.fallback_reason = RSQ_ORDER_LIMIT_FALLBACK_NONE;
-    return true;
-}
-
-static void resultPackHostRelation(Query& q) {      // the result-pack report's relation where the host made it
-    rsq_result_pack_report& r = q.resultPack.report;
-    if (!r.planned || q.holdTail) return;
-    r.tuple_size = schemaTupleSize(q.resultSchema); r.rows = q.resultRows; r.tuple_bytes = r.rows * (int64_t)r.tuple_size;
-}
-
-// A materialisation without an aggregation whose columns stand complete in q.dMatCols (whichever tier wrote them), under
-// rsq_ctx_set_result_pack = 1: one launch packs all rows into the query's device buffer (result_pack.hip), one copy brings the tuples
-// into its pinned buffer, and an ORDER BY above runs over them there.  q.hMatCols is neither filled nor read.  False: the host path
-// follows over q.dMatCols - they are untouched - and the report says why.
-static bool resultPackOnDevice(Query& q) {
-    Context& ctx = q.ctx;
-    auto& st = q.resultPack;
-    rsq_result_pack_report& r = st.report;
-    if (ctx.resultPack != 1) return false;
-    r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_SHAPE;
-    if (!r.planned || q.holdTail || q.subQuery || q.dMatCols.size() != q.matSchema.size()) return false;
-    std::vector<Type> types;
-    for (auto& a : q.matSchema) types.push_back(a.type);
-    const int64_t n = q.matRows, ts = packTupleSize(types);
-    bool mapped = false;          // (allocMatCols' form for small capacities: the host has the cells when the stream completes)
-    for (void* m : q.hMatMapped) mapped = mapped || m != nullptr;
-    if (n <= 0 || mapped) { r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_SMALL; return false; }
-    const size_t bytes = (size_t)n * (size_t)ts;          // (at most rpack::MAX_TUPLE_BYTES where fitsDevice says yes)
-    int64_t freeBytes = INT64_MAX;          // what the query holds already is not asked for again
-    if (st.devBytes < bytes) {
-        size_t freeNow = 0, total = 0;
-        RSQ_HIP(hipMemGetInfo(&freeNow, &total));
-        freeBytes = (int64_t)std::min<size_t>(freeNow, (size_t)INT64_MAX);
-    }
-    if (!rpack::fitsDevice(n, ts, freeBytes)) { r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_DOES_NOT_FIT; return false; }
-    q.resultInPinned = false; q.resultDev = nullptr; q.resultRows = 0;          // the last result's tuples go with their buffers' contents
-    if (st.devBytes < bytes) {
-        if (st.dev) ctx.free(st.dev);
-        st.dev = nullptr; st.devBytes = 0;
-        st.dev = (uint8_t*)ctx.alloc(bytes);
-        st.devBytes = bytes;
-    }
-    if (st.pinnedBytes < bytes) {
-        if (st.pinned) ctx.freePinned(st.pinned);
-        st.pinned = nullptr; st.pinnedBytes = 0;
-        st.pinned = (uint8_t*)ctx.allocPinned(bytes);
-        st.pinnedBytes = bytes;
-    }
-    if (!st.ev0) st.ev0 = ctx.takeEvent();
-    if (!st.ev1) st.ev1 = ctx.takeEvent();
-    RSQ_HIP(hipEventRecord(st.ev0, ctx.stream));
-    packTuples(ctx, types, q.dMatCols.data(), n, st.dev);
-    RSQ_HIP(hipEventRecord(st.ev1, ctx.stream));
-    q.report.num_kernels += 1;
-    const double t0 = nowMs();
-    RSQ_HIP(hipMemcpyAsync(st.pinned, st.dev, bytes, hipMemcpyDeviceToHost, ctx.stream));
-    uint32_t err = 0;
-    RSQ_HIP(hipMemcpyAsync(&err, ctx.dErr, 4, hipMemcpyDeviceToHost, ctx.stream));
-    waitForStream(ctx);
-    r.copy_ms = nowMs() - t0;
-    if (err) { ctx.errWordClean = false; checkDeviceError(err); }
-    float ms = 0;
-    RSQ_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
-    r.kernel_ms = ms;
-    q.tailNeedsAllGroups = false;
-    q.resultSchema = q.matSchema;
-    int64_t rows = n;
-    const double t1 = nowMs();
-    const bool sorted = runMaterializeSort(q, st.pinned, rows);
-    if (sorted) r.sort_ms = nowMs() - t1;
-    q.resultRows = rows;
-    q.resultPinned = st.pinned;
-    q.resultInPinned = true;
-    q.resultDev = sorted ? nullptr : st.dev;      // (sorted on the host: the device's tuples are not the result's order)
-    r.path = 1; r.fallback_reason = RSQ_RESULT_PACK_FALLBACK_NONE; r.sorted_on_host = sorted ? 1 : 0;
-    r.tuple_size = (int32_t)ts; r.rows = rows; r.tuple_bytes = rows * ts;
-    return true;
-}
-
-// An ORDER BY directly above a materialisation whose columns stand complete in q.dMatCols (whichever tier wrote them), under
-// rsq_ctx_set_order_sort = 1: the device orders the rows by the whole key list (order_sort.hip orderSortRows), packs all rows in scan
-// order, gathers the result's tuples in the order and one copy brings them, with the tie count, into the query's pinned buffer.
-// q.hMatCols is neither filled nor read.  False: the host path follows over q.dMatCols - they are untouched, as is the result state - and
-// the report says why.
-static bool orderSortOnDevice(Query& q) {
-    Context& ctx = q.ctx;
-    auto& st = q.orderSort;
-    rsq_order_sort_report& r = st.report;
-    if (ctx.orderSort != 1) return false;
-    r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_SHAPE;
-    if (!r.planned || q.holdTail || q.subQuery || q.dMatCols.size() != q.matSchema.size()) return false;
-    std::vector<Type> types;
-    for (auto& a : q.matSchema) types.push_back(a.type);
-    const int64_t n = q.matRows, ts = packTupleSize(types);
-    const bool hasLimit = q.root->hasLimit;
-    const int64_t lead = hasLimit ? std::min<int64_t>(n, q.root->limit + 1) : n;          // (runOrderLimitTail's rule: ties behind row k + 1 do not matter)
-    const int64_t outRows = hasLimit ? std::min<int64_t>(n, q.root->limit) : n;
-    r.rows = n; r.lead = std::max<int64_t>(lead, 0); r.out_rows = std::max<int64_t>(outRows, 0); r.tuple_size = (int32_t)ts;
-    bool mapped = false;          // (allocMatCols' form for small capacities: the host has the cells when the stream completes)
-    for (void* m : q.hMatMapped) mapped = mapped || m != nullptr;
-    if (n <= 0 || mapped) { r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_SMALL; return false; }
-    const size_t scanBytes = n < ((int64_t)1 << 32) ? (size_t)n * (size_t)ts : 0, outBytes = (size_t)outRows * (size_t)ts;
-    int64_t freeBytes = INT64_MAX;          // what the query holds already is not asked for again
-    if (st.buffers.rows < n || st.scanBytes < scanBytes || st.outBytes < outBytes) {
-        size_t freeNow = 0, total = 0;
-        RSQ_HIP(hipMemGetInfo(&freeNow, &total));
-        freeBytes = (int64_t)std::min<size_t>(freeNow, (size_t)INT64_MAX);
-    }
-    if (!osort::fitsDevice(n, outRows, ts, n < ((int64_t)1 << 32) ? (int64_t)radixSortTempBytes(n) : 0, freeBytes)) { r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_DOES_NOT_FIT; return false; }
-    st.buffers.ensure(ctx, n);
-    std::vector<OrderSortKey> keys;
-    for (size_t k = 0; k < st.keyCols.size(); k++) {
-        const size_t c = (size_t)st.keyCols[k];
-        keys.push_back(OrderSortKey{q.dMatCols[c], columnWidth(q.matSchema[c].type), (bool)st.keyDesc[k]});
-    }
-    OrderSortOutcome o;
-    orderSortRows(ctx, st.buffers, keys.data(), (int)keys.size(), n, lead, o);
-    q.report.num_kernels += (uint32_t)o.launches;
-    for (int k = 0; k < 8; k++) r.key_bits[k] = o.bits[k];
-    r.total_bits = o.totalBits; r.words = o.words; r.passes = o.passes;
-    float ms = 0;
-    if (!o.sorted) {          // no key varies: every leading pair ties
-        RSQ_HIP(hipEventSynchronize(st.buffers.ev[1]));
-        RSQ_HIP(hipEventElapsedTime(&ms, st.buffers.ev[0], st.buffers.ev[1])); r.range_ms = ms;
-        r.tied_pairs = o.tiedPairs; r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_TIES;
-        return false;
-    }
-    // the last execution's tuples go with these buffers' contents where the result state names them; whichever path this execution ends
-    // on sets the state anew
-    if (q.resultInPinned && q.resultPinned == st.pinned) { q.resultInPinned = false; q.resultDev = nullptr; q.resultRows = 0; }
-    if (st.scanBytes < scanBytes) {
-        if (st.dScan) ctx.free(st.dScan);
-        st.dScan = nullptr; st.scanBytes = 0;
-        st.dScan = (uint8_t*)ctx.alloc(std::max<size_t>(scanBytes, 16));
-        st.scanBytes = scanBytes;
-    }
-    if (!st.dOut || st.outBytes < outBytes) {
-        if (st.dOut) ctx.free(st.dOut);
-        st.dOut = nullptr; st.outBytes = 0;
-        st.dOut = (uint8_t*)ctx.alloc(std::max<size_t>(outBytes, 16));
-        st.outBytes = outBytes;
-    }
-    if (!st.pinned || st.pinnedBytes < outBytes + 16) {
-        if (st.pinned) ctx.freePinned(st.pinned);
-        st.pinned = nullptr; st.pinnedBytes = 0;
-        st.pinned = (uint8_t*)ctx.allocPinned(outBytes + 16);
-        st.pinnedBytes = outBytes + 16;
-    }
-    hipEvent_t* ev = st.buffers.ev;
-    packTuples(ctx, types, q.dMatCols.data(), n, st.dScan);
-    RSQ_HIP(hipEventRecord(ev[4], ctx.stream));
-    gatherTuples(ctx, st.dScan, st.dOut, o.dPerm, (int)ts, outRows);
-    RSQ_HIP(hipEventRecord(ev[5], ctx.stream));
-    q.report.num_kernels += outRows > 0 ? 2 : 1;
-    const double t0 = nowMs();
-    // the tuples first, the tie count and the error word behind them in the pinned buffer: one wait
-    uint8_t* status = st.pinned + ((outBytes + 7) & ~(size_t)7);
-    if (outBytes) RSQ_HIP(hipMemcpyAsync(st.pinned, st.dOut, outBytes, hipMemcpyDeviceToHost, ctx.stream));
-    if (lead > 1) RSQ_HIP(hipMemcpyAsync(status, o.dTies, 4, hipMemcpyDeviceToHost, ctx.stream));
-    RSQ_HIP(hipMemcpyAsync(status + 4, ctx.dErr, 4, hipMemcpyDeviceToHost, ctx.stream));
-    waitForStream(ctx);
-    r.copy_ms = nowMs() - t0;
-    uint32_t ties = 0, err = 0;
-    if (lead > 1) memcpy(&ties, status, 4);
-    memcpy(&err, status + 4, 4);
-    if (err) { ctx.errWordClean = false; checkDeviceError(err); }
-    RSQ_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); r.range_ms = ms;
-    RSQ_HIP(hipEventElapsedTime(&ms, ev[2], ev[3])); r.sort_ms = ms;
-    RSQ_HIP(hipEventElapsedTime(&ms, ev[3], ev[4])); r.pack_ms = ms;
-    RSQ_HIP(hipEventElapsedTime(&ms, ev[4], ev[5])); r.gather_ms = ms;
-    r.tied_pairs = ties;
-    if (ties) { r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_TIES; return false; }
-    q.tailNeedsAllGroups = false;
-    q.resultSchema = q.matSchema;
-    q.resultRows = outRows;
-    q.resultPinned = st.pinned;
-    q.resultInPinned = true;
-    q.resultDev = st.dOut;
-    r.path = 1; r.fallback_reason = RSQ_ORDER_SORT_FALLBACK_NONE;
-    return true;
-}
-
 void fetchHeldGroupRows(Query& q) {
     if (q.nGroupRows <= 0) return;
     ensureHostGroupRows(q, (size_t)q.nGroupRows * (size_t)q.groupRowWords);
@@ -1169,26 +946,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
     double t0 = nowMs();
     const size_t words = q.pinnedWords;
     q.report.num_kernels = 0; q.report.bytes_read = 0;
-    {   // the execution's part of the ORDER BY ... LIMIT report: the host path, under setting 1 for want of the shape until orderLimitOnDevice says otherwise
-        rsq_order_limit_report& r = q.orderLimit.report;
-        r.path = 0; r.fallback_reason = ctx.orderLimit == 1 ? RSQ_ORDER_LIMIT_FALLBACK_SHAPE : RSQ_ORDER_LIMIT_FALLBACK_NONE;
-        r.rows = r.want = r.candidates = r.capacity = 0;
-        r.select_ms = r.copy_ms = r.tail_ms = 0;
-    }
-    {   // ... and of the result-pack report: likewise - held tails, partial executions and sub-queries never reach resultPackOnDevice
-        rsq_result_pack_report& r = q.resultPack.report;
-        r.path = 0; r.fallback_reason = ctx.resultPack == 1 ? RSQ_RESULT_PACK_FALLBACK_SHAPE : RSQ_RESULT_PACK_FALLBACK_NONE;
-        r.sorted_on_host = 0; r.tuple_size = 0; r.rows = r.tuple_bytes = 0;
-        r.kernel_ms = r.copy_ms = r.sort_ms = 0;
-    }
-    {   // ... and of the order-sort report: likewise
-        rsq_order_sort_report& r = q.orderSort.report;
-        r.path = 0; r.fallback_reason = ctx.orderSort == 1 ? RSQ_ORDER_SORT_FALLBACK_SHAPE : RSQ_ORDER_SORT_FALLBACK_NONE;
-        for (int k = 0; k < 8; k++) r.key_bits[k] = 0;
-        r.total_bits = r.words = r.passes = r.tuple_size = 0;
-        r.rows = r.lead = r.out_rows = r.tied_pairs = 0;
-        r.range_ms = r.sort_ms = r.pack_ms = r.gather_ms = r.copy_ms = 0;
-    }
+    resetMaterializeReports(q);
     runSubQueries(q);
     if (!q.genericActive && q.quickTier && q.bgState.load() >= 3) {
         // the full kernels are in the cache now: the quick tier's are replaced (same arguments, same tables - nothing else changes).
@@ -1892,23 +1650,7 @@ static void executeQueryBody(Query& q, bool partialOnly, bool async) {
         }
         if (denseMode(q)) tableFromPinned(q);
         else if (q.matOp && !q.agg) {
-            if (orderLimitOnDevice(q)) {          // (rsq_ctx_set_order_limit: the candidates decided the answer, no column travels whole)
-                if (ctx.resultPack == 1) q.resultPack.report.fallback_reason = RSQ_RESULT_PACK_FALLBACK_ORDER_LIMIT;      // (no materialised row is packed at all)
-                if (ctx.orderSort == 1) q.orderSort.report.fallback_reason = RSQ_ORDER_SORT_FALLBACK_ORDER_LIMIT;      // (... and none is sorted)
-                resultPackHostRelation(q);
-                q.report.finalize_time_ms = nowMs() - t1;
-                q.report.execution_time_ms = nowMs() - t0;
-                execTrace();
-                return;
-            }
-            if (orderSortOnDevice(q)) {          // (rsq_ctx_set_order_sort: the device ordered the rows and made the result's tuples, copied once)
-                resultPackHostRelation(q);          // (result_pack's report keeps SHAPE under its setting 1: this path did the packing)
-                q.report.finalize_time_ms = nowMs() - t1;
-                q.report.execution_time_ms = nowMs() - t0;
-                execTrace();
-                return;
-            }
-            if (resultPackOnDevice(q)) {          // (rsq_ctx_set_result_pack: the tuples are made on the device and copied once)
+            if (runMaterializeDeviceTail(q)) {          // (a device tail made the result relation: no column travels whole)
                 q.report.finalize_time_ms = nowMs() - t1;
                 q.report.execution_time_ms = nowMs() - t0;
                 execTrace();
@@ -2213,19 +1955,10 @@ void queryReport(const Query& q, rsq_report* out) {
     resolveKernelTime(const_cast<Query&>(q));
     *out = q.report;
 }
-void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out) { *out = q.orderLimit.report; }
-void queryResultPackReport(const Query& q, rsq_result_pack_report* out) { *out = q.resultPack.report; }
-void queryOrderSortReport(const Query& q, rsq_order_sort_report* out) { *out = q.orderSort.report; }
-const uint8_t* queryResultDeviceTuples(const Query& q) {
-    // (the query-owned pack buffer only: the aggregation tails' buffers are arena space another statement may be handed)
-    // (the query-owned buffers only - the pack buffer, the device sort's ordered tuples)
-    return q.resultInPinned && q.resultDev && (q.resultDev == q.resultPack.dev || q.resultDev == q.orderSort.dOut) ? q.resultDev : nullptr;
-}
 int32_t queryNestedLoopsSlices(const Query& q) {
     for (const NljState& n : q.nljs) if (n.sub.query && n.outerSrc) return n.slices;      // (the top one: the others run inside its inner side)
     return 0;
 }
-
 void queryKernelTimeStats(Query& q, double* sumMs, uint64_t* executions, bool reset) {
     resolveKernelTime(q);
     if (sumMs) *sumMs = q.kernelTimeSumMs;

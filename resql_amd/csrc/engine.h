@@ -501,9 +501,9 @@ void mergeGathered(Query& q, const void* gathered, int nRanks);
 void partialBuffer(Query& q, void** dptr, int64_t* nMin, int64_t* nMax, int64_t* nSum);
 void queryResult(Query& q, rsq_result_view* out);
 void queryReport(const Query& q, rsq_report* out);
-void queryOrderLimitReport(const Query& q, rsq_order_limit_report* out);      // (struct_size is the caller's business: api.cpp)
-void queryResultPackReport(const Query& q, rsq_result_pack_report* out);      // (likewise)
-void queryOrderSortReport(const Query& q, rsq_order_sort_report* out);        // (likewise)
+void queryReport(const Query& q, rsq_order_limit_report* out);      // the last execution's (struct_size is the caller's business: api.cpp)
+void queryReport(const Query& q, rsq_result_pack_report* out);      // (likewise)
+void queryReport(const Query& q, rsq_order_sort_report* out);       // (likewise)
 // the result view's tuples in device memory, in the view's order, where the materialisation's device tail left them (rsq_ctx_set_result_pack,
 // rsq_ctx_set_order_sort);
 // null: they are on the host only.  Valid until the query's next execution or its destruction.

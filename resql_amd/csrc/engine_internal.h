@@ -418,19 +418,19 @@ struct Query {
     bool matWarmRun = false;               // waiting for the total; the total then arrives with the status words and must equal the remembered one
     const uint64_t* dMatTotal = nullptr;   // (where it stands: the last offset of the scan)
     std::vector<std::vector<uint8_t>> hMatCols;
-    // ORDER BY ... LIMIT k at the root, decided from candidates selected on the device (rsq_ctx_set_order_limit; tail.cpp planOrderLimit,
-    // engine.cpp orderLimitOnDevice, order_limit.hip): the report's plan fields are set when the statement is compiled, the others by every execution
-    struct { rsq_order_limit_report report{}; OrderLimitBuffers buffers; } orderLimit;
-    // the materialisation's device tail (rsq_ctx_set_result_pack; engine.cpp resultPackOnDevice, result_pack.hip): `planned` is set when the
-    // statement is compiled, the rest by every execution.  dev and pinned hold the packed tuples; they are the context's arenas', kept
-    // between executions, grown on demand and given back with the query - so q.resultDev == dev stays valid until this query's next execution
-    struct { rsq_result_pack_report report{}; uint8_t* dev = nullptr; size_t devBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0;
+    // The device tails of a materialisation (engine_mattail.cpp): of each, `plan` is the report as the statement's compilation leaves it
+    // (planMaterializeTails) and `report` the last execution's, which begins as a copy of `plan` (resetMaterializeReports).  The buffers are
+    // the context's arenas', kept between executions, grown on demand and given back with the query (releaseMaterializeTails).
+    // ORDER BY ... LIMIT k at the root, decided from candidates selected on the device (rsq_ctx_set_order_limit; tail.cpp planOrderLimit, order_limit.hip)
+    struct { rsq_order_limit_report plan{}, report{}; OrderLimitBuffers buffers; } orderLimit;
+    // the pack of the result's tuples (rsq_ctx_set_result_pack; result_pack.hip): dev and pinned hold the packed tuples, so q.resultDev == dev
+    // stays valid until this query's next execution
+    struct { rsq_result_pack_report plan{}, report{}; uint8_t* dev = nullptr; size_t devBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0;
              hipEvent_t ev0 = nullptr, ev1 = nullptr; } resultPack;
-    // ORDER BY above the materialisation, sorted on the device (rsq_ctx_set_order_sort; tail.cpp planOrderSort, engine.cpp orderSortOnDevice,
-    // order_sort.hip): `planned`, `keys` and keyCols / keyDesc are set when the statement is compiled, the rest by every execution.  dScan holds
-    // the tuples in scan order, dOut and pinned the result's; all are the context's arenas', kept between executions, grown on demand and
-    // given back with the query - so q.resultDev == dOut stays valid until this query's next execution
-    struct { rsq_order_sort_report report{}; OrderSortBuffers buffers; std::vector<int> keyCols; std::vector<bool> keyDesc;
+    // ORDER BY above the materialisation, sorted on the device (rsq_ctx_set_order_sort; tail.cpp planOrderSort, order_sort.hip): keyCols / keyDesc
+    // are the plan's too.  dScan holds the tuples in scan order, dOut and pinned the result's, so q.resultDev == dOut stays valid until this
+    // query's next execution
+    struct { rsq_order_sort_report plan{}, report{}; OrderSortBuffers buffers; std::vector<int> keyCols; std::vector<bool> keyDesc;
              uint8_t* dScan = nullptr; size_t scanBytes = 0; uint8_t* dOut = nullptr; size_t outBytes = 0; uint8_t* pinned = nullptr; size_t pinnedBytes = 0; } orderSort;
     bool subQuery = false;                 // compiled by compileSubQuery: a nested-loops inner side or a derived table, whose packed result nobody reads from the device tail
 
@@ -596,11 +596,12 @@ void runRowsTailSort(Query& q, uint8_t* tuples, int64_t& rows);
 // tail.cpp: is the first ORDER BY key of an `ORDER BY ... LIMIT k` above the aggregation one word of the group rows?
 void planDeviceTopK(Query& q);
 // tail.cpp: is the plan an ORDER BY ... LIMIT k over a materialisation whose first key the device can order?  (the report's plan fields)
-void planOrderLimit(Query& q);
-// tail.cpp: is the plan an ORDER BY directly above a materialisation whose every key the device can order?  (the report's plan fields, the key columns)
-void planOrderSort(Query& q);
+rsq_order_limit_report planOrderLimit(const Query& q);
+// tail.cpp: is the plan an ORDER BY directly above a materialisation whose every key the device can order?  (the report's plan fields; the
+// key columns go to q.orderSort.keyCols / keyDesc)
+rsq_order_sort_report planOrderSort(Query& q);
 // tail.cpp: the ORDER BY above the materialisation (if any) over its packed tuples in place - the reference's quicksort, then the LIMIT
-// cuts `rows`.  True: there is one.  Both tails of a materialisation call it: the host's and the device's (engine.cpp resultPackOnDevice).
+// cuts `rows`.  True: there is one.  Both tails of a materialisation call it: the host's and the device's (engine_mattail.cpp resultPackOnDevice).
 bool runMaterializeSort(Query& q, uint8_t* tuples, int64_t& rows);
 // tail.cpp: the answer from the candidates' columns, or false where rows among the leading k + 1 tie on every key
 bool runOrderLimitTail(Query& q, const uint8_t* const* candCols, size_t nCand);
@@ -647,6 +648,13 @@ double runDenseDeviceTail(Query& q);
 bool rowsDeviceTailWanted(Query& q, int64_t n);
 double runRowsDeviceTail(Query& q, int64_t n, const int64_t* groupRows = nullptr);      // (groupRows: rows other than q.dGroupRows, same layout)
 void fetchHeldGroupRows(Query& q);        // the group rows a held tail left on the device, to q.hGroupRows (engine.cpp)
+// ---- engine_mattail.cpp: the device tails of a materialisation without an aggregation (order_limit, order_sort, result_pack) ------
+void planMaterializeTails(Query& q);           // compileQuery: the three reports' plan fields
+void resetMaterializeReports(Query& q);        // every execution's start: report = plan, SHAPE under a setting of 1
+// executeQuery, the columns complete in q.dMatCols.  True: a device tail made the result relation; false: the host reads the columns back
+bool runMaterializeDeviceTail(Query& q);
+void resultPackHostRelation(Query& q);         // behind the host's tail: the relation's size in result_pack's report
+void releaseMaterializeTails(Query& q);        // ~Query
 // engine.cpp: sub-queries (SubQuery).  runSubQuery executes one and records its work; buildDerived runs a derived table's sub-query and
 // writes the table; writeDerivedFrom writes d's columns on q's context from s's packed tuples (d's own sub-query's, or the root's after
 // a merge across shards), adding the writer's work to d.sub's.  The nested-loops steps: the plan's top-level join (multi.cpp accepts no

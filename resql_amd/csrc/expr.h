@@ -44,6 +44,9 @@ bool equalTypes(const Type& a, const Type& b);           // types.h:153-173
 std::string serializeType(const Type& t);                // types.h:121-150
 int sizeInTuple(const Type& t, bool stringsByVal);       // types.h:213-261
 int columnWidth(const Type& t);                          // bytes per row of a device column
+// the cell width at which the device orders a column (order_limit.h image): INT / DATE as signed 32 bits, BIGINT / DECIMAL as signed 64
+// bits - the order of compareTyped; 0: a type it does not order
+inline int deviceOrderWidth(const Type& t) { return t.tag == RSQ_INT || t.tag == RSQ_DATE ? 4 : t.isInt64() ? 8 : 0; }
 
 enum Structure { LITERAL, UNARY, BINARY, TERNARY, OTHER };
 

@@ -395,61 +395,64 @@ static void runMaterializeTail(Query& q) {
     if (runMaterializeSort(q, q.resultTuples.data(), q.resultRows)) q.resultTuples.resize((size_t)q.resultRows * ts);
 }
 
-// `ORDER BY ... LIMIT k` at the root of a plan WITHOUT an aggregation (rsq_ctx_set_order_limit): can the rows that decide the answer be
-// selected on the device from the materialised columns (order_limit.hip)?  The first sort key must be a materialised attribute the
-// device can order - INT / DATE as signed 32 bits, BIGINT / DECIMAL as signed 64 bits, the order of compareTyped; any other first key
-// (a string, BOOL, CHAR(1)) keeps the host path, and a name the materialisation does not hold keeps the reference's error.  Later keys
-// may be of any type: the host compares them.  Fills the compile-time fields of the query's report.
-void planOrderLimit(Query& q) {
-    rsq_order_limit_report& r = q.orderLimit.report;
-    r = rsq_order_limit_report{};
-    r.first_key_column = -1;
-    if (q.agg || !q.matOp || !q.root || q.root->tag != RSQ_OP_ORDERBY || q.matOp->parent != q.root) return;
-    const OpNode* orderBy = q.root;
-    if (!orderBy->hasLimit || orderBy->limit < 0 || orderBy->limit > (1 << 20) || q.matOp->hasLimit || orderBy->exprs.empty()) return;
-    if (q.matSchema.empty() || q.matSchema.size() > (size_t)ORDER_LIMIT_MAX_COLUMNS) return;
-    const Expr* first = orderBy->exprs[0];
-    if (!first->child) return;
-    for (size_t c = 0; c < q.matSchema.size(); c++) {
-        if (q.matSchema[c].name != first->child->symbol) continue;
-        const Type& t = q.matSchema[c].type;
-        if (t.tag == RSQ_INT || t.tag == RSQ_DATE) r.key_is32 = 1;
-        else if (t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) return;
-        r.first_key_column = (int32_t)c;
-        r.descending = first->tag == RSQ_E_DESC;
-        r.planned = 1;
-        return;
-    }
+// What rsq_ctx_set_order_limit and rsq_ctx_set_order_sort plan for: the ORDER BY at the root of a plan WITHOUT an aggregation, directly
+// above the materialisation, which has no LIMIT of its own - or null
+static const OpNode* rootOrderByOverMaterialisation(const Query& q) {
+    if (q.agg || !q.matOp || !q.root || q.root->tag != RSQ_OP_ORDERBY || q.matOp->parent != q.root) return nullptr;
+    if (q.matOp->hasLimit || q.root->exprs.empty() || q.matSchema.empty()) return nullptr;
+    return q.root;
 }
 
-// ORDER BY at the root of a plan WITHOUT an aggregation, directly above the materialisation, with any LIMIT or none
-// (rsq_ctx_set_order_sort): can the device order the rows by the whole key list (order_sort.hip)?  Every key must be, as
-// materializeOrderRequests resolves it - by name, the first attribute that carries it -, a materialised attribute the device can order:
-// INT / DATE as signed 32 bits, BIGINT / DECIMAL as signed 64 bits, the order of compareTyped.  A string, CHAR(1) or BOOL key anywhere in
-// the list keeps the host path (compareTyped orders strings by (int)(int8_t)strcmp(...), which is not a byte order and is not restated),
-// and a name the materialisation does not hold keeps the reference's error.  Fills the compile-time fields of the query's report.
-void planOrderSort(Query& q) {
-    rsq_order_sort_report& r = q.orderSort.report;
-    r = rsq_order_sort_report{};
+// A sort key as materializeOrderRequests resolves it - by name, the first attribute that carries it - where that is a materialised
+// column the device can order (deviceOrderWidth): its index and the cell's 4 or 8 bytes.  False for any other key: a string, BOOL or
+// CHAR(1) keeps the host path (compareTyped orders strings by (int)(int8_t)strcmp(...), which is not a byte order and is not restated),
+// and a name the materialisation does not hold keeps the reference's error.
+static bool deviceOrderedColumn(const Query& q, const Expr* key, int& column, int& width) {
+    if (!key->child) return false;
+    for (size_t c = 0; c < q.matSchema.size(); c++) {
+        if (q.matSchema[c].name != key->child->symbol) continue;
+        column = (int)c;
+        width = deviceOrderWidth(q.matSchema[c].type);
+        return width != 0;
+    }
+    return false;
+}
+
+// `ORDER BY ... LIMIT k` (rsq_ctx_set_order_limit): can the rows that decide the answer be selected on the device from the materialised
+// columns (order_limit.hip)?  Only the first sort key must be one the device orders; later keys may be of any type: the host compares
+// them.  The compile-time fields of the query's report.
+rsq_order_limit_report planOrderLimit(const Query& q) {
+    rsq_order_limit_report r{};
+    r.first_key_column = -1;
+    const OpNode* orderBy = rootOrderByOverMaterialisation(q);
+    if (!orderBy || !orderBy->hasLimit || orderBy->limit < 0 || orderBy->limit > (1 << 20) || q.matSchema.size() > (size_t)ORDER_LIMIT_MAX_COLUMNS) return r;
+    int column = 0, width = 0;
+    if (!deviceOrderedColumn(q, orderBy->exprs[0], column, width)) return r;
+    r.first_key_column = column;
+    r.key_is32 = width == 4;
+    r.descending = orderBy->exprs[0]->tag == RSQ_E_DESC;
+    r.planned = 1;
+    return r;
+}
+
+// ORDER BY with any LIMIT or none (rsq_ctx_set_order_sort): can the device order the rows by the whole key list (order_sort.hip)?  Every
+// key must be one the device orders.  The compile-time fields of the query's report; the keys' columns go to q.orderSort.
+rsq_order_sort_report planOrderSort(Query& q) {
+    rsq_order_sort_report r{};
     q.orderSort.keyCols.clear(); q.orderSort.keyDesc.clear();
-    if (q.agg || !q.matOp || !q.root || q.root->tag != RSQ_OP_ORDERBY || q.matOp->parent != q.root) return;
-    const OpNode* orderBy = q.root;
-    if ((orderBy->hasLimit && orderBy->limit < 0) || q.matOp->hasLimit || orderBy->exprs.empty() || orderBy->exprs.size() > (size_t)osort::MAX_KEYS) return;
-    if (q.matSchema.empty() || q.matSchema.size() > (size_t)rpack::MAX_COLUMNS) return;
+    const OpNode* orderBy = rootOrderByOverMaterialisation(q);
+    if (!orderBy || (orderBy->hasLimit && orderBy->limit < 0) || orderBy->exprs.size() > (size_t)osort::MAX_KEYS || q.matSchema.size() > (size_t)rpack::MAX_COLUMNS) return r;
     std::vector<int> cols;
     std::vector<bool> desc;
     for (const Expr* e : orderBy->exprs) {
-        if (!e->child) return;
-        int at = -1;
-        for (size_t c = 0; c < q.matSchema.size() && at < 0; c++) if (q.matSchema[c].name == e->child->symbol) at = (int)c;
-        if (at < 0) return;
-        const Type& t = q.matSchema[(size_t)at].type;
-        if (t.tag != RSQ_INT && t.tag != RSQ_DATE && t.tag != RSQ_BIGINT && t.tag != RSQ_DECIMAL) return;
-        cols.push_back(at); desc.push_back(e->tag == RSQ_E_DESC);
+        int column = 0, width = 0;
+        if (!deviceOrderedColumn(q, e, column, width)) return r;
+        cols.push_back(column); desc.push_back(e->tag == RSQ_E_DESC);
     }
     q.orderSort.keyCols = cols; q.orderSort.keyDesc = desc;
     r.keys = (int32_t)cols.size();
     r.planned = 1;
+    return r;
 }
 
 // The decision of runTailOn's candidate path over the rows the device selected: candCols are the candidates' cells of every

@@ -45,19 +45,31 @@ class rsq_report(C.Structure):
                 ("jit_cache_hits", C.c_int32), ("jit_compiles", C.c_int32)]
 
 
+class _Report(C.Structure):
+    """a report struct of the C ABI as a dict: struct_size and the reserved fields dropped, arrays as lists"""
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size" and not k.startswith("reserved")}
+        return {k: list(v) if isinstance(v, C.Array) else v for k, v in d.items()}
+
+
+def _report_of(ctx, cls, fn: str, handle) -> dict:
+    """the report `cls` that the library's `fn` fills for a query or database handle, as a dict"""
+    r = cls(C.sizeof(cls))
+    ctx._check(getattr(ctx._L, fn)(handle, C.byref(r)))
+    return r.as_dict()
+
+
 class rsq_tbl_load_options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_bytes", C.c_int64), ("max_device_text_bytes", C.c_int64)]
 
 
-class rsq_tbl_load_report(C.Structure):
+class rsq_tbl_load_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("reserved", C.c_int32),
                 ("rows", C.c_int64), ("text_bytes", C.c_int64), ("lines_patched", C.c_int64),
                 ("read_ms", C.c_double), ("copy_ms", C.c_double), ("kernel_ms", C.c_double), ("patch_ms", C.c_double),
                 ("stats_ms", C.c_double), ("total_ms", C.c_double),
                 ("count_kernel_ms", C.c_double), ("starts_kernel_ms", C.c_double), ("parse_kernel_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
 
 
 TBL_HOST, TBL_DEVICE = 1, 2      # rsq_tbl_load_options.mode (0: the context's tbl_ingest)
@@ -69,14 +81,11 @@ class rsq_rowstore_options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_bytes", C.c_int64)]
 
 
-class rsq_rowstore_report(C.Structure):
+class rsq_rowstore_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("reserved", C.c_int32),
                 ("rows", C.c_int64), ("tuple_bytes", C.c_int64), ("chunks", C.c_int64),
                 ("stage_ms", C.c_double), ("copy_ms", C.c_double), ("kernel_ms", C.c_double), ("transpose_ms", C.c_double),
                 ("stats_ms", C.c_double), ("total_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
 
 
 ROWSTORE_HOST, ROWSTORE_DEVICE = 1, 2      # rsq_rowstore_options.mode (0: the context's set_rowstore_bridge)
@@ -88,13 +97,10 @@ class rsq_result_text_options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("chunk_rows", C.c_int64), ("max_device_bytes", C.c_int64)]
 
 
-class rsq_result_text_report(C.Structure):
+class rsq_result_text_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("fallback_reason", C.c_int32), ("tuples_from_device", C.c_int32),
                 ("rows", C.c_int64), ("text_bytes", C.c_int64), ("chunks", C.c_int64),
                 ("upload_ms", C.c_double), ("kernel_ms", C.c_double), ("download_ms", C.c_double), ("total_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
 TEXT_HOST, TEXT_DEVICE = 1, 2      # rsq_result_text_options.mode (0: the context's set_result_text)
@@ -102,14 +108,11 @@ TEXT_HOST, TEXT_DEVICE = 1, 2      # rsq_result_text_options.mode (0: the contex
 TEXT_FALLBACK_NONE, TEXT_FALLBACK_NO_DEVICE, TEXT_FALLBACK_SCHEMA, TEXT_FALLBACK_DOES_NOT_FIT = range(4)
 
 
-class rsq_order_limit_report(C.Structure):
+class rsq_order_limit_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
                 ("first_key_column", C.c_int32), ("key_is32", C.c_int32), ("descending", C.c_int32), ("reserved", C.c_int32),
                 ("rows", C.c_int64), ("want", C.c_int64), ("candidates", C.c_int64), ("capacity", C.c_int64),
                 ("select_ms", C.c_double), ("copy_ms", C.c_double), ("tail_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
 
 
 ORDER_LIMIT_HOST, ORDER_LIMIT_DEVICE = 0, 1      # Context.set_order_limit
@@ -118,13 +121,10 @@ ORDER_LIMIT_HOST, ORDER_LIMIT_DEVICE = 0, 1      # Context.set_order_limit
  ORDER_LIMIT_FALLBACK_TIES) = range(5)
 
 
-class rsq_result_pack_report(C.Structure):
+class rsq_result_pack_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
                 ("sorted_on_host", C.c_int32), ("tuple_size", C.c_int32), ("rows", C.c_int64), ("tuple_bytes", C.c_int64),
                 ("kernel_ms", C.c_double), ("copy_ms", C.c_double), ("sort_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
 RESULT_PACK_HOST, RESULT_PACK_DEVICE = 0, 1      # Context.set_result_pack
@@ -133,17 +133,12 @@ RESULT_PACK_HOST, RESULT_PACK_DEVICE = 0, 1      # Context.set_result_pack
  RESULT_PACK_FALLBACK_ORDER_LIMIT) = range(5)
 
 
-class rsq_order_sort_report(C.Structure):
+class rsq_order_sort_report(_Report):
     _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
                 ("keys", C.c_int32), ("key_bits", C.c_int32 * 8), ("total_bits", C.c_int32), ("words", C.c_int32), ("passes", C.c_int32),
                 ("tuple_size", C.c_int32), ("reserved", C.c_int32), ("rows", C.c_int64), ("lead", C.c_int64), ("out_rows", C.c_int64),
                 ("tied_pairs", C.c_int64), ("range_ms", C.c_double), ("sort_ms", C.c_double), ("pack_ms", C.c_double),
                 ("gather_ms", C.c_double), ("copy_ms", C.c_double)]
-
-    def as_dict(self) -> dict:
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
-        d["key_bits"] = list(self.key_bits)
-        return d
 
 
 ORDER_SORT_HOST, ORDER_SORT_DEVICE = 0, 1      # Context.set_order_sort
@@ -925,23 +920,17 @@ class Query:
     def order_limit_report(self) -> dict:
         """rsq_order_limit_report: whether the plan is an ORDER BY ... LIMIT the device can pre-select for, and for the last execution
         which path decided the answer, why, rows, candidates and the phases"""
-        r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
-        self.ctx._check(self.ctx._L.rsq_query_order_limit_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_order_limit_report, "rsq_query_order_limit_report", self.h)
 
     def order_sort_report(self) -> dict:
         """rsq_order_sort_report: whether the plan is an ORDER BY the device can sort, and for the last execution which side sorted,
         why, the composite key's bits, words and passes, the rows, the tied pairs and the phases"""
-        r = rsq_order_sort_report(C.sizeof(rsq_order_sort_report))
-        self.ctx._check(self.ctx._L.rsq_query_order_sort_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_order_sort_report, "rsq_query_order_sort_report", self.h)
 
     def result_pack_report(self) -> dict:
         """rsq_result_pack_report: whether the plan is a materialisation the device can pack, and for the last execution which side
         packed the result tuples, why, whether the host sorted them, the relation's size and the phases"""
-        r = rsq_result_pack_report(C.sizeof(rsq_result_pack_report))
-        self.ctx._check(self.ctx._L.rsq_query_result_pack_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_result_pack_report, "rsq_query_result_pack_report", self.h)
 
     def kernel_time_stats(self, reset: bool = False):
         """(device ms summed over the executions since the last reset, number of executions)"""
@@ -1014,35 +1003,25 @@ class Database:
     @property
     def load_report(self) -> dict:
         """rsq_tbl_load_report of the last BULK INSERT: which path parsed the file, why, rows, lines patched, phase times"""
-        r = rsq_tbl_load_report(C.sizeof(rsq_tbl_load_report))
-        self.ctx._check(self.ctx._L.rsq_db_load_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_tbl_load_report, "rsq_db_load_report", self.h)
 
     @property
     def result_text_report(self) -> dict:
         """rsq_result_text_report of the last SELECT that `tofile` wrote: which path wrote qres.tbl, why, rows, chunks, phase times"""
-        r = rsq_result_text_report(C.sizeof(rsq_result_text_report))
-        self.ctx._check(self.ctx._L.rsq_db_result_text_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_result_text_report, "rsq_db_result_text_report", self.h)
 
     @property
     def order_limit_report(self) -> dict:
         """rsq_order_limit_report of the last SELECT: which path decided its ORDER BY ... LIMIT, why, rows, candidates, phase times"""
-        r = rsq_order_limit_report(C.sizeof(rsq_order_limit_report))
-        self.ctx._check(self.ctx._L.rsq_db_order_limit_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_order_limit_report, "rsq_db_order_limit_report", self.h)
 
     def order_sort_report(self) -> dict:
         """rsq_order_sort_report of the last SELECT: which side sorted its ORDER BY, why, the composite key, the rows, phase times"""
-        r = rsq_order_sort_report(C.sizeof(rsq_order_sort_report))
-        self.ctx._check(self.ctx._L.rsq_db_order_sort_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_order_sort_report, "rsq_db_order_sort_report", self.h)
 
     def result_pack_report(self) -> dict:
         """rsq_result_pack_report of the last SELECT: which side packed its result tuples, why, the relation's size, phase times"""
-        r = rsq_result_pack_report(C.sizeof(rsq_result_pack_report))
-        self.ctx._check(self.ctx._L.rsq_db_result_pack_report(self.h, C.byref(r)))
-        return r.as_dict()
+        return _report_of(self.ctx, rsq_result_pack_report, "rsq_db_result_pack_report", self.h)
 
     def execute_script(self, text: str):
         res = None

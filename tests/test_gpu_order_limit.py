@@ -1,5 +1,5 @@
 """ORDER BY ... LIMIT over a materialisation decided from candidates the device selects (Context.set_order_limit(1); order_limit.hip,
-engine.cpp orderLimitOnDevice, tail.cpp runOrderLimitTail).  The device path is never compared with itself: every statement is held
+engine_mattail.cpp orderLimitOnDevice, tail.cpp runOrderLimitTail).  The device path is never compared with itself: every statement is held
 against (a) the CPU oracle, text and tuples byte for byte, and (b) the same compiled statement with the setter at 0.  Every case names
 the path and the fallback reason it expects (tests/orderlimitcases.py) - none may fall back silently - and is executed twice, so the
 warm materialisation (its write pass runs with the remembered row total) is covered.  The reference's own answers

@@ -1,4 +1,4 @@
-"""ORDER BY over a materialisation sorted on the device (Context.set_order_sort(1); order_sort.hip, engine.cpp orderSortOnDevice).  The
+"""ORDER BY over a materialisation sorted on the device (Context.set_order_sort(1); order_sort.hip, engine_mattail.cpp orderSortOnDevice).  The
 device path is never compared with itself: every statement is held against (a) the CPU oracle, text and tuples byte for byte, and (b)
 the same compiled statement with the setter at 0, tuples and launches.  Every case names the path and the fallback reason it expects
 (tests/ordersortcases.py) - none may fall back silently - and is executed twice under setting 1, so the warm materialisation and the

@@ -1,4 +1,4 @@
-"""A materialisation's result tuples packed on the device (Context.set_result_pack(1); result_pack.hip, engine.cpp resultPackOnDevice) and
+"""A materialisation's result tuples packed on the device (Context.set_result_pack(1); result_pack.hip, engine_mattail.cpp resultPackOnDevice) and
 read there by the device text (result_text.hip).  The device path is never compared with itself: every statement is held against (a) the
 CPU oracle, tuples and text byte for byte, and (b) the same compiled statement with the setter at 0.  Every case names the path, the
 fallback reason and sorted_on_host it expects (tests/resultpackcases.py) - none may fall back silently - and is executed twice under

@@ -2,7 +2,7 @@
 device ordering the rows (1) against the parent commit.  A development aid, not part of bench.py.
 usage: python tools/order_sort_timing.py [SF] --parent-tree DIR [--parent-commit SHA] [--rounds K] [--repeat N] [--only a,b]
                                          [--out FILE] [--parent-out FILE] [--limit-seconds N]
-DIR is a built checkout of the commit before Context.set_order_sort existed.  Processes run one after the other on one device, the two
+DIR is a built checkout of the parent commit (one that has Context.set_order_sort runs under its setting 0).  Processes run one after the other on one device, the two
 builds alternating, K rounds (default 1) of: the parent, this tree under setting 1, the parent, this tree under setting 0 (what a host
 that never calls the setter runs) - and the parent once more at the end.  One setting per process: an execution on the host path takes
 a second.  Each process generates lineitem and, per statement, executes twice unrecorded and N times (default 5) recorded:
@@ -86,7 +86,7 @@ def measure(tree, label, sf, repeat, only, setting):
         p["result_rows"], p["result_tuple_size"], p["tuples_sha1"] = tuples_digest(ctx, q, P)
         for k in TIMES:
             p[k] = [round(x, 3) for x in (sorted(p[k])[len(p[k]) // 2], min(p[k]), max(p[k]))] if p[k] else None
-        print(json.dumps({"label": label, "statement": name, "sf": sf, "executions": repeat, "setting": setting if has_setter else "parent", "times": p}), flush=True)
+        print(json.dumps({"label": label, "statement": name, "sf": sf, "executions": repeat, "setting": "parent" if label.startswith("parent") or not has_setter else setting, "times": p}), flush=True)
         q.close()
     table.close()
     ctx.close()

@@ -2,7 +2,7 @@
 (Context.set_result_pack(0)) against the device packing them (1) against the parent commit.  A development aid, not part of bench.py.
 usage: python tools/result_pack_timing.py [SF] --parent-tree DIR [--parent-commit SHA] [--rounds K] [--once a,b] [--repeat N] [--only a,b]
                                           [--out FILE] [--parent-out FILE] [--limit-seconds N]
-DIR is a built checkout of the commit before Context.set_result_pack existed.  Processes run one after the other on one device, the
+DIR is a built checkout of the parent commit (one that has Context.set_result_pack runs under its setting 0).  Processes run one after the other on one device, the
 two builds alternating, K rounds (default 1) of: the parent, this tree with the two settings alternating on one compiled query, the
 parent, this tree under setting 0 alone (what a host that never calls the setter runs) - and the parent once more at the end.  The
 host path's time depends on the process (where its pageable buffers lie), so the parent's spread is taken over all its processes.
@@ -111,7 +111,7 @@ def measure(tree, label, sf, repeat, only, want):
 
 def summarise(name, lines):
     mine = [l for l in lines if l["statement"] == name]
-    parent = [l["settings"]["parent"] for l in mine if l["label"].startswith("parent")]
+    parent = [l["settings"].get("parent") or l["settings"]["0"] for l in mine if l["label"].startswith("parent")]
     zero = [l["settings"]["0"] for l in mine if not l["label"].startswith("parent")]
     one = [l["settings"]["1"] for l in mine if "1" in l["settings"]]
     out = {"statement": name, "summary": True, "rows": one[0]["rows"], "tuple_size": one[0]["tuple_size"]}
