@@ -567,7 +567,8 @@ class Result:
             return "true" if v else "false"
         if t.tag == DECIMAL:
             neg = v < 0
-            d = str(-v if neg else v)
+            # (the magnitude is a signed 64-bit negation, as in the engine's and the oracle's writers: the smallest value keeps its own '-')
+            d = str(v if v == -(1 << 63) else -v if neg else v)
             if len(d) <= t.scale:
                 d = "0." + "0" * (t.scale - len(d)) + d
             elif t.scale > 0:
